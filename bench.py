@@ -6,9 +6,12 @@ Workload (BASELINE.json configs[3] / `metric`, at the size one GPU box can build
 31.5 GB RefSeq subset is not reachable offline; the stand-in is a low-redundancy synthetic database (default 1.6 M random base
 sequences x 2 variants at 5 % divergence = 3.2 M references, 4.5 Gbp: every 15-mer has ~4 unrelated list entries, as a
 collision-dominated RefSeq-scale DB15 would have many more), its accelerator BUILT ON THE DEVICE from the .edx (no .acx is read
-or uploaded).  The database is as large as the box holds (--db-scale auto: the metric's own 31.5 GB .edx = 11.37 units on a 288 GB device in a
-300 GB container, with the compiled reference run on it beside the device path); `config.extrapolation.measured_sizes` carries the bench line
-measured at three database sizes up to the metric's own (profiles/r06_sizes.json).
+or uploaded).  A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what its headline needs and no more: it builds the 2.77 GB
+database of rounds 1-3 (--db-scale 1, seconds), warms up, times the N steps, writes --dump-outputs if asked and prints the line.  With
+--full the database is as large as the box holds (--db-scale auto: the metric's own 31.5 GB .edx = 11.37 units on a 288 GB device in a
+300 GB container, with the compiled reference run on it beside the device path) and every other leg below runs as well;
+`config.extrapolation.measured_sizes` carries the bench line measured at three database sizes up to the metric's own
+(profiles/r06_sizes.json).
 
 A step = one batch of reads through the WHOLE device path as the product runs it: bench.py calls the C batch scheduler of
 the `burst_hip` command line (bh_align_ranges, burst_amd/csrc/host/bh_align.c) -- each step's batch is staged afresh from
@@ -20,13 +23,13 @@ single-GPU job of --steps batches is cut into N equal shares of unique queries (
 asks about) through the product's multi-rank search (bh_search_multi_ex); the path partitions, so there is no collective on the
 data path -- every rank's page-locked record buffer is a shared-memory segment rank 0 has mapped (bh_node.c), the hand-over inside
 the timed region is one word per rank and rank 0 reads the records where they lie (`handover` in the JSON line).  Extra keys of the
-N > 1 line: `weak_scaling` (every rank --steps batches of its own), `configs3_job` (10 M reads over the N GPUs), `rccl` (the same job
+N > 1 line with --full: `weak_scaling` (every rank --steps batches of its own), `configs3_job` (10 M reads over the N GPUs), `rccl` (the same job
 with bhip_comm_gather_hits across all N ranks inside the timed region: rccl_ranks, rccl_gather_ms).  torch.distributed only carries the
 job name and the barriers around the timed regions.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel by time on the critical path (HIP events on the stream it runs on);
 `roofline.per_kernel` lists the others with their own bound; PMC-derived traffic / VALU figures come from profiles/
-(tools/profile_round.sh).  `cpu_baseline` is the compiled reference itself (oracle/_ref/burst15, one thread per core of the job's
+(tools/profile_round.sh).  --full adds the keys below.  `cpu_baseline` is the compiled reference itself (oracle/_ref/burst15, one thread per core of the job's
 CPU quota) on a bounded sample of the same reads and database (its .acx is a NAMED PIPE fed from the device-built tables while it reads
 them -- read_accelerator, burst.c:3535-3594, only reads forward -- so the 167 GB accelerator of the metric's database never exists as a file):
 one run, its alignment loops timed between its own progress lines ("Using ACCELERATOR to align" .. "Search complete", burst.c:4048-4525)
@@ -550,6 +553,37 @@ def share_of_job(ranges, rank, world):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_last_step(out_dir, hits, last_range, n_uniq):
+    """--dump-outputs: the records the timed path handed back for its last step -- the batch of unique queries last_range = [u0, u1)
+    (entries u0..u1-1 and, with both strands, their twins n_uniq + u) -- one DIR/<field>.npy per record field, sorted by (q, refIx) as
+    the scheduler delivers them; 32-bit integers as float64 (exact), the rest as float32.  Above DUMP_BYTES a fixed sample of the
+    entries is kept (those with the smallest multiplicative hash of q that fit): every record of a sampled entry"""
+    u0, u1 = last_range
+    q = hits["q"].astype(np.int64)
+    key = (q << 32) | hits["refIx"].astype(np.int64)
+    mine = ((q >= u0) & (q < u1)) | ((q >= n_uniq + u0) & (q < n_uniq + u1))
+    # the batches' records lie one after the other, each sorted by (q, refIx): the last step's are the longest tail of its own entries
+    # over which the key rises (a step that aligns the same range as the one before it starts where the key falls)
+    other = np.flatnonzero(~mine)
+    falls = np.flatnonzero(key[:-1] >= key[1:])
+    first = max(other[-1] + 1 if len(other) else 0, falls[-1] + 1 if len(falls) else 0)
+    last = hits[first:]
+    fields = [(n, np.float64 if last.dtype[n].itemsize == 4 and last.dtype[n].kind == "u" else np.float32) for n in last.dtype.names]
+    per_rec = sum(np.dtype(t).itemsize for _, t in fields)
+    keep = np.ones(len(last), bool)
+    cap = DUMP_BYTES // per_rec
+    if len(last) > cap:
+        h = (last["q"].astype(np.uint64) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)      # (one-to-one on 32-bit q)
+        keep = h < np.partition(h, cap)[cap]
+    os.makedirs(out_dir, exist_ok=True)
+    for n, t in fields:
+        np.save(os.path.join(out_dir, n + ".npy"), last[n][keep].astype(t))
+    log("[bench] --dump-outputs: %d records of the last step (entries of unique queries %d..%d), %d written to %s" % (len(last), u0, u1, int(keep.sum()), out_dir))
+
+
 def parity_vs_reference(dev, db, args, batch_uniq):
     """the reference's .b6 for the cpu_baseline sample against the device path's for the same reads (same database, same flags)"""
     from burst_amd import host
@@ -606,8 +640,15 @@ def main():
     ap.add_argument("--reads", type=int, default=2000000, help="reads per step (per rank with --scaling weak, all GPUs together with --scaling strong)")
     ap.add_argument("--pool", type=int, default=4, help="distinct batches the steps cycle through")
     ap.add_argument("--read-len", type=int, default=100)
-    ap.add_argument("--db-scale", default="auto", help="multiplies --n-base (1 = 3.2 M references / 4.5 Gbp / .edx 2.77 GB; 11.37 = the metric's 31.5 GB .edx); "
-                    "auto (default) = the largest of %s that the device, the host memory and the work directory hold" % (AUTO_SCALES,))
+    ap.add_argument("--db-scale", default=None, help="multiplies --n-base (1 = 3.2 M references / 4.5 Gbp / .edx 2.77 GB; 11.37 = the metric's 31.5 GB .edx); "
+                    "auto = the largest of %s that the device, the host memory and the work directory hold.  Default: 1 (a database "
+                    "built in seconds), auto with --full" % (AUTO_SCALES,))
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the database as large as the box holds (unless --db-scale), the CPU "
+                    "baseline and the parity check against the compiled reference, the command-line run, the small-database and strains legs, the "
+                    "1.25 M-read job, the consolidation pass and, N > 1, the other scaling, configs[3]'s job and the RCCL gather.  The --no-* "
+                    "options below switch single legs of a --full run off")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the records of the last timed step (one .npy per field, float32 / "
+                    "float64, at most 64 MB: a fixed sample of the queries when there are more) to DIR; N = 1 only")
     ap.add_argument("--n-base", type=int, default=1600000, help="random base sequences (round 2's family-dominated database: --n-base 33000 --n-variants 30)")
     ap.add_argument("--n-variants", type=int, default=2)
     ap.add_argument("--db-profile", default="pairs", choices=["pairs", "strains"], help="pairs (default, what the headline is quoted on): every base sequence with --n-variants variants at --variant-rate; "
@@ -643,14 +684,18 @@ def main():
     ap.add_argument("--ab", action="append", default=[], help="N = 1: after the timed region, time the same steps again with these library options (name=value[,name=value]; repeatable) "
                     "on the same resident database -- extra key `ab` of the JSON line, an A/B on one box in one process")
     args = ap.parse_args()
+    if args.db_scale is None:
+        args.db_scale = "auto" if args.full else "1"
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     dist = None
-    import torch
     # BURST_BENCH_DIST1=1 (test hook, under torch.distributed.run with one process): take the N > 1 code path on a single GPU
     use_dist = world > 1 or (os.environ.get("BURST_BENCH_DIST1") == "1" and "MASTER_ADDR" in os.environ)
+    if args.dump_outputs and use_dist:
+        raise SystemExit("--dump-outputs: one process (N = 1) only")
+    import torch
     # BURST_BENCH_DEVICE=<d> (test hook): every rank on device d -- the N > 1 command line of the driver on a one-GPU box.  RCCL
     # refuses two ranks on one device, so the launcher's plumbing (barriers, the max over ranks) is gloo then and the records take
     # the shared-memory hand-over, which needs no communicator
@@ -674,7 +719,7 @@ def main():
     # the size of the database and where its files go: rank 0 decides (from its device's free memory, the host's memory and the
     # room in the work directory), every rank takes its word
     ref_exe = os.path.join(ROOT, "oracle", "_ref", "burst%d" % args.K)
-    want_base = world == 1 and not args.no_cpu_baseline and os.path.exists(ref_exe)
+    want_base = args.full and world == 1 and not args.no_cpu_baseline and os.path.exists(ref_exe)
     try:
         free_hbm = torch.cuda.mem_get_info(local_rank)[0]
     except Exception:
@@ -870,12 +915,14 @@ def main():
         handover_main = {"kind": "view over the ranks' shared-memory segments" if (node is not None and rs.view.n_runs == world and world > 1) else "one array",
                          "records_per_run": [int(len(x)) for x in runs_], "distinct_entries": int(sum(len(np.unique(x["q"])) for x in runs_)),
                          "xor_of_reference_numbers": int(np.bitwise_xor.reduce(np.concatenate([x["refIx"] for x in runs_]))) if sum(len(x) for x in runs_) else 0}
-    # what the records are for: rank 0's consolidation of the timed job's records into .b6 lines (bh_report_view: per-mode selection,
-    # coordinates, formatting), written to /dev/null -- outside the timed region, reported beside it
+    if args.dump_outputs:
+        dump_last_step(args.dump_outputs, run.hits, pool_range((args.warmup + args.steps - 1) % P), U)
+    # what the records are for (--full): rank 0's consolidation of the timed job's records into .b6 lines (bh_report_view: per-mode
+    # selection, coordinates, formatting), written to /dev/null -- outside the timed region, reported beside it
     consolidation = None
     # (the timed job cycles through the pool: a query appears several times in its records, which no report accepts; one pass over the pool)
-    cons_run = search(job_share(0, P, weak=False))
-    if rank == 0:
+    cons_run = search(job_share(0, P, weak=False)) if args.full else None
+    if rank == 0 and args.full:
         try:
             t_ = time.time()
             n_lines_ = host.report_view(os.devnull, db, qs, rs.view, args.mode, 0) if use_dist else host.report(os.devnull, db, qs, cons_run.hits, args.mode, 0)
@@ -887,7 +934,7 @@ def main():
     # per rank --, (c) the main job with the records gathered over RCCL (bhip_comm_gather_hits across all N ranks) instead of
     # meeting in shared memory.  Extra keys of the line; `value` stays the main job's
     extra = {}
-    if use_dist:
+    if use_dist and args.full:
         if world > 1:
             e2, n2, _ = timed(job_share(args.warmup, args.steps, weak=not weak))
             r2 = job_reads(args.warmup, args.steps, weak=not weak)
@@ -902,7 +949,7 @@ def main():
     # The RCCL gather across all ranks in the same run (second measurement of the main job, records through bhip_comm_gather_hits inside the
     # timed region).  It runs LAST -- rank 0 has the whole line ready by then -- and under a watchdog: this exchange has never met two
     # devices (every box so far had one), and a collective that does not come back must not take the run's measurement with it.
-    want_rccl = use_dist and one_dev is None and args.gather == "shm"
+    want_rccl = args.full and use_dist and one_dev is None and args.gather == "shm"
 
     def rccl_extra():
         comm2 = make_comm()
@@ -1076,7 +1123,7 @@ def main():
                      "seed_words_per_read": st["n_seed_words"] / max(1.0, float(st["n_queries"]))},
             "host": {"db_read_s": t_db, "device_upload_s": t_dev, "query_ingest_s": t_q, "sec_in_device_calls": sec_align},
         }
-        if world == 1 and not args.no_short_job:
+        if args.full and world == 1 and not args.no_short_job:
             # One rank's share of BASELINE configs[3]'s job on 8 GPUs: 10 M reads / 8 = 1.25 M reads = less than one batch.  A job that
             # short has nothing to hide its staging, seed lookups and match profiles behind.  Whole, and cut into four pieces so that
             # piece k + 1 is prepared while piece k is aligned (bh_align.c, BURST_HOST_PIECES): the pieces' fixed costs eat the overlap.
@@ -1194,7 +1241,7 @@ def main():
             res["parity_vs_reference"] = ref_note
         if handover_main is not None:
             res["handover"] = handover_main
-        if world == 1 and (not args.no_end_to_end or (not args.no_continuity and args.db_scale > 1.5)):
+        if args.full and world == 1 and (not args.no_end_to_end or (not args.no_continuity and args.db_scale > 1.5)):
             # the command line and the small-database run are processes of their own with a database of their own on the device: this
             # process lets go of its copy first (a large database does not fit twice)
             if rs is not None:
@@ -1209,14 +1256,14 @@ def main():
                 log("[bench] device memory after this process let go of its database: %.1f GB free of %.1f" % (f_ / 1e9, t_ / 1e9))
             except Exception:
                 pass
-        if world == 1 and not args.no_end_to_end:
+        if args.full and world == 1 and not args.no_end_to_end:
             try:
                 res["end_to_end"] = end_to_end(edx, reads_fa, args, local_rank)
             except Exception as e:      # reported, never fatal for the measurement
                 res["end_to_end"] = {"error": str(e)}
             if res["end_to_end"] and "reads_per_s" in res["end_to_end"]:
                 res["end_to_end_reads_per_s"] = res["end_to_end"]["reads_per_s"]
-        if world == 1 and not args.no_continuity and args.db_scale > 1.5:
+        if args.full and world == 1 and not args.no_continuity and args.db_scale > 1.5:
             # rounds 1-3 quoted the rate on the 2.77 GB database: the same steps on it, for continuity (a child process; extra key)
             try:
                 t = time.time()
@@ -1229,14 +1276,14 @@ def main():
                                               "what": "the database of rounds 1-3 (BENCH_r03: 556 M reads/s), same steps, same kernels"}
             except Exception as e:
                 res["continuity_small_db"] = {"error": str(e)}
-        if world == 1 and not args.no_strains and args.db_profile == "pairs" and args.db_scale > 1.5:
+        if args.full and world == 1 and not args.no_strains and args.db_profile == "pairs" and args.db_scale > 1.5:
             # The redundancy regime, driver-timed (round 5's verdict: the headline's stand-in is low-redundancy on purpose; a database with
             # families of near-identical strains moves the work from the prefilter to the sweeps and the rate by an order of magnitude, while
             # the reference does not move).  A child process with its own database; its reference leg and parity check included.
             try:
                 t = time.time()
                 cmd = [sys.executable, os.path.abspath(__file__), "--db-profile", "strains", "--db-scale", str(args.strains_scale), "--steps", str(max(4, args.steps // 2)), "--warmup", str(min(args.warmup, 3)),
-                       "--reads", str(args.reads), "--pool", str(args.pool), "--cpu-sample", "100000", "--no-end-to-end", "--no-continuity", "--no-strains", "--no-short-job",
+                       "--reads", str(args.reads), "--pool", str(args.pool), "--cpu-sample", "100000", "--full", "--no-end-to-end", "--no-continuity", "--no-strains", "--no-short-job",
                        "--workdir", os.path.join(args.workdir, "strains")] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + [x for kv in args.opt for x in ("--opt", kv)]
                 r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
                 d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

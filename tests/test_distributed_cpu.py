@@ -117,6 +117,46 @@ def test_job_shares_partition_the_job():
                 assert np.array_equal(got, flat)
 
 
+@pytest.mark.parametrize("P,fr", [(1, False), (3, False), (3, True)])
+def test_dump_outputs_takes_the_last_step(P, fr, tmp_path, monkeypatch):
+    """bench.py --dump-outputs: of the timed job's records (batches one after the other, each sorted by (q, refIx)) exactly those of
+    the last step are written, one float .npy per field; above the size cap a sample of whole entries, the same one every time"""
+    import bench
+    from burst_amd import capi
+    U, steps = 900, 5
+    rng = np.random.default_rng(3)
+    batches, want = [], None
+    for k in range(steps):
+        u0, u1 = (k % P) * U // P, (k % P + 1) * U // P
+        ents = np.arange(u0, u1)
+        if fr:
+            ents = np.concatenate([ents, U + ents])
+        q = np.repeat(ents, rng.integers(0, 3, size=len(ents)))
+        h = np.zeros(len(q), capi.HIT_DTYPE)
+        h["q"] = q
+        h["refIx"] = rng.integers(0, 1 << 31, size=len(q))
+        h["score"] = rng.random(len(q))
+        h["ed"] = rng.integers(0, 3, size=len(q))
+        h = np.unique(h)                  # (sorted by (q, refIx, ...): a batch's order)
+        batches.append(h)
+        want = h
+    hits = np.concatenate(batches)
+    last = ((steps - 1) % P * U // P, ((steps - 1) % P + 1) * U // P)
+    bench.dump_last_step(str(tmp_path / "a"), hits, last, U)
+    for n in capi.HIT_DTYPE.names:
+        got = np.load(str(tmp_path / "a" / (n + ".npy")))
+        assert got.dtype in (np.float32, np.float64) and np.array_equal(got, want[n].astype(got.dtype))
+    # the cap: a fixed sample of whole entries, below it, identical in two runs
+    per_rec = 3 * 8 + 5 * 4               # (q, refIx, finalPos as float64; score and the four bytes as float32)
+    monkeypatch.setattr(bench, "DUMP_BYTES", want.size * per_rec // 2)
+    for d in ("b", "c"):
+        bench.dump_last_step(str(tmp_path / d), hits, last, U)
+    qb, qc = (np.load(str(tmp_path / d / "q.npy")) for d in ("b", "c"))
+    assert np.array_equal(qb, qc) and 0 < len(qb) * per_rec <= bench.DUMP_BYTES
+    kept = set(qb.tolist())
+    assert len(qb) == sum(1 for x in want["q"] if float(x) in kept)
+
+
 def test_clump_shards_partition_the_database():
     """bh_clump_shard (--shard db): contiguous clump ranges that cover the database, about the same number of reference columns each"""
     from burst_amd import host

@@ -407,7 +407,7 @@ def test_bench_multi_rank_path_with_one_process(tmp_path):
     import json
     import sys
     bench = os.path.join(gl.ROOT, "bench.py")
-    common = ["--db-scale", "1", "--n-base", "20000", "--reads", "100000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-end-to-end", "--no-continuity", "--workdir", str(tmp_path / "w")]
+    common = ["--db-scale", "1", "--n-base", "20000", "--reads", "100000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-end-to-end", "--no-continuity", "--workdir", str(tmp_path / "w")]
     r1 = subprocess.run([sys.executable, bench] + common, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r1.returncode == 0, r1.stderr[-3000:]
     a = json.loads(r1.stdout.strip().splitlines()[-1])

@@ -6,7 +6,7 @@
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${1:-$R/gpurun_out/bench_two_ranks_one_device.json}; shift
 BURST_BENCH_DEVICE=0 BURST_HOST_DEBUG=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 \
-  $R/bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end "$@" > $OUT 2> $OUT.err
+  $R/bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline --no-end-to-end "$@" > $OUT 2> $OUT.err
 grep -E "bh_search_multi|^\[bench\]|rror" $OUT.err | tail -12
 python3 - "$OUT" <<'PY'
 import json, sys

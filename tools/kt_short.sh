@@ -2,7 +2,7 @@
 # kernel trace of a short bench run: tools/kt_short.sh <tag> <bench args...>   (top kernels to gpurun_out/<tag>_kt.txt)
 cd /tmp && export TMPDIR=/tmp
 R=/root/repo; O=$R/gpurun_out; TAG=$1; shift
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_kt -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-end-to-end --no-continuity --no-strains --no-short-job --no-prime "$@" > $O/${TAG}_kt.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_kt -- python $R/bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-end-to-end --no-continuity --no-strains --no-short-job --no-prime "$@" > $O/${TAG}_kt.log 2>&1
 python - "$O/${TAG}_kt" <<'PY' | tee $O/${TAG}_kt.txt
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + '/**/*kernel_stats.csv', recursive=True):

@@ -2,7 +2,7 @@
 # One parametrised recipe file for the GPU box (replaces the per-call scripts of rounds 1-4):  gpurun -- 'bash tools/run.sh <what> [args]'
 # Everything lands in gpurun_out/<TAG>_* (TAG from the environment, default "run"); copy what should be judged into profiles/.
 #   tests [pytest args]          the -m gpu suite (default: all of tests/), every failure listed
-#   bench [bench.py args]        the driver's command line (python bench.py --gpus 1 --steps 20 --warmup 5) with the job's memory sampled beside it
+#   bench [bench.py args]        the driver's command line with every leg (python bench.py --gpus 1 --steps 20 --warmup 5 --full) with the job's memory sampled beside it
 #   ab <db-scale> <spec> ...     bench.py --ab <spec> ... on one resident database (spec = name=value[,name=value]; library options of bhip_set_option)
 #   variant <libdir> [args]      bench.py with the libraries of burst_amd/<libdir> (tools/build_variant.sh: prof = phase timers, ...)
 #   benchprof [bench.py args]    the driver's command line under rocprofv3 --kernel-trace --stats: bench line + kernel statistics of one process
@@ -22,7 +22,7 @@ tests)
 bench)
 	(while true; do echo "$(date +%s) $(cat /sys/fs/cgroup/memory.current 2>/dev/null) $(df --output=used -B1 /dev/shm | tail -1) $(grep -E '^(anon|file|shmem|file_mapped|kernel) ' /sys/fs/cgroup/memory.stat 2>/dev/null | tr '\n' ' ')"; sleep 2; done) > $O/${TAG}_mem.txt & MW=$!
 	T0=$SECONDS
-	timeout ${LIMIT:-2400} python bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+	timeout ${LIMIT:-2400} python bench.py --gpus 1 --steps 20 --warmup 5 --full "$@" > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 	echo "bench exit $? after $((SECONDS - T0)) s"; kill $MW
 	grep "^\[bench\]" $O/${TAG}_bench.err | cut -c1-330; sum "$TAG" $O/${TAG}_bench.json
 	python - "$O/${TAG}_bench.json" <<'PY'
@@ -37,7 +37,7 @@ benchprof)
 	# so that roofline.frac can be recomputed from the profiler's average of the same launches (round 5's verdict: 9 % between two runs)
 	cd /tmp && export TMPDIR=/tmp
 	T0=$SECONDS
-	timeout ${LIMIT:-2400} rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_kt -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --db-scale 11.37 --no-end-to-end --no-continuity --no-strains --no-short-job "$@" > $O/${TAG}_benchprof.log 2> $O/${TAG}_benchprof.err
+	timeout ${LIMIT:-2400} rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_kt -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --db-scale 11.37 --no-end-to-end --no-continuity --no-strains --no-short-job "$@" > $O/${TAG}_benchprof.log 2> $O/${TAG}_benchprof.err
 	echo "benchprof exit $? after $((SECONDS - T0)) s"
 	grep '^{' $O/${TAG}_benchprof.log | tail -1 > $O/${TAG}_bench_under_rocprof_driver_line.json
 	python - "$O" "$TAG" <<'PY'
@@ -48,7 +48,7 @@ for f in glob.glob('%s/%s_kt/**/*kernel_stats.csv' % (O, TAG), recursive=True): 
     rows = list(csv.DictReader(open(f)))
     if any('k_prefilter_cq' in r['Name'] for r in rows) and (best is None or len(rows) > len(best)): best = rows
 d = json.loads(open('%s/%s_bench_under_rocprof_driver_line.json' % (O, TAG)).read())
-out = ['command: rocprofv3 --kernel-trace --stats -- python bench.py --gpus 1 --steps 20 --warmup 5 --db-scale 11.37 --no-end-to-end --no-continuity --no-strains --no-short-job   (same process as %s_bench_under_rocprof_driver_line.json)' % TAG,
+out = ['command: rocprofv3 --kernel-trace --stats -- python bench.py --gpus 1 --steps 20 --warmup 5 --full --db-scale 11.37 --no-end-to-end --no-continuity --no-strains --no-short-job   (same process as %s_bench_under_rocprof_driver_line.json)' % TAG,
        '%-50s %7s %12s %12s' % ('kernel', 'calls', 'avg_us', 'total_ms')]
 for r in (best or [])[:60]:
     n = r['Name'].replace('HIP_vector_type<unsigned int, 2u>', 'uint2').split('(')[0][:48]
@@ -80,7 +80,7 @@ ab)
 	echo "ab exit $?"; grep "^\[bench\] ab\|^\[bench\] rank\|accelerator built" $O/${TAG}_ab.err | cut -c1-420; grep "prefilter kernel:" $O/${TAG}_ab.err | sort | uniq -c; sum "$TAG" $O/${TAG}_ab.json ;;
 variant)
 	V=$1; shift
-	BURST_AMD_LIBDIR=$R/burst_amd/$V BHIP_PROF=1 timeout ${LIMIT:-900} python bench.py --workdir $W --keep-files $QUIET "$@" > $O/${TAG}_$V.json 2> $O/${TAG}_$V.err
+	BURST_AMD_LIBDIR=$R/burst_amd/$V BHIP_PROF=1 timeout ${LIMIT:-900} python bench.py --full --workdir $W --keep-files $QUIET "$@" > $O/${TAG}_$V.json 2> $O/${TAG}_$V.err
 	grep "phase share" $O/${TAG}_$V.err; sum "$TAG/$V" $O/${TAG}_$V.json ;;
 profile)
 	PROFILE_COMMIT=${COMMIT:-unknown} bash tools/profile_round.sh $TAG --workdir $W "$@" 2>&1 | grep -v "rocprim\|k_acx\|fillBuffer\|k_qs_" | head -24 ;;
@@ -91,7 +91,7 @@ shape)
 	configs4) A="--db-scale 5 --read-len 320 --mode FORAGE --id 0.95 --fr --iupac 0.001 --edits 0,2,4,8,12 --reads 500000 --cpu-sample ${CPU_SAMPLE:-20000}" ;;
 	*) echo "shape configs1|configs2|configs4"; exit 1 ;;
 	esac
-	timeout ${LIMIT:-2400} python bench.py --workdir $W.$1 --no-end-to-end --no-continuity --no-short-job --no-strains $A ${SHAPE_EXTRA:-} > $O/${TAG}_$1.json 2> $O/${TAG}_$1.err
+	timeout ${LIMIT:-2400} python bench.py --full --workdir $W.$1 --no-end-to-end --no-continuity --no-short-job --no-strains $A ${SHAPE_EXTRA:-} > $O/${TAG}_$1.json 2> $O/${TAG}_$1.err
 	echo "$1 exit $?"; sum "$1" $O/${TAG}_$1.json; rm -rf $W.$1 ;;
 cli)
 	S=$1; shift
