@@ -46,7 +46,7 @@ class BhipQuerySpan(C.Structure):
 EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_batch", "bhip_align_pairs", "bhip_prefilter", "bhip_set_option", "bhip_get_stats",
            "bhip_device_info", "bhip_destroy", "bhip_last_error", "bhip_abi_version", "bhip_set_ref_order", "bhip_copy_hits_device", "bhip_sync_hits",
            "bhip_comm_create", "bhip_comm_unique_id", "bhip_comm_create_rank", "bhip_comm_allreduce_min", "bhip_comm_fetch_gathered", "bhip_comm_gather_hits", "bhip_comm_stage_device", "bhip_comm_gather_staged", "bhip_comm_stage_reset", "bhip_comm_destroy", "bhip_acx_export", "bhip_reserve", "bhip_reserve_symbols", "bhip_sort_queries", "bhip_stage_spans", "bhip_alloc_host", "bhip_free_host", "bhip_host_register", "bhip_host_unregister", "bhip_set_enqueued_hook", "bhip_acx_export_entries",
-           "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy"]
+           "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks"]
 
 
 class BurstHipError(RuntimeError):
@@ -73,6 +73,8 @@ def _load():
     vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
     lib.bhip_init.argtypes = [i32, vp, vp, u32, u32, vp, vp, i32, i32, vp, u32, vp, i32, C.POINTER(vp)]
     lib.bhip_init.restype = i32
+    lib.bhip_dna_marks.argtypes = [i32, vp, u64, vp, vp, u64, u32, C.POINTER(u64), C.POINTER(u64), vp, vp]
+    lib.bhip_dna_marks.restype = i32
     lib.bhip_align_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, i32, vp, u64, C.POINTER(u64)]
     lib.bhip_align_batch.restype = i32
     lib.bhip_stage_queries.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32]
@@ -339,3 +341,17 @@ class Device:
             _chk(rc)
             k = n.value
             return oq[:k], oc[:k], on[:k]
+
+
+def dna_marks(sym, ref_start, ref_len, W, max_chain=0, max_sh=0, device=0):
+    """duplicate marks of one -d DNA partition on the device (bhip_dna_marks): sym = uint8 symbol codes, references at
+    [ref_start[r], ref_start[r] + ref_len[r]); returns (flags, max_chain, max_sh, info) with info as include/burst_hip.h lists it"""
+    sym = np.ascontiguousarray(sym, np.uint8)
+    rs = np.ascontiguousarray(ref_start, np.uint64)
+    rl = np.ascontiguousarray(ref_len, np.uint32)
+    flags = np.zeros(len(sym), np.uint8)
+    info = np.zeros(8, np.uint64)
+    mc, ms = C.c_uint64(max_chain), C.c_uint64(max_sh)
+    _chk(lib().bhip_dna_marks(device, sym.ctypes.data, len(sym), rs.ctypes.data, rl.ctypes.data, len(rs), W, C.byref(mc), C.byref(ms),
+                                flags.ctypes.data, info.ctypes.data))
+    return flags, mc.value, ms.value, info

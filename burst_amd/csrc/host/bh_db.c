@@ -323,6 +323,9 @@ static void tux_bucket_sort(Tux *pack, uint32_t n) {
 }
 
 
+static int db_from_fragments(BhDb *db, char **head, const uint8_t **seq, uint32_t *len, uint32_t *start, uint32_t totR, uint32_t shear_cap,
+                             int dedupe, uint32_t latency);
+
 int bh_db_from_fasta(const char *path, uint32_t maxLenQ, float thres, int do_shear, long shear_len, int dedupe, BhDb *db) {
 	return bh_db_from_fasta_ex(path, maxLenQ, thres, do_shear, shear_len, dedupe, 16, db);      /* LATENCY, burst.c:83 */
 }
@@ -362,6 +365,16 @@ int bh_db_from_fasta_ex(const char *path, uint32_t maxLenQ, float thres, int do_
 		head = malloc((size_t)totR * sizeof(*head)); seq = malloc((size_t)totR * sizeof(*seq)); len = malloc((size_t)totR * 4);
 		for (uint32_t i = 0; i < nR; ++i) head[i] = R[i].head, seq[i] = R[i].seq, len[i] = R[i].len;
 	}
+	rc = db_from_fragments(db, head, seq, len, start, totR, shear_cap, dedupe, latency);
+	free(head); free(seq); free(len); free(R);
+	return rc;
+}
+
+/* The stages after the shear, common to the uniform shear (QUICK) and the duplicate-guided one (DNA): the fragment list
+ * (header, first symbol, length, start in its sequence or NULL) is ordered, de-duplicated, clumped and given its header table.
+ * The caller keeps the four arrays (`start` excepted: db owns it). */
+static int db_from_fragments(BhDb *db, char **head, const uint8_t **seq, uint32_t *len, uint32_t *start, uint32_t totR, uint32_t shear_cap,
+                             int dedupe, uint32_t latency) {
 	/* order: by length, then lexicographically inside pods whose lengths differ by at most LATENCY (default 16, `-l`)
 	 * (burst.c:2149-2186); `-l 0` keeps the input order (2187-2189) */
 	uint32_t *srt = own(db, malloc(((size_t)totR + 1) * 4));
@@ -415,9 +428,9 @@ int bh_db_from_fasta_ex(const char *path, uint32_t maxLenQ, float thres, int do_
 		cl[c] = m; words += m / 2u + (m & 1);
 	}
 	uint8_t *packed = own(db, calloc(words + 1, 16));
-	if (!packed) { free(head); free(seq); free(len); free(R); bh_db_free(db); return bh_set_error(BH_E_OOM, "OOM:RefClump"); }
+	if (!packed) { bh_db_free(db); return bh_set_error(BH_E_OOM, "OOM:RefClump"); }
 	uint64_t *cw = malloc(((size_t)nC + 1) * 8);
-	if (!cw) { free(head); free(seq); free(len); free(R); bh_db_free(db); return bh_set_error(BH_E_OOM, "OOM:RefClump"); }
+	if (!cw) { bh_db_free(db); return bh_set_error(BH_E_OOM, "OOM:RefClump"); }
 	cw[0] = 0;
 	for (uint32_t c = 0; c < nC; ++c) cw[c + 1] = cw[c] + cl[c] / 2u + (cl[c] & 1);
 	#pragma omp parallel for schedule(static, 256)
@@ -452,7 +465,6 @@ int bh_db_from_fasta_ex(const char *path, uint32_t maxLenQ, float thres, int do_
 	}
 	db->refStart = start;
 	db->identityMap = 1;
-	free(head); free(seq); free(len); free(R);
 	return BH_OK;
 }
 
@@ -617,7 +629,44 @@ static void expand_word(const uint8_t *s, int K, int ix, uint32_t w, uint8_t *se
 
 int bh_acx_build(BhDb *db, int K, int z) { return bh_acx_build_ex(db, K, z, 0); }
 /* skip_ambig = -sa: words holding any ambiguous symbol are left out, no BadList (burst.c:3341, 3360-3366) */
+static int acx_build_impl(BhDb *db, int K, int z, int skip_ambig);
 int bh_acx_build_ex(BhDb *db, int K, int z, int skip_ambig) {
+	uint8_t *keep = NULL;
+	int rc = bh_db_trim_lanes(db, &keep);
+	if (!rc) rc = acx_build_impl(db, K, z, skip_ambig);
+	bh_db_untrim_lanes(db, keep);
+	return rc;
+}
+
+/* A database built by the compressive shear (-d DNA) knows its fragment lengths; its clump area holds one symbol past a shorter lane's
+ * end, and there that symbol is a real base of the parent sequence (burst.c:2717).  make_accelerator indexes a lane only up to its
+ * RefLen (3342-3377), while both builders here take a lane's length to be the clump length minus trailing zero codes: they are handed
+ * a copy of the clump area whose symbols at j >= RefLen are zero.  The .edx is written from the untrimmed area. */
+int bh_db_trim_lanes(BhDb *db, uint8_t **keep) {
+	*keep = NULL;
+	if (!db->fragLen || !db->packed) return BH_OK;
+	uint8_t *t = malloc((db->packedWords + 1) * 16);
+	if (!t) return bh_set_error(BH_E_OOM, "OOM:trim_lanes");
+	memcpy(t, db->packed, (db->packedWords + 1) * 16);
+	uint64_t w0 = 0;
+	for (uint32_t c = 0; c < db->numRclumps; ++c) {
+		const uint32_t cl = db->clumpLen[c];
+		for (uint32_t k = 16 * c; k < db->totR && k < 16 * c + 16; ++k) {
+			const uint32_t L = db->fragLen[db->refIxSrt[k]];
+			for (uint32_t j = L; j < cl; ++j) t[(w0 + j / 2) * 16 + (k & 15)] &= (uint8_t)(j & 1 ? 0x0F : 0xF0);
+		}
+		w0 += cl / 2u + (cl & 1);
+	}
+	*keep = db->packed; db->packed = t;
+	return BH_OK;
+}
+void bh_db_untrim_lanes(BhDb *db, uint8_t *keep) {
+	if (!keep) return;
+	free(db->packed);
+	db->packed = keep;
+}
+
+static int acx_build_impl(BhDb *db, int K, int z, int skip_ambig) {
 	const uint64_t nw = 1ull << (2 * K);
 	const uint32_t nC = db->numRclumps;
 	const uint64_t fullSize = K > 14 ? 0x7FFFFFFFull : (1ull << 24);
@@ -979,4 +1028,92 @@ int bh_db_slice(const BhDb *db, uint32_t c0, uint32_t c1, BhDb *out) {
 	out->hasAcx = 1; out->K = K; out->acxFmt = fmtOut; out->acxZ = db->acxZ;
 	out->acxLens = lens; out->acxLists = lists; out->acxListBytes = bytes; out->badList = bl; out->badSz = nb;
 	return BH_OK;
+}
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * -d DNA / RNA with -s (process_references, DNA_16 branch, burst.c:1859-2108), then the stages of the QUICK build. */
+static double dna_wall(void) { return omp_get_wtime(); }
+int bh_db_from_fasta_dna(const char *path, uint32_t maxLenQ, float thres, long shear_len, uint32_t partitions, int dedupe, uint32_t latency,
+                         int device, BhDb *db, BhDnaStats *stats) {
+	BhDnaStats st_local, *st = stats ? stats : &st_local;
+	memset(st, 0, sizeof *st);
+	memset(db, 0, sizeof *db);
+	double t0 = dna_wall();
+	const uint32_t minShear = (uint32_t)(maxLenQ / thres), ov = minShear;
+	const uint32_t shear = minShear > (uint32_t)shear_len ? minShear : (uint32_t)shear_len, W = shear + ov;
+	if (shear_len <= 0) return bh_set_error(BH_E_USAGE, "ERROR: the compressive build needs shearing (-s)");
+	if (W < 24) return bh_set_error(BH_E_USAGE, "ERROR: -d DNA needs shear + overlap >= 24 symbols (here %u + %u): below that the reference's "
+	                                "classes of equal windows depend on its sort's arbitrary order; raise -s or the query length", shear, ov);
+	RefRec *R = NULL; uint32_t nR = 0; char *text = NULL;
+	int rc = parse_ref_fasta(path, &R, &nR, &text);
+	if (rc) return rc;
+	own(db, text);
+	if (!nR) { free(R); bh_db_free(db); return bh_set_error(BH_E_USAGE, "ERROR: no references in %s", path); }
+	/* the symbol layout of parse_tl_fasta_db: one array, a single 0 between consecutive sequences, zeros behind the last */
+	uint64_t tot = 0;
+	for (uint32_t i = 0; i < nR; ++i) tot += (uint64_t)R[i].len + 1;
+	uint8_t *sym = own(db, calloc(tot + 64, 1));
+	uint8_t *flags = calloc(tot + 64, 1);
+	uint64_t *rs = malloc((size_t)nR * 8); uint32_t *rl = malloc((size_t)nR * 4);
+	uint64_t *rsp = malloc((size_t)nR * 8);
+	if (!sym || !flags || !rs || !rl || !rsp) { free(flags); free(rs); free(rl); free(rsp); free(R); bh_db_free(db); return bh_set_error(BH_E_OOM, "OOM:SeqDump"); }
+	for (uint64_t i = 0, off = 0; i < nR; ++i) { rs[i] = off; rl[i] = R[i].len; memcpy(sym + off, R[i].seq, R[i].len); off += (uint64_t)R[i].len + 1; }
+	st->secParse = dna_wall() - t0; t0 = dna_wall();
+	/* marks, partition by partition (-dp: index ranges of ceil(n / P) references) */
+	const uint32_t P = partitions ? partitions : 1, cp_range = nR / P + (nR % P != 0);
+	st->W = W; st->shear = shear; st->ov = ov; st->partitions = P; st->symbols = tot; st->device = device;
+	uint64_t maxChain = 0, maxSh = 0;
+	if (device >= 0 && getenv("BURST_HOST_DNA_MARKS")) { st->device = -1; snprintf(st->note, sizeof st->note, "BURST_HOST_DNA_MARKS is set"); }
+	for (uint32_t rix = 0; rix < nR; rix += cp_range) {
+		const uint32_t red = nR < rix + cp_range ? nR : rix + cp_range, np = red - rix;
+		const uint64_t base = rs[rix];
+		for (uint32_t i = 0; i < np; ++i) rsp[i] = rs[rix + i] - base;
+		if (st->device >= 0) {
+			uint64_t info[8] = {0};
+			const int drc = bhip_dna_marks(st->device, sym + base, rsp[np - 1] + rl[red - 1], rsp, rl + rix, np, W, &maxChain, &maxSh, flags + base, info);
+			if (drc == BHIP_OK) {
+				st->eligible += info[0]; st->chunks += info[1]; st->exactChunks += info[2];
+				if (info[3] > st->peakDeviceBytes) st->peakDeviceBytes = info[3];
+				st->secUpload += info[4] * 1e-6; st->secSort += info[5] * 1e-6; st->secClassify += info[6] * 1e-6; st->secMark += info[7] * 1e-6;
+				continue;
+			}
+			if (drc != BHIP_E_DEVICE || rix) {      /* a device that worked for an earlier partition does not hand over midway */
+				rc = bh_set_error(drc == BHIP_E_ARG ? BH_E_USAGE : BH_E_DEVICE, "ERROR: %s", bhip_last_error());
+				goto out;
+			}
+			snprintf(st->note, sizeof st->note, "%s", bhip_last_error());
+			st->device = -1;
+		}
+		if ((rc = bh_dna_marks_host(sym + base, rsp, rl + rix, np, W, &maxChain, &maxSh, flags + base))) goto out;
+	}
+	st->maxChain = maxChain; st->maxSh = maxSh;
+	st->secMarks = dna_wall() - t0; t0 = dna_wall();
+	/* the flag-guided shear (2031-2103); its capacity is the reference's: twice the uniform count at step ov */
+	uint64_t cap = 0;
+	for (uint32_t i = 0; i < nR; ++i) {
+		long unit = (long)rl[i] - (long)ov;
+		if (unit <= 0) unit = 1;
+		cap += (uint64_t)(unit / ov + (unit % ov != 0));
+	}
+	cap = (uint32_t)(cap * 2);
+	{
+		uint32_t *fref = malloc(cap * 4 + 4), *fstart = own(db, malloc(cap * 4 + 4)), *flen = own(db, malloc(cap * 4 + 4));
+		char **head = malloc(cap * sizeof(char *) + 8); const uint8_t **seq = malloc(cap * sizeof(uint8_t *) + 8);
+		uint64_t nf = 0;
+		if (!fref || !fstart || !flen || !head || !seq) { free(fref); free(head); free(seq); rc = bh_set_error(BH_E_OOM, "OOM:RefStart"); goto out; }
+		if ((rc = bh_dna_shear(flags, rs, rl, nR, shear, ov, fref, fstart, flen, cap, &nf))) { free(fref); free(head); free(seq); goto out; }
+		for (uint64_t x = 0; x < nf; ++x) head[x] = R[fref[x]].head, seq[x] = sym + rs[fref[x]] + fstart[x];
+		free(fref);
+		st->fragments = nf;
+		st->secShear = dna_wall() - t0; t0 = dna_wall();
+		db->rebase = 1; db->shear = minShear;
+		rc = db_from_fragments(db, head, seq, flen, fstart, (uint32_t)nf, W, dedupe, latency);
+		free(head); free(seq);
+		if (!rc) db->fragLen = flen;
+		st->secStages = dna_wall() - t0;
+	}
+out:
+	free(flags); free(rs); free(rl); free(rsp); free(R);
+	if (rc) bh_db_free(db);
+	return rc;
 }

@@ -59,6 +59,7 @@ typedef struct BhDb {
 	int identityMap;         /* direct-FASTA runs: RefMap is the identity (burst.c:4545-4551) */
 	void *owned[32]; int nOwned;
 	void *mapBase; uint64_t mapLen;      /* the clump area of a large .edx is a read-only mapping of the file (bh_edx_read): the processes of a node share one copy */
+	uint32_t *fragLen;       /* [origTotR] fragment lengths of a compressive (-d DNA) build, or NULL: what the accelerator builders index (bh_db_trim_lanes) */
 } BhDb;
 
 int  bh_is_edx(const char *path);                       /* burst.c:4894-4901: first byte has bit 7 set; <0 on IO error */
@@ -73,6 +74,28 @@ int  bh_db_from_fasta_ex(const char *path, uint32_t maxLenQ, float thres, int do
 /* n .edx files laid end to end into one (every part but the last must fill its last clump; no duplicate-fragment tables): a
  * database too large to be built in one piece in the memory at hand, built part by part */
 int  bh_edx_merge(const char *const *paths, int n, const char *out_path);
+/* -d DNA / RNA with -s: the compressive build (process_references, DNA_16 branch, burst.c:1859-2108).  The sequences lie in one array,
+ * a single 0 between consecutive ones (parse_tl_fasta_db, 541-605); duplicate marks per partition of ceil(n / partitions) references
+ * (`-dp`, 0 = 1) on `device` (bhip_dna_marks) or, with device < 0 or none usable, by bh_dna_marks_host; the flag-guided shear; then
+ * the stages of the QUICK build.  stats may be NULL. */
+typedef struct BhDnaStats {
+	int device;                 /* where the marks were computed: device number, or -1 = host */
+	uint32_t W, shear, ov, partitions;
+	uint64_t maxChain, maxSh, eligible, chunks, exactChunks, peakDeviceBytes, symbols, fragments;
+	double secParse, secMarks, secShear, secStages;
+	double secUpload, secSort, secClassify, secMark;      /* device marks, summed over partitions */
+	char note[256];             /* why the host computed the marks on a machine asked to use a device */
+} BhDnaStats;
+int  bh_db_from_fasta_dna(const char *path, uint32_t maxLenQ, float thres, long shear_len, uint32_t partitions, int dedupe, uint32_t latency,
+                          int device, BhDb *db, BhDnaStats *stats);
+/* flags[p - ref_start[0]... ] for the positions [0, ref_start[n-1] + ref_len[n-1]) of one partition (ref_start relative to sym):
+ * the OR of the two convs (low nibble); reads and updates *max_chain / *max_sh as the reference's state across partitions */
+int  bh_dna_marks_host(const uint8_t *sym, const uint64_t *ref_start, const uint32_t *ref_len, uint64_t n_refs, uint32_t W,
+                       uint64_t *max_chain, uint64_t *max_sh, uint8_t *flags);
+int  bh_dna_shear(const uint8_t *flags, const uint64_t *ref_start, const uint32_t *ref_len, uint32_t n_refs, uint32_t shear, uint32_t ov,
+                  uint32_t *frag_ref, uint32_t *frag_start, uint32_t *frag_len, uint64_t cap, uint64_t *n_frag);
+int  bh_db_trim_lanes(BhDb *db, uint8_t **keep);      /* db->packed := copy with every lane zeroed from its fragment length on (no-op without fragLen) */
+void bh_db_untrim_lanes(BhDb *db, uint8_t *keep);
 int  bh_acx_build(BhDb *db, int K, int z);
 /* skip_ambig = -sa: leave out every word that holds an ambiguous symbol (burst.c:3360-3366) */
 int  bh_acx_build_ex(BhDb *db, int K, int z, int skip_ambig);

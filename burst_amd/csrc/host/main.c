@@ -2,7 +2,7 @@
  *
  *   burst_hip -r DB.edx -a DB.acx -q reads.fa -o out.b6 -m {BEST|ALLPATHS|CAPITALIST|FORAGE|ANY} -i 0.97 [-fr] [-y] [-w]
  *   burst_hip -r refs.fa -q reads.fa -o out.b6 [-s [len]]            direct FASTA (exhaustive, no accelerator)
- *   burst_hip -r refs.fa -d [QUICK|DNA|RNA] [qLen] -o DB.edx [-a DB.acx] [-s [len]] -i 0.97      database construction
+ *   burst_hip -r refs.fa -d [QUICK|DNA|RNA] [qLen] -o DB.edx [-a DB.acx] [-s [len]] [-dp N] -i 0.97      database construction
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
  * reference's exit code 1.  Extra flags: --device N, --batch N (unique queries per device call), -k {12|15}.
@@ -27,12 +27,17 @@ static int code_to_exit(int rc) { return rc == BH_E_USAGE ? 1 : rc == BH_E_IO ? 
 static int build_accelerator(BhDb *db, int K, int z, int device, int on_host, int skip_ambig) {
 	if (!on_host && !skip_ambig) {
 		void *hh = NULL;
+		uint8_t *keep = NULL;      /* a -d DNA database: the builder sees every lane cut at its fragment length (bh_db_trim_lanes) */
+		int rc = bh_db_trim_lanes(db, &keep);
+		if (rc) return rc;
 		if (!bh_device_open_ex(db, device, z, K, &hh)) {
-			const int rc = bh_acx_from_device(db, hh, K, z);
+			rc = bh_acx_from_device(db, hh, K, z);
 			bhip_destroy(hh);
+			bh_db_untrim_lanes(db, keep);
 			if (!rc) printf(" --> accelerator built on device %d\n", device);
 			return rc;
 		}
+		bh_db_untrim_lanes(db, keep);
 		printf(" --> no device accelerator build (%s); using the host builder\n", bh_last_error());
 	}
 	return bh_acx_build_ex(db, K, z, skip_ambig);
@@ -59,6 +64,8 @@ static void usage(void) {
 	puts("--output (-o) <name>: Blast6/edx file for output alignments/database [required]");
 	puts("--forwardreverse (-fr), --whitespace (-w), --nwildcard (-y), --mode (-m) BEST|ALLPATHS|CAPITALIST|FORAGE|ANY");
 	puts("--makedb (-d) [name qLen], --id (-i) <decimal>, --threads (-t) <int>, --shear (-s) [len], --noprogress");
+	puts("   -d DNA|RNA with -s: the compressive build (shears start at duplicated regions; marks on the device, else the host)");
+	puts("--dbpartition (-dp) <int>: -d DNA marks in this many slices of the references (less memory)");
 	puts("--taxonomy (-b) <name>, --taxacut (-bc) <num>, --taxa_ncbi (-bn), --taxasuppress (-bs) [STRICT]: taxonomy column (interpolated in CAPITALIST)");
 	puts("--gpus <int> [--devices a,b,...] [--gather host|rccl]: shard the queries over the GPUs of this node; every rank's records reach host");
 	puts("   memory over its own PCIe link and meet there (host, default) or are gathered over RCCL / xGMI to rank 0's device first (rccl)");
@@ -74,6 +81,7 @@ int main(int argc, char **argv) {
 	BhMode mode = BH_CAPITALIST;                    /* burst.c:81 */
 	float thres = 0.97f;                            /* burst.c:93 */
 	int xalpha = 0;
+	int dna_db = 0, dpart = 0;
 	int z = 1, do_rc = 0, incl_ws = 0, makedb = 0, do_shear = 0, do_accel = 0, dedupe = 0, device = 0, K = 0, skip_ambig = 0, threads = 0, rep_flags = 0;
 	long shear_amt = 500, db_qlen = 500;            /* burst.c:94 */
 	uint32_t latency = 16;                          /* burst.c:83 */
@@ -109,7 +117,7 @@ int main(int argc, char **argv) {
 			if (i + 1 != argc && argv[i + 1][0] != '-' && !atol(argv[i + 1])) {
 				++i;
 				if (strcmp(argv[i], "DNA") && strcmp(argv[i], "RNA") && strcmp(argv[i], "QUICK")) { printf("Unsupported makedb mode '%s'\n", argv[i]); return 1; }
-				if (strcmp(argv[i], "QUICK")) printf(" --> NOTE: -d %s: the compressive clustering of the reference's builder is not included; the database is laid out as -d QUICK (same alignments, less compact)\n", argv[i]);
+				dna_db = strcmp(argv[i], "QUICK") != 0;
 			}
 			if (i + 1 != argc && argv[i + 1][0] != '-') { db_qlen = atol(argv[++i]); if (db_qlen <= 0) { fprintf(stderr, "ERROR: bad max query length '%s'\n", argv[i]); return 1; } }
 		}
@@ -172,8 +180,15 @@ int main(int argc, char **argv) {
 			latency = (uint32_t)atoi(argv[i]);
 			printf(" --> Setting clump formation latency to %d bases\n", atoi(argv[i]));
 		}
-		else if (!strcmp(a, "--clustradius") || !strcmp(a, "-cr") || !strcmp(a, "--dbpartition") || !strcmp(a, "-dp")) {
-			printf("ERROR: option %s belongs to the compressive (-d DNA/RNA) database builder, which burst_hip does not include; use -d QUICK\n", a); return 1;
+		else if (!strcmp(a, "--dbpartition") || !strcmp(a, "-dp")) {                    /* burst.c:4986-4993 */
+			if (++i == argc || argv[i][0] == '-') { puts("ERROR: --dbpartition requires integer argument"); return 1; }
+			const int temp = atoi(argv[i]);
+			if (temp < 0) { fputs("ERROR: numb partitions must be >= 1\n", stderr); return 1; }
+			dpart = temp;
+			printf(" --> Partitioning database into %d slices\n", temp);
+		}
+		else if (!strcmp(a, "--clustradius") || !strcmp(a, "-cr")) {
+			printf("ERROR: option %s tunes the reference's fingerprints (-f), which burst_hip does not include\n", a); return 1;
 		}
 		else if (!strcmp(a, "--xalphabet") || !strcmp(a, "-x")) { xalpha = 1; printf(" --> Allowing any alphabet (unambiguous ID matching)\n"); }
 		else if (!strcmp(a, "--fingerprint") || !strcmp(a, "-f") || !strcmp(a, "--prepass") ||
@@ -208,16 +223,31 @@ int main(int argc, char **argv) {
 		if (e) { fputs("ERROR: DBs can't make DBs.\n", stderr); return 1; }
 		BhDb db;
 		if (!do_shear) db_qlen = 0;                                             /* burst.c:5121 */
-		if ((rc = bh_db_from_fasta_ex(ref_FN, (uint32_t)db_qlen, thres, do_shear, shear_amt, 1, latency, &db))) DIE(rc);
+		double tw = wall();
+		if (dna_db && do_shear) {
+			/* the compressive build (burst.c:1859-2108).  Without -s the reference reaches RefLen unset and crashes: the QUICK layout below */
+			BhDnaStats st;
+			if ((rc = bh_db_from_fasta_dna(ref_FN, (uint32_t)db_qlen, thres, shear_amt, (uint32_t)dpart, 1, latency, device, &db, &st))) DIE(rc);
+			printf("Compressive build [shear %u, ov %u, window %u, %u partition%s]: max chain %llu, max sh %llu, %llu fragments\n", st.shear, st.ov, st.W,
+			       st.partitions, st.partitions == 1 ? "" : "s", (unsigned long long)st.maxChain, (unsigned long long)st.maxSh, (unsigned long long)st.fragments);
+			if (st.device >= 0) printf(" --> duplicate marks computed on device %d (%llu eligible positions, %llu chunk%s, %llu by the exact path, peak %.2f GB)\n", st.device,
+			                           (unsigned long long)st.eligible, (unsigned long long)st.chunks, st.chunks == 1 ? "" : "s", (unsigned long long)st.exactChunks, st.peakDeviceBytes / 1e9);
+			else printf(" --> duplicate marks computed on the host (%s)\n", st.note[0] ? st.note : "no device asked for");
+			printf(" [parse %.3f s] [marks %.3f s: upload %.3f, sort %.3f, classify %.3f, mark %.3f] [shear %.3f s] [order/dedupe/clumps %.3f s]\n", st.secParse, st.secMarks,
+			       st.secUpload, st.secSort, st.secClassify, st.secMark, st.secShear, st.secStages);
+		} else if ((rc = bh_db_from_fasta_ex(ref_FN, (uint32_t)db_qlen, thres, do_shear, shear_amt, 1, latency, &db))) DIE(rc);
 		puts("Writing database...");
+		tw = wall();
 		if ((rc = bh_edx_write(&db, output_FN, db_qlen, thres))) DIE(rc);
-		printf("Database written: %u refs [%u orig], %u clumps, %u maxR\n", db.totR, db.origTotR, db.numRclumps, db.maxLenR);
+		printf("Database written: %u refs [%u orig], %u clumps, %u maxR [write %.3f s]\n", db.totR, db.origTotR, db.numRclumps, db.maxLenR, wall() - tw);
 		if (do_accel) {
 			if (!K) K = 12;
 			if (accel_dev || !xcel_FN) { puts("ERROR: -ad builds the accelerator at search time; give -a <name> to write one"); return 1; }
 			printf("Generating accelerator '%s' (K=%d)\n", xcel_FN, K);
+			tw = wall();
 			if ((rc = build_accelerator(&db, K, z, device, host_acx, skip_ambig))) DIE(rc);
 			if ((rc = bh_acx_write(&db, xcel_FN))) DIE(rc);
+			printf(" [accelerator %.3f s]\n", wall() - tw);
 		}
 		bh_db_free(&db);
 		return 0;

@@ -25,7 +25,16 @@ class BhDb(C.Structure):
                 ("tmpRIX", u32p), ("refIxSrt", u32p), ("clumpLen", u32p), ("packed", u8p), ("packedWords", C.c_uint64),
                 ("hasAcx", C.c_int), ("K", C.c_int), ("acxFmt", C.c_int), ("acxZ", C.c_int),
                 ("acxLens", u32p), ("acxLists", u8p), ("acxListBytes", C.c_uint64), ("badList", u32p), ("badSz", C.c_uint32),
-                ("identityMap", C.c_int), ("owned", C.c_void_p * 32), ("nOwned", C.c_int), ("mapBase", C.c_void_p), ("mapLen", C.c_uint64)]
+                ("identityMap", C.c_int), ("owned", C.c_void_p * 32), ("nOwned", C.c_int), ("mapBase", C.c_void_p), ("mapLen", C.c_uint64),
+                ("fragLen", u32p)]
+
+
+class BhDnaStats(C.Structure):
+    _fields_ = [("device", C.c_int), ("W", C.c_uint32), ("shear", C.c_uint32), ("ov", C.c_uint32), ("partitions", C.c_uint32),
+                ("maxChain", C.c_uint64), ("maxSh", C.c_uint64), ("eligible", C.c_uint64), ("chunks", C.c_uint64), ("exactChunks", C.c_uint64),
+                ("peakDeviceBytes", C.c_uint64), ("symbols", C.c_uint64), ("fragments", C.c_uint64),
+                ("secParse", C.c_double), ("secMarks", C.c_double), ("secShear", C.c_double), ("secStages", C.c_double),
+                ("secUpload", C.c_double), ("secSort", C.c_double), ("secClassify", C.c_double), ("secMark", C.c_double), ("note", C.c_char * 256)]
 
 
 class BhQueries(C.Structure):
@@ -89,6 +98,8 @@ def lib():
         L.bh_edx_read.argtypes = [C.c_char_p, C.POINTER(BhDb)]
         L.bh_acx_read.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(BhDb)]
         L.bh_db_from_fasta.argtypes = [C.c_char_p, C.c_uint32, C.c_float, C.c_int, C.c_long, C.c_int, C.POINTER(BhDb)]
+        L.bh_db_from_fasta_dna.argtypes = [C.c_char_p, C.c_uint32, C.c_float, C.c_long, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.POINTER(BhDb), C.POINTER(BhDnaStats)]
+        L.bh_dna_marks_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
         L.bh_edx_write.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_long, C.c_float]
         L.bh_acx_build.argtypes = [C.POINTER(BhDb), C.c_int, C.c_int]
         L.bh_acx_write.argtypes = [C.POINTER(BhDb), C.c_char_p]
@@ -157,9 +168,18 @@ class Db:
         return d
 
     @classmethod
-    def from_fasta(cls, fasta, max_len_q, thres, shear_len=500, dedupe=True, K=None, z=1):
+    def from_fasta(cls, fasta, max_len_q, thres, shear_len=500, dedupe=True, K=None, z=1, layout="QUICK", partitions=1, device=-1, latency=16):
+        """layout="DNA" (or "RNA") with shear_len: the compressive build, its duplicate marks on `device` (< 0 = the host restatement);
+        the build's figures are in .dna_stats"""
         d = cls()
-        _chk(lib().bh_db_from_fasta(fasta.encode(), max_len_q, thres, 1 if shear_len else 0, shear_len or 0, int(dedupe), C.byref(d.c)))
+        if layout in ("DNA", "RNA") and shear_len:
+            st = BhDnaStats()
+            _chk(lib().bh_db_from_fasta_dna(fasta.encode(), max_len_q, thres, shear_len, partitions, int(dedupe), latency, device, C.byref(d.c), C.byref(st)))
+            d.dna_stats = st
+        elif layout in ("QUICK", "DNA", "RNA"):
+            _chk(lib().bh_db_from_fasta(fasta.encode(), max_len_q, thres, 1 if shear_len else 0, shear_len or 0, int(dedupe), C.byref(d.c)))
+        else:
+            raise ValueError("layout must be QUICK, DNA or RNA")
         d._open = True
         d.c.identityMap = 0            # a database, not a direct-FASTA run
         if K:
@@ -569,3 +589,14 @@ def edx_merge(paths, out):
 def synth_reads(refs, path, n_reads, read_len, edits, rc=False, iupac=0.0, seed=42, first_read=0, append=False):
     e = np.ascontiguousarray(edits, np.uint32)
     _chk(lib().bh_synth_reads_ex(refs.encode(), path.encode(), n_reads, read_len, e.ctypes.data_as(u32p), len(e), int(rc), iupac, seed, first_read, int(append)))
+
+
+def dna_marks(sym, ref_start, ref_len, W, max_chain=0, max_sh=0):
+    """the host restatement of one -d DNA partition's duplicate marks (bh_dna_marks_host): (flags, max_chain, max_sh)"""
+    sym = np.ascontiguousarray(sym, np.uint8)
+    rs = np.ascontiguousarray(ref_start, np.uint64)
+    rl = np.ascontiguousarray(ref_len, np.uint32)
+    flags = np.zeros(len(sym) + 1, np.uint8)
+    mc, ms = C.c_uint64(max_chain), C.c_uint64(max_sh)
+    _chk(lib().bh_dna_marks_host(sym.ctypes.data, rs.ctypes.data, rl.ctypes.data, len(rs), W, C.byref(mc), C.byref(ms), flags.ctypes.data))
+    return flags[:len(sym)], mc.value, ms.value

@@ -285,6 +285,19 @@ BHIP_API int bhip_sync_hits(void *handle);
 BHIP_API int bhip_sort_queries(int device, const uint8_t *codes, uint64_t codes_bytes, const uint64_t *start, const uint32_t *len,
                       uint64_t n, uint32_t max_len, uint32_t *perm, uint8_t *is_new);
 
+/* Duplicate marks of the compressive database build (-d DNA, the reference's process_references DNA_16 branch, burst.c:1899-2023)
+ * for one partition, on the device; needs no handle.  sym = the partition's symbol codes (one byte each, 0..15), sym_len bytes from
+ * the first reference's first symbol to the last one's end; reference r covers [ref_start[r], ref_start[r] + ref_len[r]) of it
+ * (ascending).  W = shear + overlap >= 24.  Every position j < ref_len - W whose first 13 symbols are A/C/G/T is binned by that
+ * 13-mer; classes of equal symbols [13, 24) and of equal windows [13, W) inside a bin give the two convs, and flags[p] (one byte
+ * per position of [0, sym_len), written in full) = their OR.  *max_chain / *max_sh are the reference's state across partitions:
+ * when both are 0 on entry this partition's tally sets them.  BHIP_E_ARG when a duplicate window meets max_chain == 0 (where the
+ * reference divides by zero), BHIP_E_DEVICE when there is no usable device.  info (may be NULL): [0] eligible positions, [1]
+ * chunks of bins, [2] chunks that a hash collision sent down the exact path, [3] peak device bytes, [4..7] microseconds of
+ * upload, sort, classification and marking. */
+BHIP_API int bhip_dna_marks(int device, const uint8_t *sym, uint64_t sym_len, const uint64_t *ref_start, const uint32_t *ref_len,
+                            uint64_t n_refs, uint32_t W, uint64_t *max_chain, uint64_t *max_sh, uint8_t *flags, uint64_t *info);
+
 /* Tuning knobs.  "prefilter_stride": 0 (default) = automatic sparse seeds -- per query the largest stride s <= K for
  * which an alignment within budget still keeps >= 3 of the words starting at 0, s, 2s, ... (one edit destroys at most
  * ceil(K/s) of them), fewest .acx look-ups with the same no-false-negative guarantee; s >= 1 forces every s-th word,
