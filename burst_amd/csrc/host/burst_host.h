@@ -263,6 +263,47 @@ int  bh_report_tax(FILE *out, const BhDb *db, const BhQueries *q, const BhipHit 
 /* the same over records that lie in several runs (the records of an entry inside one run, contiguous) */
 int  bh_report_view(FILE *out, const BhDb *db, const BhQueries *q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx, uint64_t *nLines);
 
+/* ---- a session: the database stays on the devices, a list of query files runs through it (bh_session.c) ---- */
+typedef struct BhSession BhSession;
+typedef struct BhSessionOpts {            /* fixed for the whole session */
+	BhMode mode; float thres; int do_rc, incl_ws, z, do_accel, K, skip_ambig, rep_flags;      /* K = 0 with do_accel: the accelerator file's (db->K when a sample's turn comes) */
+	uint64_t batch;
+	int shard_db;                         /* number of database shards (0 / 1 = query-sharded), as for bh_search_multi_ex */
+	const BhTaxOpts *tax;                 /* NULL = no taxonomy column (copied; the BhTax it points to must outlive the session) */
+	int ingest_ahead;                     /* 1 = bh_session_prefetch parses a sample on a thread while the current one is searched and reported */
+	int verbose;                          /* 1 = the command line's per-sample lines on standard output */
+} BhSessionOpts;
+typedef struct BhSampleResult {
+	int rc; char err[512];
+	uint64_t totQ, numUniq, nHits, nLines; uint32_t nBatches;
+	double secIngest, secIngestWaited, secSearch, secReport;
+	BhipStats total;                      /* counters of the sample's batches, summed over this process's ranks */
+} BhSampleResult;
+/* ranks / n_local / n_ranks / comm / node: as for bh_search_multi_ex (the threads of this process: n_local = n_ranks; or one rank of a
+ * job of processes: n_local = 1).  The session keeps the pointers: `db`, `ranks` (whose handles may still be opened after this call,
+ * before the first sample is finished) and their runs belong to the caller and must outlive it.  BhMultiRank.align back ends work as
+ * in bh_search_multi_ex; they are handed the BhQueries of the sample being searched.  c0 is the caller's, the query ranges are the
+ * session's (set per sample). */
+int  bh_session_open(const BhDb *db, BhMultiRank *ranks, int n_local, int n_ranks, void *comm, BhNode *node, const BhSessionOpts *o, BhSession **s);
+/* start the ingest of the sample whose turn comes after the next bh_session_load / _run.  One ingest thread at a time: called while
+ * one is outstanding, the name is kept and its ingest starts as soon as that one has been taken.  Without ingest_ahead, or with
+ * BURST_HOST_SERIAL_INGEST set, it does nothing and every sample is read when its turn comes. */
+int  bh_session_prefetch(BhSession *s, const char *queries);
+/* one sample: bh_session_run = bh_session_load (ingest or take the prefetched tables, bins, shear check, create the output) +
+ * bh_session_finish (page-lock, buffers, search, report, release).  Between the two a launcher of several processes sees the sample
+ * (bh_session_sample), agrees on its status with the other ranks and sizes their hand-over (bh_session_set_node); bh_session_drop
+ * gives the loaded sample up.  BH_E_USAGE / BH_E_IO of a sample are recorded in `res` and leave the session usable (no output file is
+ * left behind); every error of the search, BH_E_OOM, BH_E_DEVICE and BH_E_INTERNAL end it: later calls return that code at once.
+ * In a job of processes only rank 0 writes; the other ranks pass through the search and return the sample's status. */
+int  bh_session_load(BhSession *s, const char *queries, const char *out_path, BhSampleResult *res);
+int  bh_session_finish(BhSession *s, BhSampleResult *res);
+int  bh_session_drop(BhSession *s);
+int  bh_session_run(BhSession *s, const char *queries, const char *out_path, BhSampleResult *res);
+const BhQueries *bh_session_sample(const BhSession *s);
+void bh_session_set_node(BhSession *s, BhNode *node);
+int  bh_session_ended(const BhSession *s);      /* 0, or the code of the error that ended the session */
+void bh_session_close(BhSession *s);
+
 const char *bh_last_error(void);
 int bh_set_error(int code, const char *fmt, ...);
 

@@ -3,10 +3,12 @@
  *   burst_hip -r DB.edx -a DB.acx -q reads.fa -o out.b6 -m {BEST|ALLPATHS|CAPITALIST|FORAGE|ANY} -i 0.97 [-fr] [-y] [-w]
  *   burst_hip -r refs.fa -q reads.fa -o out.b6 [-s [len]]            direct FASTA (exhaustive, no accelerator)
  *   burst_hip -r refs.fa -d [QUICK|DNA|RNA] [qLen] -o DB.edx [-a DB.acx] [-s [len]] [-dp N] -i 0.97      database construction
+ *   burst_hip -r DB.edx (-a DB.acx | -ad) --samples LIST -m ... -i ...    a list of `queries<TAB>output` against the one resident database (bh_session.c)
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
  * reference's exit code 1.  Extra flags: --device N, --batch N (unique queries per device call), -k {12|15}.
  */
+#define _GNU_SOURCE      /* getline */
 #include "burst_host.h"
 #include <stdlib.h>
 #include <string.h>
@@ -56,6 +58,180 @@ static void *ingest_main(void *p) {
 	return NULL;
 }
 
+/* the database onto the devices of the n_gpus ranks (one host thread each): replicated, or -- shard_db -- rank r the clumps of shard
+ * r % n_shards (slices[r], ranks[r].c0); prints the device lines; returns 0 or the exit code */
+static int open_devices(const BhDb *db, int n_gpus, const int *dev_list, int shard_db, int n_shards, int accel_dev, int K, int z,
+                        void **hhs, BhMultiRank *ranks, BhDb *slices) {
+	int rcs[BH_MAX_GPUS]; char errs[BH_MAX_GPUS][512];
+	for (int r = 0; r < BH_MAX_GPUS; ++r) rcs[r] = BH_E_INTERNAL;
+	int shared_dev = 0;
+	for (int a = 0; a < n_gpus; ++a) for (int b = a + 1; b < n_gpus; ++b) shared_dev |= dev_list[a] == dev_list[b];
+	omp_set_dynamic(0);
+	/* A replicated database whose accelerator is built on the devices (-ad): the ranks build it TOGETHER, each the lists of 1/N of the words,
+	 * and complete each other's tables device to device (bhip_build_accelerator_shared + bhip_team_share; BURST_HIP_SOLO_BUILD=1: every
+	 * rank builds the whole thing as before).  The gates of the devices are held here, around the ranks: ranks on one device meet inside. */
+	void *team = NULL;
+	const int coop = n_gpus > 1 && !shard_db && accel_dev && !db->hasAcx && !getenv("BURST_HIP_SOLO_BUILD");
+	if (coop && bhip_team_create(n_gpus, &team)) { fprintf(stderr, "libburst_hip: %s\n", bhip_last_error()); return 4; }
+	if (coop) {
+		for (int a = 0; a < n_gpus; ++a) { int seen = 0; for (int b = 0; b < a; ++b) seen |= dev_list[a] == dev_list[b]; if (!seen) bh_device_gate(dev_list[a], 1); }
+		printf("Accelerator: built by the %d ranks together (word ranges, device-to-device exchange)\n", n_gpus);
+	}
+	#pragma omp parallel num_threads(n_gpus)
+	{
+		const int r = omp_get_thread_num();
+		const BhDb *part = db;
+		rcs[r] = BH_OK;
+		if (coop) {
+			if (omp_get_num_threads() != n_gpus) rcs[r] = BH_E_INTERNAL;      /* (no team: nobody enters the exchange) */
+			else if ((rcs[r] = bh_device_open_shared(db, dev_list[r], z, K, r, n_gpus, bhip_team_share, team, &hhs[r]))) snprintf(errs[r], sizeof errs[r], "%s", bh_last_error());
+		} else {
+		if (shard_db) {      /* this rank's clumps: a view of the clump area + (with an .acx) the lists restricted to it */
+			uint32_t c0, c1;
+			bh_clump_shard(db, n_shards, r % n_shards, &c0, &c1);
+			ranks[r].c0 = c0;
+			if ((rcs[r] = bh_db_slice(db, c0, c1, &slices[r]))) snprintf(errs[r], sizeof errs[r], "%s", bh_last_error());
+			part = &slices[r];
+		}
+		/* ranks that share a device (--devices 0,0,...: diagnostics on a one-GPU machine) open their handles one after the other:
+		 * the accelerator build sizes its scratch from the memory that is free when it starts */
+		if (!rcs[r] && shared_dev) {
+			#pragma omp critical (bh_device_open)
+			if ((rcs[r] = bh_device_open_ex(part, dev_list[r], z, accel_dev ? K : 0, &hhs[r]))) snprintf(errs[r], sizeof errs[r], "%s", bh_last_error());
+		} else if (!rcs[r] && (rcs[r] = bh_device_open_ex(part, dev_list[r], z, accel_dev ? K : 0, &hhs[r]))) snprintf(errs[r], sizeof errs[r], "%s", bh_last_error());
+		}
+	}
+	if (coop) for (int a = 0; a < n_gpus; ++a) { int seen = 0; for (int b = 0; b < a; ++b) seen |= dev_list[a] == dev_list[b]; if (!seen) bh_device_gate(dev_list[a], 0); }
+	if (team) bhip_team_destroy(team);
+	for (int r = 0; r < n_gpus; ++r) if (rcs[r]) { fprintf(stderr, "%s\n", rcs[r] == BH_E_INTERNAL ? "OpenMP did not start one host thread per GPU" : errs[r]); return 4; }
+	for (int r = 0; r < n_gpus; ++r) { char nm[256]; int ncu = 0; uint64_t hbm = 0; if (!bhip_device_info(hhs[r], nm, sizeof nm, &ncu, &hbm)) printf("Device %d: %s, %d CUs, %.0f GiB\n", dev_list[r], nm, ncu, hbm / 1073741824.0); }
+	if (shard_db) for (int r = 0; r < n_gpus; ++r) printf("Rank %d: replica group %d, clumps [%u, %u)\n", r, r / n_shards, ranks[r].c0, ranks[r].c0 + slices[r].numRclumps);
+	return 0;
+}
+
+/* ---- --samples LIST: a list of query files against one resident database, each to its own .b6 (bh_session.c) ---- */
+typedef struct {
+	const char *ref_FN, *xcel_FN, *tax_FN, *list_FN;
+	BhMode mode; float thres; int z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device;
+	int n_gpus, n_gpus_given, n_dev_list, *dev_list, shard_db, n_shards; uint64_t batch; BhTaxOpts *txo;
+} SamplesArgs;
+typedef struct { char *q, *o; int line; } Sample;
+
+/* `queries<TAB>output` per line; blank lines and lines that start with '#' are skipped.  Returns 0 or the exit code. */
+static int read_sample_list(const SamplesArgs *a, Sample **out, int *n_out) {
+	FILE *f = fopen(a->list_FN, "rb");
+	if (!f) { fprintf(stderr, "ERROR: Cannot open sample list: %s\n", a->list_FN); return 2; }
+	Sample *S = NULL; int n = 0, cap = 0, line = 0;
+	char *buf = NULL; size_t bcap = 0;
+	while (getline(&buf, &bcap, f) >= 0) {
+		++line;
+		size_t len = strlen(buf);
+		while (len && (buf[len - 1] == '\n' || buf[len - 1] == '\r')) buf[--len] = 0;
+		if (!len || buf[0] == '#') continue;
+		char *tab = strchr(buf, '\t');
+		if (!tab || tab == buf || !tab[1] || strchr(tab + 1, '\t')) { printf("ERROR: %s line %d: expected 'queries<TAB>output'\n", a->list_FN, line); fclose(f); return 1; }
+		*tab = 0;
+		if (n == cap) { cap = cap ? 2 * cap : 64; S = realloc(S, (size_t)cap * sizeof(*S)); if (!S) { fclose(f); fputs("OOM:samples\n", stderr); return 3; } }
+		S[n].q = strdup(buf); S[n].o = strdup(tab + 1); S[n].line = line;
+		if (!S[n].q || !S[n].o) { fclose(f); fputs("OOM:samples\n", stderr); return 3; }
+		++n;
+	}
+	free(buf); fclose(f);
+	if (!n) { printf("ERROR: %s names no sample\n", a->list_FN); return 1; }
+	for (int i = 0; i < n; ++i) {
+		for (int k = 0; k < i; ++k) if (!strcmp(S[i].o, S[k].o)) { printf("ERROR: %s line %d: output '%s' is the output of line %d already\n", a->list_FN, S[i].line, S[i].o, S[k].line); return 1; }
+		for (int k = 0; k < n; ++k) if (!strcmp(S[i].o, S[k].q)) { printf("ERROR: %s line %d: output '%s' is the query file of line %d\n", a->list_FN, S[i].line, S[i].o, S[k].line); return 1; }
+		if (!strcmp(S[i].o, a->ref_FN) || (a->xcel_FN && !strcmp(S[i].o, a->xcel_FN)) || !strcmp(S[i].o, a->list_FN)) {
+			printf("ERROR: %s line %d: output '%s' is the database, the accelerator or the list itself\n", a->list_FN, S[i].line, S[i].o); return 1;
+		}
+	}
+	*out = S; *n_out = n;
+	return 0;
+}
+
+static int samples_main(SamplesArgs *a) {
+	Sample *S = NULL; int nS = 0, rc;
+	{ const int e = read_sample_list(a, &S, &nS); if (e) return e; }
+	const int usedb = bh_is_edx(a->ref_FN);
+	if (usedb < 0) DIE(usedb);
+	/* direct FASTA references: their clumps depend on the longest query (burst.c:5151) -- there is nothing to keep resident */
+	if (!usedb) { puts("ERROR: --samples needs an .edx database (the clumps of FASTA references depend on the queries: nothing would stay resident)"); return 1; }
+	int K = a->K, shard_db = a->shard_db, n_shards = a->n_shards;
+	const int n_gpus = a->n_gpus;
+	if (n_gpus > BH_MAX_GPUS) { printf("ERROR: --gpus %d (max %d)\n", n_gpus, BH_MAX_GPUS); return 1; }
+	if (shard_db && !n_shards) n_shards = n_gpus;
+	if (!shard_db || n_shards < 2) { shard_db = 0; n_shards = 1; }
+	/* more shards than devices: one upload per shard per search -- nothing stays resident either (out of scope for --samples) */
+	if (shard_db && n_gpus == 1 && n_shards > 1) { puts("ERROR: --samples does not take the serial-shards path (--gpus 1 --shards S uploads every shard for every search)"); return 1; }
+	if (n_gpus % n_shards) { printf("ERROR: --shards %d does not divide --gpus %d\n", n_shards, n_gpus); return 1; }
+	if (a->threads > 0) omp_set_num_threads(a->threads);
+	const double start = wall();
+	double tp = start;
+	#define PHASE(name) do { const double t_ = wall(); printf(" [%-28s %8.3f s]\n", name, t_ - tp); tp = t_; } while (0)
+	BhDb db; memset(&db, 0, sizeof db);
+	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
+	void *hhs[BH_MAX_GPUS]; BhMultiRank ranks[BH_MAX_GPUS]; BhDb slices[BH_MAX_GPUS];
+	memset(hhs, 0, sizeof hhs); memset(ranks, 0, sizeof ranks); memset(slices, 0, sizeof slices);
+	int dev_list[BH_MAX_GPUS];
+	for (int r = 0; r < n_gpus; ++r) dev_list[r] = a->n_dev_list ? a->dev_list[r] : (a->n_gpus_given ? r : a->device);
+	for (int r = 0; r < n_gpus; ++r) ranks[r].rank = r;
+	if (a->do_accel && a->accel_dev && !K) K = 12;
+	if (a->tax_FN) {                                                                 /* burst.c:5142-5149 (the session copies the options) */
+		if ((rc = bh_tax_load(a->tax_FN, &taxonomy))) DIE(rc);
+		a->txo->tax = &taxonomy;
+	}
+	/* the session first: the first sample is parsed on its ingest thread beside the database phases (as the single -q is) */
+	BhSessionOpts so; memset(&so, 0, sizeof so);
+	so.mode = a->mode; so.thres = a->thres; so.do_rc = a->do_rc; so.incl_ws = a->incl_ws; so.z = a->z; so.do_accel = a->do_accel; so.K = K;
+	so.skip_ambig = a->skip_ambig; so.rep_flags = a->rep_flags; so.batch = a->batch; so.shard_db = shard_db ? n_shards : 0; so.tax = a->tax_FN ? a->txo : NULL;
+	so.ingest_ahead = 1; so.verbose = 1;
+	BhSession *ses = NULL;
+	if ((rc = bh_session_open(&db, ranks, n_gpus, n_gpus, NULL, NULL, &so, &ses))) DIE(rc);
+	bh_queries_sort_device(dev_list[0]);      /* large query files are sorted on the (first) search device */
+	bh_session_prefetch(ses, S[0].q);
+	#define DIES(rc) do { bh_session_close(ses); DIE(rc); } while (0)
+	puts("\nEDB database provided. Parsing...");
+	if ((rc = bh_edx_read(a->ref_FN, &db))) DIES(rc);
+	if (db.xalpha) { bh_session_close(ses); fputs("ERROR: DB made with Xalpha; queries can't use Xalpha.\n", stderr); return 1; }
+	printf(" --> EDB: %u refs [%u orig], %u clumps, %u maxR\n", db.totR, db.origTotR, db.numRclumps, db.maxLenR);
+	if (a->do_accel && a->accel_dev) printf(" --> [Accel] K=%d, built on the device from the database\n", K);
+	else if (a->do_accel) {
+		if ((rc = bh_acx_read(a->xcel_FN, K, a->z, &db))) DIES(rc);      /* K = 0: 12 or 15, whichever the file's exact size says */
+		K = db.K;
+		printf(" --> [Accel] K=%d, %s format, %u ambiguous clumps\n", K, db.acxFmt ? "LARGE" : "SMALL", db.badSz);
+	}
+	PHASE("database read");
+	if (shard_db && (uint32_t)n_shards > db.numRclumps) { bh_session_close(ses); puts("ERROR: more database shards than clumps"); return 1; }
+	{ const int e = open_devices(&db, n_gpus, dev_list, shard_db, n_shards, a->accel_dev, K, a->z, hhs, ranks, slices); if (e) { bh_session_close(ses); return e; } }
+	for (int r = 0; r < n_gpus; ++r) ranks[r].hh = hhs[r];
+	PHASE("device database upload");
+	int n_failed = 0, first_fail = 0, n_done = 0;
+	for (int i = 0; i < nS; ++i) {
+		printf("Sample %d/%d: %s -> %s\n", i + 1, nS, S[i].q, S[i].o);
+		if (i + 1 < nS) bh_session_prefetch(ses, S[i + 1].q);
+		BhSampleResult res;
+		rc = bh_session_run(ses, S[i].q, S[i].o, &res);
+		if (rc) {
+			printf("Sample %d/%d FAILED (exit code %d): %s\n", i + 1, nS, code_to_exit(rc), res.err);
+			if (!n_failed++) first_fail = code_to_exit(rc);
+			/* usage and I/O errors are the sample's own; after anything else nothing more is started on a device */
+			if (bh_session_ended(ses)) { n_failed += nS - 1 - i; printf("The session ends here: %d sample(s) not started\n", nS - 1 - i); break; }
+		} else ++n_done;
+		fflush(stdout);
+	}
+	printf("\nSamples: %d done, %d failed. Alignment time: %f seconds\n", n_done, n_failed, wall() - start);
+	fflush(NULL);
+	#undef PHASE
+	#undef DIES
+	if (!getenv("BURST_HOST_TEARDOWN")) _exit(first_fail);      /* (as the single-sample path: the operating system releases a finished process's memory faster) */
+	bh_session_close(ses);
+	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); bh_run_free(&ranks[r].run); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
+	bh_db_free(&db); bh_tax_free(&taxonomy);
+	for (int i = 0; i < nS; ++i) { free(S[i].q); free(S[i].o); }
+	free(S);
+	return first_fail;
+}
+
 static void usage(void) {
 	puts("\nburst_hip: BURST-compatible optimal aligner, MI355X (gfx950) device path");
 	puts("--references (-r) <name>: FASTA/edx DB of reference sequences [required]");
@@ -74,6 +250,8 @@ static void usage(void) {
 	puts("--shards <S>: database shards (implies --shard db; default = --gpus): the ranks form gpus / S replica groups of S shards, the queries cut over the groups");
 	puts("--device <int>, --batch <int>, -k <12|15>, --make-acx <name> (with -r DB.edx: rebuild the accelerator of a database)");
 	puts("--accelerator-device (-ad): no .acx file, the device builds the accelerator from the .edx (word length -k, default 12)");
+	puts("--samples <list>: align a list of query files against the one resident database, each to its own output; one sample per line,");
+	puts("                  'queries<TAB>output' (in place of -q / -o; needs -r DB.edx; the database is read, uploaded and indexed once)");
 	puts("--host-acx: build accelerators (-d ... -a, --make-acx) with the host builder instead of the device");
 }
 
@@ -87,7 +265,7 @@ int main(int argc, char **argv) {
 	uint32_t latency = 16;                          /* burst.c:83 */
 	int n_gpus = 1, n_gpus_given = 0, gather_host = 1, n_dev_list = 0, dev_list[BH_MAX_GPUS], accel_dev = 0, host_acx = 0, shard_db = 0, n_shards = 0;
 	uint64_t batch = 1u << 21;      /* unique queries per device batch: the fixed cost of a batch (launches, synchronisation) is about 1 ms of device time */
-	const char *ref_FN = 0, *query_FN = 0, *output_FN = 0, *xcel_FN = 0, *mkacx_FN = 0, *tax_FN = 0;
+	const char *ref_FN = 0, *query_FN = 0, *output_FN = 0, *xcel_FN = 0, *mkacx_FN = 0, *tax_FN = 0, *samples_FN = 0;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
 	BhTaxOpts txo; memset(&txo, 0, sizeof txo); txo.taxacut = 10;   /* burst.c:92 */
 	setenv("GPU_MAX_HW_QUEUES", "8", 0);      /* HIP runtime: hardware queues for the library's four streams (read when the runtime starts) */
@@ -136,6 +314,7 @@ int main(int argc, char **argv) {
 		else if (!strcmp(a, "--skipambig") || !strcmp(a, "-sa")) skip_ambig = 1;
 		else if (!strcmp(a, "--noprogress")) { }
 		else if (!strcmp(a, "--no-dupe-hunt")) rep_flags |= BH_REP_NO_DUPE_HUNT;   /* diagnostics: print every (hit, reference) expansion */
+		else if (!strcmp(a, "--samples")) { NEEDARG("--samples"); samples_FN = argv[i]; }
 		else if (!strcmp(a, "--make-acx")) { NEEDARG("--make-acx"); mkacx_FN = argv[i]; }
 		else if (!strcmp(a, "--device")) { NEEDARG("--device"); device = atoi(argv[i]); }
 		else if (!strcmp(a, "--gpus")) { NEEDARG("--gpus"); n_gpus = atoi(argv[i]); n_gpus_given = 1; if (n_gpus < 1) { puts("ERROR: --gpus must be >= 1"); return 1; } }
@@ -199,6 +378,18 @@ int main(int argc, char **argv) {
 	}
 	if (n_dev_list && !n_gpus_given) { n_gpus = n_dev_list; n_gpus_given = 1; }
 	if (n_dev_list && n_dev_list != n_gpus) { puts("ERROR: --devices must name one device per --gpus rank"); return 1; }
+	if (samples_FN) {
+		/* per sample what a separate invocation writes; everything checked here is checked before a device is touched.  Out of scope:
+		 * per-sample identity / mode, FASTA references, -x, serial shards and the RCCL gather (refused below and in samples_main) */
+		if (query_FN || output_FN || makedb || mkacx_FN) { puts("ERROR: --samples names the query files and outputs itself: it does not go with -q, -o, -d or --make-acx"); return 1; }
+		if (!ref_FN) { puts("ERROR: --samples needs -r DB.edx"); return 1; }
+		if (xalpha) { puts("ERROR: --samples does not take -x (raw alphabets work against FASTA references only)"); return 1; }
+		if (!gather_host) { puts("ERROR: --samples takes the host gather only (drop --gather rccl)"); return 1; }
+		if (accel_dev && xcel_FN) { puts("ERROR: -ad builds the accelerator on the device; drop -a"); return 1; }
+		SamplesArgs sa = {ref_FN, xcel_FN, tax_FN, samples_FN, mode, thres, z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device,
+		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo};
+		return samples_main(&sa);
+	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
 		if (!ref_FN) { puts("ERROR: --make-acx needs -r DB.edx"); return 1; }
 		BhDb db; int rc0;
@@ -318,10 +509,9 @@ int main(int argc, char **argv) {
 	 * the counts + grouped ncclSend / ncclRecv; minima by ncclAllReduce MIN) -- N shares through rank 0's one PCIe link: the path
 	 * for ranks that cannot see each other's memory.  --gpus 1 --gather rccl takes the RCCL path with one rank. */
 	if (n_gpus > BH_MAX_GPUS) { printf("ERROR: --gpus %d (max %d)\n", n_gpus, BH_MAX_GPUS); return 1; }
-	void *hhs[BH_MAX_GPUS]; int rcs[BH_MAX_GPUS]; char errs[BH_MAX_GPUS][512];
+	void *hhs[BH_MAX_GPUS];
 	BhMultiRank ranks[BH_MAX_GPUS]; BhDb slices[BH_MAX_GPUS]; uint64_t ru0[BH_MAX_GPUS], ru1[BH_MAX_GPUS];
 	memset(hhs, 0, sizeof hhs); memset(ranks, 0, sizeof ranks); memset(slices, 0, sizeof slices);
-	for (int r = 0; r < BH_MAX_GPUS; ++r) rcs[r] = BH_E_INTERNAL;
 	void *comm = NULL;
 	const int use_rccl = n_gpus_given && !gather_host;
 	if (shard_db && !n_shards) n_shards = n_gpus;
@@ -371,48 +561,7 @@ int main(int argc, char **argv) {
 	if (shard_db && (uint32_t)n_shards > db.numRclumps) { puts("ERROR: more database shards than clumps"); return 1; }
 	if (!n_dev_list) for (int r = 0; r < n_gpus; ++r) dev_list[r] = n_gpus_given ? r : device;
 	if (use_rccl && bhip_comm_create(n_gpus, dev_list, &comm)) { fprintf(stderr, "libburst_hip: %s\n", bhip_last_error()); return 4; }
-	int shared_dev = 0;
-	for (int a = 0; a < n_gpus; ++a) for (int b = a + 1; b < n_gpus; ++b) shared_dev |= dev_list[a] == dev_list[b];
-	omp_set_dynamic(0);
-	/* A replicated database whose accelerator is built on the devices (-ad): the ranks build it TOGETHER, each the lists of 1/N of the words,
-	 * and complete each other's tables device to device (bhip_build_accelerator_shared + bhip_team_share; BURST_HIP_SOLO_BUILD=1: every
-	 * rank builds the whole thing as before).  The gates of the devices are held here, around the ranks: ranks on one device meet inside. */
-	void *team = NULL;
-	const int coop = n_gpus > 1 && !shard_db && accel_dev && !db.hasAcx && !getenv("BURST_HIP_SOLO_BUILD");
-	if (coop && bhip_team_create(n_gpus, &team)) { fprintf(stderr, "libburst_hip: %s\n", bhip_last_error()); return 4; }
-	if (coop) {
-		for (int a = 0; a < n_gpus; ++a) { int seen = 0; for (int b = 0; b < a; ++b) seen |= dev_list[a] == dev_list[b]; if (!seen) bh_device_gate(dev_list[a], 1); }
-		printf("Accelerator: built by the %d ranks together (word ranges, device-to-device exchange)\n", n_gpus);
-	}
-	#pragma omp parallel num_threads(n_gpus)
-	{
-		const int r = omp_get_thread_num();
-		const BhDb *part = &db;
-		rcs[r] = BH_OK;
-		if (coop) {
-			if (omp_get_num_threads() != n_gpus) rcs[r] = BH_E_INTERNAL;      /* (no team: nobody enters the exchange) */
-			else if ((rcs[r] = bh_device_open_shared(&db, dev_list[r], z, K, r, n_gpus, bhip_team_share, team, &hhs[r]))) snprintf(errs[r], sizeof errs[r], "%s", bh_last_error());
-		} else {
-		if (shard_db) {      /* this rank's clumps: a view of the clump area + (with an .acx) the lists restricted to it */
-			uint32_t c0, c1;
-			bh_clump_shard(&db, n_shards, r % n_shards, &c0, &c1);
-			ranks[r].c0 = c0;
-			if ((rcs[r] = bh_db_slice(&db, c0, c1, &slices[r]))) snprintf(errs[r], sizeof errs[r], "%s", bh_last_error());
-			part = &slices[r];
-		}
-		/* ranks that share a device (--devices 0,0,...: diagnostics on a one-GPU machine) open their handles one after the other:
-		 * the accelerator build sizes its scratch from the memory that is free when it starts */
-		if (!rcs[r] && shared_dev) {
-			#pragma omp critical (bh_device_open)
-			if ((rcs[r] = bh_device_open_ex(part, dev_list[r], z, accel_dev ? K : 0, &hhs[r]))) snprintf(errs[r], sizeof errs[r], "%s", bh_last_error());
-		} else if (!rcs[r] && (rcs[r] = bh_device_open_ex(part, dev_list[r], z, accel_dev ? K : 0, &hhs[r]))) snprintf(errs[r], sizeof errs[r], "%s", bh_last_error());
-		}
-	}
-	if (coop) for (int a = 0; a < n_gpus; ++a) { int seen = 0; for (int b = 0; b < a; ++b) seen |= dev_list[a] == dev_list[b]; if (!seen) bh_device_gate(dev_list[a], 0); }
-	if (team) bhip_team_destroy(team);
-	for (int r = 0; r < n_gpus; ++r) if (rcs[r]) { fprintf(stderr, "%s\n", rcs[r] == BH_E_INTERNAL ? "OpenMP did not start one host thread per GPU" : errs[r]); return 4; }
-	for (int r = 0; r < n_gpus; ++r) { char nm[256]; int ncu = 0; uint64_t hbm = 0; if (!bhip_device_info(hhs[r], nm, sizeof nm, &ncu, &hbm)) printf("Device %d: %s, %d CUs, %.0f GiB\n", dev_list[r], nm, ncu, hbm / 1073741824.0); }
-	if (shard_db) for (int r = 0; r < n_gpus; ++r) printf("Rank %d: replica group %d, clumps [%u, %u)\n", r, r / n_shards, ranks[r].c0, ranks[r].c0 + slices[r].numRclumps);
+	{ const int e = open_devices(&db, n_gpus, dev_list, shard_db, n_shards, accel_dev, K, z, hhs, ranks, slices); if (e) return e; }
 	PHASE("device database upload");
 	if (usedb) {
 		JOIN_INGEST();

@@ -75,6 +75,29 @@ class BhRunView(C.Structure):
         return out
 
 
+class BhTax(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("pair", C.c_void_p), ("blob", C.c_void_p)]
+
+
+class BhTaxOpts(C.Structure):
+    _fields_ = [("tax", C.POINTER(BhTax)), ("suppress", C.c_int), ("strict", C.c_int), ("taxacut", C.c_uint32), ("ncbi", C.c_int)]
+
+
+class BhSessionOpts(C.Structure):
+    _fields_ = [("mode", C.c_int), ("thres", C.c_float), ("do_rc", C.c_int), ("incl_ws", C.c_int), ("z", C.c_int), ("do_accel", C.c_int), ("K", C.c_int),
+                ("skip_ambig", C.c_int), ("rep_flags", C.c_int), ("batch", C.c_uint64), ("shard_db", C.c_int), ("tax", C.POINTER(BhTaxOpts)),
+                ("ingest_ahead", C.c_int), ("verbose", C.c_int)]
+
+
+class BhSampleResult(C.Structure):
+    _fields_ = [("rc", C.c_int), ("err", C.c_char * 512), ("totQ", C.c_uint64), ("numUniq", C.c_uint64), ("nHits", C.c_uint64), ("nLines", C.c_uint64),
+                ("nBatches", C.c_uint32), ("secIngest", C.c_double), ("secIngestWaited", C.c_double), ("secSearch", C.c_double), ("secReport", C.c_double),
+                ("total", capi.BhipStats)]
+
+
+E_USAGE, E_IO, E_OOM, E_INTERNAL, E_DEVICE = -1, -2, -3, -4, -5
+
+
 class HostError(RuntimeError):
     pass
 
@@ -137,6 +160,22 @@ def lib():
         L.bh_synth_reads_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint32, u32p, C.c_uint32, C.c_int, C.c_double, C.c_uint64, C.c_uint64, C.c_int]
         L.bh_edx_merge.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p]
         L.bh_score_lut.argtypes = [C.c_int, C.c_void_p]
+        L.bh_tax_load.argtypes = [C.c_char_p, C.POINTER(BhTax)]
+        L.bh_tax_free.argtypes = [C.POINTER(BhTax)]
+        L.bh_tax_free.restype = None
+        L.bh_session_open.argtypes = [C.POINTER(BhDb), C.POINTER(BhMultiRank), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(BhSessionOpts), C.POINTER(C.c_void_p)]
+        L.bh_session_prefetch.argtypes = [C.c_void_p, C.c_char_p]
+        L.bh_session_load.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(BhSampleResult)]
+        L.bh_session_finish.argtypes = [C.c_void_p, C.POINTER(BhSampleResult)]
+        L.bh_session_run.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(BhSampleResult)]
+        L.bh_session_drop.argtypes = [C.c_void_p]
+        L.bh_session_sample.argtypes = [C.c_void_p]
+        L.bh_session_sample.restype = C.POINTER(BhQueries)
+        L.bh_session_set_node.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_session_set_node.restype = None
+        L.bh_session_ended.argtypes = [C.c_void_p]
+        L.bh_session_close.argtypes = [C.c_void_p]
+        L.bh_session_close.restype = None
         _lib = L
     return _lib
 
@@ -279,6 +318,15 @@ class QuerySet:
         c = self.c
         self.n_reads, self.n_uniq, self.n_entries = int(c.totQ), int(c.numUniq), int(c.numEntries)
 
+    @classmethod
+    def view(cls, ptr):
+        """the query tables somebody else owns (a session's current sample: what its align back end is handed), not freed here"""
+        q = cls.__new__(cls)
+        q.c = C.cast(ptr, C.POINTER(BhQueries)).contents
+        q._borrowed = True
+        q.n_reads, q.n_uniq, q.n_entries = int(q.c.totQ), int(q.c.numUniq), int(q.c.numEntries)
+        return q
+
     def batch(self, u0=0, u1=None):
         """capi.Queries view (no copy for the forward-only case) of unique queries [u0, u1) with their RC twins"""
         c = self.c
@@ -314,7 +362,7 @@ class QuerySet:
         return int(off[min(u1, self.n_uniq)] - off[u0])
 
     def close(self):
-        if self.c.codes:
+        if self.c.codes and not getattr(self, "_borrowed", False):
             lib().bh_queries_free(C.byref(self.c))
 
     def __del__(self):
@@ -447,6 +495,139 @@ class RankSearch:
         self.all.close()
         if self.node is not None:
             self.node.close()
+
+
+class Session:
+    """A database that stays resident while query files run through it, each to its own .b6 (bh_session.c; burst_hip --samples):
+
+        db = host.Db.read("DB.edx", "DB.acx")
+        with host.Session(db, db.open_device(0), mode="BEST", thres=0.98) as s:
+            for i, (q, out) in enumerate(samples):
+                if i + 1 < len(samples):
+                    s.prefetch(samples[i + 1][0])      # parsed on a thread while this one is searched and reported
+                res = s.run(q, out)                    # dict: rc (0 = written), err, totQ, numUniq, nHits, nLines, seconds, stats
+
+    devs: a device handle (Db.open_device), a list of them (the ranks are threads of this process: query-sharded, or with shard_db = S
+    database-sharded over slices opened by the caller, c0 = their first clumps), or None with an `align` back end.  rank / world / node:
+    one rank of a job of processes (python -m burst_amd.run).  align(qs, ranges, mode_number) -> HIT_DTYPE records: a back end in place of
+    the device scheduler, handed the QuerySet of the sample being searched (the CPU tests put the oracle here); reduce_min as in RankSearch.
+    accel: the queries take the accelerator's route (default: the database was read with an .acx); K: word length of a device-built
+    accelerator (an .acx says its own).  A sample's usage or I/O error is its own (rc < 0 in the result, no output left); any other
+    error ends the session (`ended`)."""
+
+    def __init__(self, db, devs=None, mode="CAPITALIST", thres=0.97, rc=False, whitespace=False, z=1, accel=None, K=0, batch=1 << 21, shard_db=0,
+                 taxonomy=None, taxacut=10, tax_ncbi=False, tax_suppress=False, tax_strict=False, rep_flags=0, ingest_ahead=True,
+                 align=None, reduce_min=None, rank=0, world=None, c0=0, node=None, comm=None, verbose=False):
+        self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
+        devs = list(devs) if isinstance(devs, (list, tuple)) else [devs]
+        n_local = len(devs)
+        world = world or n_local
+        c0 = list(c0) if isinstance(c0, (list, tuple)) else [c0] * n_local
+        self.ranks = (BhMultiRank * n_local)()
+        for i, d in enumerate(devs):
+            mr = self.ranks[i]
+            mr.rank, mr.hh, mr.c0 = (rank if n_local == 1 else i), (d._h if d is not None else None), c0[i]
+            if align is not None:
+                mr.align = self._align_cb(align)
+            if reduce_min is not None:
+                mr.reduce_min = self._reduce_cb(reduce_min)
+        if any(d is None for d in devs) and align is None:
+            raise ValueError("a session needs device handles or an align back end")
+        accel = bool(db.c.hasAcx) if accel is None else bool(accel)
+        self.tax, self.taxo = BhTax(), BhTaxOpts()
+        o = BhSessionOpts()
+        o.mode, o.thres, o.do_rc, o.incl_ws, o.z, o.do_accel, o.K = MODES[mode], thres, int(rc), int(whitespace), z, int(accel), int(db.c.K) if db.c.hasAcx else K
+        o.rep_flags, o.batch, o.shard_db, o.ingest_ahead, o.verbose = rep_flags, batch, int(shard_db), int(ingest_ahead), int(verbose)
+        if taxonomy:
+            _chk(lib().bh_tax_load(taxonomy.encode(), C.byref(self.tax)))
+            self.taxo.tax, self.taxo.suppress, self.taxo.strict, self.taxo.taxacut, self.taxo.ncbi = C.pointer(self.tax), int(tax_suppress), int(tax_strict), taxacut, int(tax_ncbi)
+            o.tax = C.pointer(self.taxo)
+        self.ended = False
+        _chk(lib().bh_session_open(C.byref(db.c), self.ranks, n_local, world, comm, node.h if node is not None else None, C.byref(o), C.byref(self.h)))
+
+    def _align_cb(self, align):
+        def _align(ctx, q, u0, u1, n, mode, batch, run):
+            try:
+                h = np.ascontiguousarray(align(QuerySet.view(q), [(int(u0[i]), int(u1[i])) for i in range(n)], int(mode)), dtype=capi.HIT_DTYPE)
+                return int(lib().bh_run_put(run, h.ctypes.data_as(C.c_void_p), len(h)))
+            except Exception:      # (an exception must not cross the C frame)
+                import traceback
+                traceback.print_exc()
+                return E_DEVICE
+        self._cb.append(ALIGN_FN(_align))
+        return self._cb[-1]
+
+    def _reduce_cb(self, reduce_min):
+        def _reduce(ctx, buf, n):
+            try:
+                reduce_min(np.ctypeslib.as_array(buf, shape=(int(n),)))
+                return 0
+            except Exception:
+                import traceback
+                traceback.print_exc()
+                return E_DEVICE
+        self._cb.append(REDUCE_FN(_reduce))
+        return self._cb[-1]
+
+    @staticmethod
+    def _result(res):
+        d = {k: getattr(res, k) for k in ("rc", "totQ", "numUniq", "nHits", "nLines", "nBatches", "secIngest", "secIngestWaited", "secSearch", "secReport")}
+        d["err"] = res.err.decode("utf-8", "replace")
+        d["stats"] = res.total.as_dict()
+        return d
+
+    def _done(self, rc, res):
+        self.ended = bool(lib().bh_session_ended(self.h))
+        return self._result(res)
+
+    def prefetch(self, queries):
+        _chk(lib().bh_session_prefetch(self.h, queries.encode()))
+
+    def run(self, queries, out):
+        res = BhSampleResult()
+        return self._done(lib().bh_session_run(self.h, queries.encode(), out.encode() if out else None, C.byref(res)), res)
+
+    def load(self, queries, out):
+        """first half of run(): the sample's tables are in hand (`sample`), its output is created; finish() or drop() must follow"""
+        res = BhSampleResult()
+        return self._done(lib().bh_session_load(self.h, queries.encode(), out.encode() if out else None, C.byref(res)), res)
+
+    def finish(self):
+        res = BhSampleResult()
+        return self._done(lib().bh_session_finish(self.h, C.byref(res)), res)
+
+    def drop(self):
+        lib().bh_session_drop(self.h)
+
+    @property
+    def sample(self):
+        p = lib().bh_session_sample(self.h)
+        return QuerySet.view(p) if p else None
+
+    def set_node(self, node):
+        self.node = node
+        lib().bh_session_set_node(self.h, node.h if node is not None else None)
+
+    def close(self):
+        if self.h:
+            lib().bh_session_close(self.h)
+            self.h = C.c_void_p()
+            for i in range(len(self.ranks)):
+                lib().bh_run_free(C.byref(self.ranks[i].run))
+            if self.tax.n or self.tax.blob:
+                lib().bh_tax_free(C.byref(self.tax))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 libc = C.CDLL(None)
