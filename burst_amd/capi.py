@@ -64,8 +64,8 @@ def _load():
                           "burst_amd has no CPU fallback" % LIB_PATH)
     # The superseded prefilter kernels (options prefilter_cw = 0 / 1) are NOT in libburst_hip.so: the tests ask for the test-only library
     # that holds them (tests/conftest.py sets LOAD_LEGACY_PREFILTERS in THIS process; child processes -- bench.py, burst_hip -- run the
-    # product library alone).  Loaded first and globally, so that the product library's two weak references (bhip_internal.h:
-    # bhip_legacy_pf_launch / _attrs) resolve to it.
+    # product library alone).  Loaded first and globally, so that the product library's weak reference (bhip_internal.h:
+    # bhip_legacy_pf_kernel) resolves to it.
     legacy = os.path.join(os.path.dirname(LIB_PATH), "libburst_hip_legacy.so")
     if LOAD_LEGACY_PREFILTERS and os.path.exists(legacy):
         globals()["_legacy_lib"] = C.CDLL(legacy, mode=C.RTLD_GLOBAL)

@@ -2,6 +2,7 @@
 // bhip_reserve) and the kernel-level entry points (bhip_align_pairs, bhip_prefilter): what replaces the bodies of the two OpenMP
 // loops of do_alignments (burst.c:4077-4289, 4343-4484).  HIP-event timing of every phase on the stream it runs on.
 #include "bhip_handle.h"
+#include "bhip_pf_select.h"
 
 // ---- ordering of the output records: (q, refIx) ascending, done on the device.  A query has one or two records, rarely
 // more, so a counting sort by query (rank inside the query from the counting atomic, offsets from one exclusive scan)
@@ -180,10 +181,11 @@ static void launch_prefix_task(Handle *h, Lane *L, hipStream_t st, int NWP, uint
 	#undef LT
 }
 // Resident blocks per CU of a kernel from its static register / LDS use (512 VGPRs per SIMD lane granted in steps of 8, at
-// most 8 waves per SIMD; about 148 KB of LDS): the persistent grid-stride kernels are launched with exactly that many
-// blocks, a block that has to wait for a free slot would run its whole share after the others.
-static uint32_t blocks_per_cu(const void *fn, uint32_t threads, size_t dyn_lds) {
-	hipFuncAttributes fa;
+// most 8 waves per SIMD; about 148 KB of the 160 KB of LDS -- measured on gfx950: 11 single-wave blocks of 13 144 B fit a CU and 12 do
+// not, 10 of 14 168 B fit and 11 do not): the persistent grid-stride kernels are launched with exactly that many blocks, a block that
+// has to wait for a free slot would run its whole share after the others.  fa_out: what the runtime said about the kernel.
+static uint32_t blocks_per_cu(const void *fn, uint32_t threads, size_t dyn_lds, hipFuncAttributes *fa_out = nullptr) {
+	hipFuncAttributes fa_here, &fa = fa_out ? *fa_out : fa_here;
 	memset(&fa, 0, sizeof fa);
 	if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return 4;
 	const uint32_t waves_per_block = (threads + 63) / 64;
@@ -253,27 +255,37 @@ static int upload_plan(Handle *h, const uint8_t *q_codes, const uint64_t *q_off,
 	return 0;
 }
 
-// prefilter of list positions [0, n_list) of `d_qlist` on the lane's stream
-static int launch_prefilter(Handle *h, Lane *L, hipStream_t pf_st, const uint32_t *d_qlist, uint32_t n_list, uint2 *cand, uint32_t *candcnt, uint32_t cand_cap,
-                            bool with_bad, uint32_t *n_cand_dev, Counters *dc) {
-	const uint32_t *bad = with_bad ? h->bad.as<uint32_t>() : nullptr;
-	const uint32_t n_bad = with_bad ? h->n_bad : 0;
-	const uint32_t *plan = h->cur->plan.as<uint32_t>();
-	hipStream_t st = pf_st;
-	int rc;
-	// main pass: hashed counters, four queries per wave (any database size)
-	if ((rc = L->fb_list.reserve((size_t)n_list * 4 + 16))) return rc;
-	HIPCHK(hipMemsetAsync(&dc->n_fb, 0, 4, st));
-	L->fb_dirty = true;      // (the overflow list and its counter are shared with launch_prefilter_mask: a later class of this lane must not find them)
-	{
-		const uint32_t n_quads = (n_list + 3) / 4;
-		const uint32_t grid = std::min<uint32_t>(n_quads, (uint32_t)h->n_cu * 6);
-		hipLaunchKernelGGL(k_prefilter_hash, dim3(grid), dim3(64), 0, st, h->s_codes(), h->s_off(), h->s_emac(),
-			d_qlist, n_list, h->acx_view(), h->K, bad, n_bad, cand, candcnt, n_cand_dev, cand_cap, &dc->ent_read,
-			plan, L->fb_list.as<uint32_t>(), &dc->n_fb);
-		HIPCHK(hipGetLastError());
+// The overflow lists of a lane's prefilter: the list positions of the queries whose tables overflowed a pass, and how many.  Both prefilters
+// of a lane (clump-level: launch_prefilter; lane-resolved: launch_prefilter_mask) keep them in L->fb_list and count them in Counters::n_fb /
+// n_fb2, class after class.  INVARIANT: a second pass and the dense fallback only ever read the list and the counter that the first pass of
+// the SAME class wrote.  (Round 6's fuzzer under BHIP_POISON met a second pass that took the list positions of a 2-word class, counted by
+// the clump-level prefilter in n_fb, for those of the 4-word class behind it.)  So the counters are zero when a class begins -- by
+// enqueue_lane's reset of the whole counter block for the lane's first lane-resolved launch of a call, by a memset here otherwise; an
+// unconditional memset would be one more stream operation in front of every prefilter of the headline chain.
+struct PfOverflow {
+	uint32_t *fb1 = nullptr, *n_fb1 = nullptr;      // queries that overflowed the first pass
+	uint32_t *fb2 = nullptr, *n_fb2 = nullptr;      // ... and the second (lane-resolved prefilter only)
+	int begin(Lane *L, Counters *dc, hipStream_t st, uint32_t n_list, bool lane_resolved) {
+		int rc;
+		if ((rc = L->fb_list.reserve(lane_resolved ? (size_t)n_list * 8 + 64 : (size_t)n_list * 4 + 16))) return rc;
+		fb1 = L->fb_list.as<uint32_t>(); n_fb1 = &dc->n_fb;
+		if (lane_resolved) {
+			fb2 = fb1 + n_list + 8; n_fb2 = &dc->n_fb2;
+			if (L->pf_launches || L->fb_dirty) HIPCHK(hipMemsetAsync(&dc->n_fb, 0, 8, st));      // (n_fb, n_fb2)
+			L->fb_dirty = false;
+		} else {
+			HIPCHK(hipMemsetAsync(&dc->n_fb, 0, 4, st));
+			L->fb_dirty = true;      // (a later lane-resolved class of this lane must not find this count)
+		}
+		return 0;
 	}
-	// fallback pass for the (rare) queries whose table overflowed: dense per-clump counters, LDS if they fit, else global memory
+};
+
+// fallback pass for the (rare) queries of the overflow list `fb` (*n_fb of them): dense per-clump counters, LDS if they fit, else global
+// memory; (list position, clump) pairs into `cand`.  12 ms per launch at 6.8 M clumps whatever the number of queries.
+static int launch_dense_fallback(Handle *h, Lane *L, hipStream_t st, const uint32_t *d_qlist, uint32_t n_list, const uint32_t *bad, uint32_t n_bad,
+                                 uint2 *cand, uint32_t *candcnt, uint32_t *n_cand_dev, uint32_t cand_cap, Counters *dc, const uint32_t *fb, const uint32_t *n_fb) {
+	const uint32_t *plan = h->cur->plan.as<uint32_t>();
 	const bool narrow = h->cur->st_maxlen < 255u + (uint32_t)h->K;
 	const size_t lds_w = ((size_t)(h->n_clumps + (narrow ? 3 : 1)) / (narrow ? 4 : 2)) * 4 + 1536u * 4 + 512u * 8 + 512u * 4 + 16;
 	const uint32_t nw32 = (h->n_clumps + 1) / 2;
@@ -282,23 +294,42 @@ static int launch_prefilter(Handle *h, Lane *L, hipStream_t pf_st, const uint32_
 		const uint32_t grid = std::min<uint32_t>(n_list, (uint32_t)h->n_cu * per_cu);
 		if (narrow) hipLaunchKernelGGL(k_prefilter_wave<uint8_t>, dim3(grid), dim3(64), lds_w, st, h->s_codes(), h->s_off(),
 			h->s_emac(), d_qlist, n_list, h->acx_view(), h->K, h->n_clumps, bad, n_bad, cand, candcnt,
-			n_cand_dev, cand_cap, &dc->ent_read, plan, L->fb_list.as<uint32_t>(), &dc->n_fb);
+			n_cand_dev, cand_cap, &dc->ent_read, plan, fb, n_fb);
 		else hipLaunchKernelGGL(k_prefilter_wave<uint16_t>, dim3(grid), dim3(64), lds_w, st, h->s_codes(), h->s_off(),
 			h->s_emac(), d_qlist, n_list, h->acx_view(), h->K, h->n_clumps, bad, n_bad, cand, candcnt,
-			n_cand_dev, cand_cap, &dc->ent_read, plan, L->fb_list.as<uint32_t>(), &dc->n_fb);
+			n_cand_dev, cand_cap, &dc->ent_read, plan, fb, n_fb);
 	} else {
 		// dense counters in global memory, one workgroup per query (very large databases only)
-		uint32_t grid = std::min<uint32_t>(n_list, (uint32_t)h->n_cu * 2);
+		int rc;
+		const uint32_t grid = std::min<uint32_t>(n_list, (uint32_t)h->n_cu * 2);
 		if ((rc = L->gcnt.reserve((size_t)grid * nw32 * 4))) return rc;
 		hipLaunchKernelGGL(k_prefilter<false>, dim3(grid), dim3(256), 0, st, h->s_codes(), h->s_off(),
 			h->s_emac(), d_qlist, n_list, h->acx_view(), h->K, h->n_clumps,
-			L->gcnt.as<uint32_t>(), bad, n_bad, cand, candcnt, n_cand_dev, cand_cap, &dc->ent_read, L->fb_list.as<uint32_t>(), &dc->n_fb, plan);
+			L->gcnt.as<uint32_t>(), bad, n_bad, cand, candcnt, n_cand_dev, cand_cap, &dc->ent_read, fb, n_fb, plan);
 	}
 	HIPCHK(hipGetLastError());
 	return 0;
 }
 
-// lane-resolved prefilter: tasks (list position, reference lane) into L->tasks; queries whose table overflowed go through the
+// clump-level prefilter of list positions [0, n_list) of `d_qlist` on the lane's stream
+static int launch_prefilter(Handle *h, Lane *L, hipStream_t st, const uint32_t *d_qlist, uint32_t n_list, uint2 *cand, uint32_t *candcnt, uint32_t cand_cap,
+                            bool with_bad, uint32_t *n_cand_dev, Counters *dc) {
+	const uint32_t *bad = with_bad ? h->bad.as<uint32_t>() : nullptr;
+	const uint32_t n_bad = with_bad ? h->n_bad : 0;
+	int rc;
+	PfOverflow ov;
+	if ((rc = ov.begin(L, dc, st, n_list, false))) return rc;
+	{	// main pass: hashed counters, four queries per wave (any database size)
+		const uint32_t n_quads = (n_list + 3) / 4;
+		const uint32_t grid = std::min<uint32_t>(n_quads, (uint32_t)h->n_cu * 6);
+		hipLaunchKernelGGL(k_prefilter_hash, dim3(grid), dim3(64), 0, st, h->s_codes(), h->s_off(), h->s_emac(),
+			d_qlist, n_list, h->acx_view(), h->K, bad, n_bad, cand, candcnt, n_cand_dev, cand_cap, &dc->ent_read,
+			h->cur->plan.as<uint32_t>(), ov.fb1, ov.n_fb1);
+		HIPCHK(hipGetLastError());
+	}
+	return launch_dense_fallback(h, L, st, d_qlist, n_list, bad, n_bad, cand, candcnt, n_cand_dev, cand_cap, dc, ov.fb1, ov.n_fb1);
+}
+
 // words per query row of the range table (8 when no query of the class samples more)
 static uint32_t seed_row_words(uint32_t maxwords) { return maxwords <= 8 ? 8u : std::max<uint32_t>(16u, (maxwords + 15u) & ~15u); }
 // prefix words of the two-stage sweep for a class (0 = one-stage sweep): about 6 prefix symbols per allowed edit, shorter than the query vector
@@ -332,26 +363,11 @@ static int launch_peq(Handle *h, hipStream_t st, StageSlot *S, const uint32_t *d
 	}
 	return 0;
 }
-// k_seed_ranges for one (lane, class) list of staged batch S into the lane's per-class buffers
-// per-query counters of the counting-filter prefilter for an expected record stream (sampled words x occurrence-weighted mean list length)
-static int pf_table_bits(const Handle *h, int algo, double expect) {
-	return h->opt_pf_table ? h->opt_pf_table : algo == 0 ? (expect <= 600.0 ? 9 : expect <= 1200.0 ? 10 : 11) : (expect <= 230.0 ? 9 : expect <= 470.0 ? 10 : 11);
-}
-// Leaving out a query's longest list (k_seed_ranges: its guaranteed count drops from 4 to 3 for a 100-bp read at 98 %) walks ~21 % fewer
-// records -- and lets more of them through the counting filter: a record survives when its counter holds need - 1 OTHER records, and a
-// survivor costs about eight records' worth of work (exact-table insertion).  Measured at three database sizes:
-// it pays while the remaining stream loads the counters below ~0.35 per counter (19 GB database: 152 records on 512 counters, +6 %) and
-// costs at the metric's size (246 records: 8 % survivors instead of 2.5 %, -6 %); on small databases the kernel's time does not depend on
-// the records at all and the extra candidates only cost sweeps.  -1 = by that rule, 0 = never, n = whenever the count stays >= n.
+// whether k_seed_ranges leaves out a query's longest list: the rule, and what was measured, in bhip_pf_select.h
 static uint32_t seed_min_need_for(const Handle *h, double mean_words, uint32_t W16) {
-	if (h->opt_seed_min_need >= 0) return (uint32_t)h->opt_seed_min_need;
-	const double t_all = mean_words * h->acx_wmean;
-	const double t_less = t_all * (mean_words > 1.0 ? (mean_words - 1.0) / mean_words : 1.0) * 0.93;
-	// (k_prefilter_cf: a stream of at most 255 records counts in bytes: twice the counters; the streams of a batch scatter around their mean.
-	// k_prefilter_cw: 1 024 byte slots of list masks for up to 8 lists whatever the stream's length, 512 halfword slots beyond)
-	const double counters = h->opt_pf_cw ? (W16 <= 8 ? 1024.0 : 512.0) : (double)(1u << pf_table_bits(h, 0, t_all)) * (h->opt_pf_bytes && t_less <= 200.0 ? 2.0 : 1.0);
-	return (t_all >= 100.0 && t_less / counters <= 0.35) ? 3u : 0u;
+	return bhip_seed_min_need(h->opt_seed_min_need, h->opt_pf_cw, h->opt_pf_table, h->opt_pf_bytes, h->acx_wmean, mean_words, W16);
 }
+// k_seed_ranges for one (lane, class) list of staged batch S into the lane's per-class buffers
 static int launch_seed(Handle *h, Lane *L, hipStream_t st, StageSlot *S, int cls, const uint32_t *d_qlist, uint32_t n_list, uint32_t maxwords, double mean_words, bool ahead = false) {
 	int rc;
 	const uint32_t W16 = seed_row_words(maxwords);
@@ -381,143 +397,89 @@ static int launch_seed(Handle *h, Lane *L, hipStream_t st, StageSlot *S, int cls
 	return 0;
 }
 
-// dense clump-level kernels into L->cand as (list position, clump) pairs
+// the counting-filter kernel of a choice (bhip_pf_select.h), first pass (big = 0) or second pass over the queries that overflowed it
+// (big = 1: the largest tables); null: a superseded kernel and no test-only library in the process
+static bhip_pf_kernel_t pf_kernel(const BhipPfChoice &c, int big) {
+	if (c.legacy) return bhip_legacy_pf_kernel ? bhip_legacy_pf_kernel(c.kind, big ? 11 : c.htb, big ? 4 : c.rb, c.cw_mode, big) : nullptr;
+	if (c.kind == BHIP_PF_CQ) return c.cw_mode == 0 ? (big ? k_prefilter_cq<0, 1> : k_prefilter_cq<0, 0>) : (big ? k_prefilter_cq<1, 1> : k_prefilter_cq<1, 0>);
+	return big ? k_prefilter_cw<2, 1> : k_prefilter_cw<2, 0>;      // plans beyond 16 lists per query: one query per wave
+}
+
+// lane-resolved prefilter of a class (algo: bhip_pf_algo): tasks (list position, reference lane) into L->tasks; the queries that overflow its
+// tables go through the dense clump-level kernels into L->cand as (list position, clump) pairs
 static int launch_prefilter_mask(Handle *h, Lane *L, hipStream_t st, int cls, const uint32_t *d_qlist, uint32_t n_list, uint32_t maxwords, uint32_t *n_tasks_dev,
-                                 uint32_t *n_cand_dev, Counters *dc, int prune) {
+                                 uint32_t *n_cand_dev, Counters *dc, int algo, int prune) {
 	int rc;
-	if ((rc = L->fb_list.reserve((size_t)n_list * 8 + 64))) return rc;      // two lists: the queries that overflowed the first pass, and the second
-	// (n_fb, n_fb2; the lane's first class finds the whole counter block zeroed by enqueue_lane -- unless an earlier class went through the
-	// clump-level prefilter, which counts ITS overflowed queries in n_fb: round 6's fuzzer under BHIP_POISON met a second pass that took the
-	// list positions of a 2-word class for those of the 4-word class behind it)
-	if (L->pf_launches || L->fb_dirty) HIPCHK(hipMemsetAsync(&dc->n_fb, 0, 8, st));
-	L->fb_dirty = false;
-	uint32_t *fb1 = L->fb_list.as<uint32_t>(), *fb2 = fb1 + n_list + 8, *fb_dense = fb1;
-	uint32_t *n_fb_dense = &dc->n_fb;
+	PfOverflow ov;
+	if ((rc = ov.begin(L, dc, st, n_list, true))) return rc;
 	const uint32_t W16 = seed_row_words(maxwords);
+	const double mean_words = n_list ? (double)L->seed_words[cls] / (double)n_list : (double)maxwords;
 	// the lookups of this batch may have run ahead (seed_next_batch, during the previous call)
 	if (!(L->seeded_ok[cls] && L->seeded_seq[cls] == h->cur->seq && L->seeded_n[cls] == n_list && L->seeded_W16[cls] == W16))
-		if ((rc = launch_seed(h, L, st, h->cur, cls, d_qlist, n_list, maxwords, n_list ? (double)L->seed_words[cls] / (double)n_list : (double)maxwords))) return rc;
-	const int algo = h->opt_pf_algo >= 0 ? h->opt_pf_algo : L->pf_algo;
-	const uint32_t n_quads = (n_list + 3) / 4;
-	// hash table size per query from the expected number of distinct clumps (sampled words x occurrence-weighted mean list
-	// length): 512 slots keep 12 single-wave blocks on a CU, 1024 -> 7, 2048 -> 4
-	const double expect = (n_list ? (double)L->seed_words[cls] / (double)n_list : (double)maxwords) * h->acx_wmean;   // mean, not max: outliers use the fallback
-	// (the touched list holds half the slots; a query that exceeds it is re-done by the dense fallback, so the estimate -- an
-	// upper bound, every repeated clump counted once per word -- may be cut close)
-	// (counting filter: the approximate counters tolerate a load around 1 -- false survivors only cost work)
-	const int htb = pf_table_bits(h, algo, expect);
-	// resident single-wave blocks per CU from the kernel's static LDS / register use (measured on gfx950: 11 blocks of 13 144 B
-	// fit a CU and 12 do not, 10 of 14 168 B fit and 11 do not: about 148 KB of the 160 KB are available to them; 512 VGPRs per SIMD lane in steps of 8).  The kernel is a persistent loop over a static
-	// partition of the list: one block too many per CU would run after the others and double the time.
-	hipFuncAttributes fa;
-	memset(&fa, 0, sizeof fa);
-	// record blocks (64 per query) the counting-filter kernel keeps in registers: the expected stream of a query after the longest
-	// lists have been left out (expect counts them all: an upper bound), 2 .. 4; the wider tables only come with 2 or 4
-	int rb = h->opt_pf_rb ? h->opt_pf_rb : (expect <= 110.0 ? 2 : expect <= 230.0 ? 3 : 4);
-	if (htb != 9 && rb == 3) rb = 4;
-	const bool cw = algo == 0 && h->opt_pf_cw;      // k_prefilter_cw / k_prefilter_cq: the slot layout follows the number of lists a query can have
-	const int cw_mode = W16 <= 8 ? 0 : W16 <= 16 ? 1 : 2;
-	const bool cq = cw && h->opt_pf_cw == 2 && cw_mode < 2;      // four queries per wave, streams walked by the whole wave (up to 16 lists per query)
-	// (the superseded counting-filter kernels -- k_prefilter_cf, k_prefilter_cw<0 / 1>: options prefilter_cw = 0 / 1 -- are not in this library:
-	// libburst_hip_legacy.so, which the tests load in front of it, provides them through two weak symbols)
-	const bool legacy = algo == 0 && !cq && !(cw && cw_mode == 2);
-	if (legacy && (!bhip_legacy_pf_launch || !bhip_legacy_pf_attrs))
+		if ((rc = launch_seed(h, L, st, h->cur, cls, d_qlist, n_list, maxwords, mean_words))) return rc;
+	// expected number of distinct clumps of a query: sampled words x occurrence-weighted mean list length
+	const BhipPfChoice c = bhip_pf_choose(algo, h->opt_pf_cw, h->opt_pf_table, h->opt_pf_rb, W16, mean_words * h->acx_wmean);
+	const bool filter = c.kind != BHIP_PF_MASK, cw = c.kind == BHIP_PF_CW || c.kind == BHIP_PF_CQ;
+	const bhip_pf_kernel_t fp = filter ? pf_kernel(c, 0) : nullptr, fp2 = filter && c.two_pass ? pf_kernel(c, 1) : nullptr;
+	if (filter && (!fp || (c.two_pass && !fp2)))
 		return fail(BHIP_E_ARG, "option prefilter_cw = %d selects a superseded prefilter kernel that is not part of libburst_hip.so (tests: libburst_hip_legacy.so is loaded first)", h->opt_pf_cw);
-	{
-		const void *fp = cq ? (cw_mode == 0 ? (const void *)k_prefilter_cq<0, 0> : (const void *)k_prefilter_cq<1, 0>)
-			: cw && cw_mode == 2 ? (const void *)k_prefilter_cw<2, 0>
-			: algo == 0 ? nullptr
-			: (htb == 9 ? (const void *)k_prefilter_mask<9> : htb == 10 ? (const void *)k_prefilter_mask<10> : (const void *)k_prefilter_mask<11>);
-		if (legacy) { size_t lds = 0; int regs = 0; if (bhip_legacy_pf_attrs(cw ? 1 : 0, htb, rb, cw_mode, &lds, &regs)) { lds = 48 * 1024; regs = 128; } fa.sharedSizeBytes = lds; fa.numRegs = regs; }
-		else if (hipFuncGetAttributes(&fa, fp) != hipSuccess) { fa.sharedSizeBytes = 48 * 1024; fa.numRegs = 128; }
-	}
-	const uint32_t by_lds = (148u * 1024u) / (uint32_t)std::max<size_t>(512, (fa.sharedSizeBytes + 511) & ~(size_t)511);
-	const uint32_t by_reg = 4u * (512u / (uint32_t)std::max(8, (fa.numRegs + 7) & ~7));
-	const uint32_t fit = std::max<uint32_t>(1u, std::min<uint32_t>(cw ? 32u : 12u, std::min(by_lds, by_reg)));
+	// As many single-wave blocks per CU as are resident at once: the kernel is a persistent loop over a static partition of the list, one
+	// block too many per CU would run after the others and double the time.  (Should the runtime not know the kernel: 4.)
+	hipFuncAttributes fa;
+	const void *fn = filter ? (const void *)fp : c.htb == 9 ? (const void *)k_prefilter_mask<9> : c.htb == 10 ? (const void *)k_prefilter_mask<10> : (const void *)k_prefilter_mask<11>;
+	const uint32_t fit = std::min<uint32_t>(cw ? 32u : 12u, blocks_per_cu(fn, 64u, 0, &fa));
 	if (getenv("BHIP_DEBUG")) {
-		if (cw) fprintf(stderr, "[bhip] prefilter kernel: %s, slot mode %d, %zu B LDS, %d VGPRs -> %u blocks per CU\n", cq ? "four queries per wave, streams by the whole wave" : "one query per wave", cw_mode, fa.sharedSizeBytes, fa.numRegs, fit);
-		else fprintf(stderr, "[bhip] prefilter kernel: table 2^%d, %d record blocks in registers, %zu B LDS, %d VGPRs -> %u blocks per CU\n", htb, rb, fa.sharedSizeBytes, fa.numRegs, fit);
+		if (cw) fprintf(stderr, "[bhip] prefilter kernel: %s, slot mode %d, %zu B LDS, %d VGPRs -> %u blocks per CU\n", c.kind == BHIP_PF_CQ ? "four queries per wave, streams by the whole wave" : "one query per wave", c.cw_mode, fa.sharedSizeBytes, fa.numRegs, fit);
+		else fprintf(stderr, "[bhip] prefilter kernel: table 2^%d, %d record blocks in registers, %zu B LDS, %d VGPRs -> %u blocks per CU\n", c.htb, c.rb, fa.sharedSizeBytes, fa.numRegs, fit);
 	}
 	const uint32_t waves = h->opt_pf_waves ? std::min<uint32_t>((uint32_t)h->opt_pf_waves, fit) : fit;
-	const uint32_t grid = std::min<uint32_t>(cw && !cq ? n_list : n_quads, (uint32_t)h->n_cu * waves);
+	const uint32_t grid = std::min<uint32_t>(c.kind == BHIP_PF_CW ? n_list : (n_list + 3) / 4, (uint32_t)h->n_cu * waves);
 	HIPCHK(hipEventRecord(L->ev_pf[cls][1], st));
-	if (cw || algo == 0) {
+	const uint32_t *fb_dense = ov.fb1, *n_fb_dense = ov.n_fb1;
+	if (filter) {
+		auto launch = [&](bhip_pf_kernel_t k, uint32_t g, uint32_t *fb, uint32_t *n_fb, const uint32_t *sel, const uint32_t *n_sel) {
+			hipLaunchKernelGGL(k, dim3(g), dim3(64), 0, st, L->ranges_c[cls].as<uint2>(), L->hdr_c[cls].as<uint2>(), W16, n_list,
+				h->acx_view().rec, h->bad.as<uint32_t>(), h->n_bad,
+				h->clump_len.as<uint32_t>(), h->tot_refs, L->tasks.as<uint2>(), n_tasks_dev, (uint32_t)L->task_cap, &dc->ent_read,
+				fb, n_fb, &dc->unit_sum, &dc->col_sum, &dc->qlen_sum, &dc->surv_sum,
+				L->tasks2.as<uint2>(), &dc->n_tasks2_cls[cls], prune, sel, n_sel, c.kind == BHIP_PF_CF ? h->opt_pf_bytes : 0);
+		};
 		// first pass, then the queries whose survivors overflowed its exact lane table once more with the largest tables (BIG / <11, 4>);
 		// an empty second pass costs ~10 us, the dense per-clump fallback behind it 12 ms per launch at 6.8 M clumps whatever the number of queries
-#define PFW_ARGS(FB, NFB, SEL, NSEL) L->ranges_c[cls].as<uint2>(), L->hdr_c[cls].as<uint2>(), W16, n_list, \
-		h->acx_view().rec, h->bad.as<uint32_t>(), h->n_bad, \
-		h->clump_len.as<uint32_t>(), h->tot_refs, L->tasks.as<uint2>(), n_tasks_dev, (uint32_t)L->task_cap, &dc->ent_read, \
-		FB, NFB, &dc->unit_sum, &dc->col_sum, &dc->qlen_sum, &dc->surv_sum, \
-		L->tasks2.as<uint2>(), &dc->n_tasks2_cls[cls], prune, SEL, NSEL, 0
-		// the second pass of a strain-rich batch is not a handful of queries (round 5 gave it one block per CU): as many blocks as fit
-		const uint32_t g2 = (uint32_t)h->n_cu * std::max<uint32_t>(1u, std::min<uint32_t>(4u, blocks_per_cu(cw_mode == 0 ? (const void *)k_prefilter_cq<0, 1> : (const void *)k_prefilter_cq<1, 1>, 64u, 0)));
-		const bool two_pass = cw || htb != 11;
-		if (legacy) {
-			BhipPfLaunch a;
-			memset(&a, 0, sizeof a);
-			a.kind = cw ? 1 : 0; a.htb = htb; a.rb = rb; a.cw_mode = cw_mode; a.big = 0; a.grid = grid; a.stream = (void *)st;
-			a.ranges = L->ranges_c[cls].as<uint2>(); a.hdr = L->hdr_c[cls].as<uint2>(); a.W16 = W16; a.n_list = n_list; a.ent = h->acx_view().rec; a.bad = h->bad.as<uint32_t>(); a.n_bad = h->n_bad;
-			a.clump_len = h->clump_len.as<uint32_t>(); a.tot_refs = h->tot_refs; a.tasks = L->tasks.as<uint2>(); a.n_tasks = n_tasks_dev; a.task_cap = (uint32_t)L->task_cap; a.ent_read = &dc->ent_read;
-			a.fb = fb1; a.n_fb = &dc->n_fb; a.unit_sum = &dc->unit_sum; a.col_sum = &dc->col_sum; a.qlen_sum = &dc->qlen_sum; a.surv_sum = &dc->surv_sum;
-			a.tasks2 = L->tasks2.as<uint2>(); a.n_tasks2 = &dc->n_tasks2_cls[cls]; a.prune = prune; a.sel = nullptr; a.n_sel = nullptr; a.bytes = cw ? 0 : h->opt_pf_bytes;
-			if (bhip_legacy_pf_launch(&a)) return fail(BHIP_E_DEVICE, "launch of a legacy prefilter kernel failed");
-			if (two_pass) {
-				a.big = 1; a.htb = 11; a.rb = 4; a.grid = (uint32_t)h->n_cu; a.fb = fb2; a.n_fb = &dc->n_fb2; a.sel = fb1; a.n_sel = &dc->n_fb;
-				if (bhip_legacy_pf_launch(&a)) return fail(BHIP_E_DEVICE, "launch of a legacy prefilter kernel failed");
-			}
-		} else if (cq && cw_mode == 0) {
-			hipLaunchKernelGGL((k_prefilter_cq<0, 0>), dim3(grid), dim3(64), 0, st, PFW_ARGS(fb1, &dc->n_fb, (const uint32_t *)nullptr, (const uint32_t *)nullptr));
+		launch(fp, grid, ov.fb1, ov.n_fb1, nullptr, nullptr);
+		if (c.two_pass) {
 			HIPCHK(hipGetLastError());
-			hipLaunchKernelGGL((k_prefilter_cq<0, 1>), dim3(g2), dim3(64), 0, st, PFW_ARGS(fb2, &dc->n_fb2, (const uint32_t *)fb1, (const uint32_t *)&dc->n_fb));
-		} else if (cq) {
-			hipLaunchKernelGGL((k_prefilter_cq<1, 0>), dim3(grid), dim3(64), 0, st, PFW_ARGS(fb1, &dc->n_fb, (const uint32_t *)nullptr, (const uint32_t *)nullptr));
-			HIPCHK(hipGetLastError());
-			hipLaunchKernelGGL((k_prefilter_cq<1, 1>), dim3(g2), dim3(64), 0, st, PFW_ARGS(fb2, &dc->n_fb2, (const uint32_t *)fb1, (const uint32_t *)&dc->n_fb));
-		} else {      // plans beyond 16 lists per query: one query per wave
-			hipLaunchKernelGGL((k_prefilter_cw<2, 0>), dim3(grid), dim3(64), 0, st, PFW_ARGS(fb1, &dc->n_fb, (const uint32_t *)nullptr, (const uint32_t *)nullptr));
-			HIPCHK(hipGetLastError());
-			hipLaunchKernelGGL((k_prefilter_cw<2, 1>), dim3((uint32_t)h->n_cu), dim3(64), 0, st, PFW_ARGS(fb2, &dc->n_fb2, (const uint32_t *)fb1, (const uint32_t *)&dc->n_fb));
+			// the second pass of a strain-rich batch is not a handful of queries (round 5 gave it one block per CU): k_prefilter_cq gets as many
+			// blocks as fit, up to 4; the one-query-per-wave kernels one per CU
+			const uint32_t g2 = (uint32_t)h->n_cu * (c.kind == BHIP_PF_CQ ? std::min<uint32_t>(4u, blocks_per_cu((const void *)fp2, 64u, 0)) : 1u);
+			launch(fp2, g2, ov.fb2, ov.n_fb2, ov.fb1, ov.n_fb1);
+			fb_dense = ov.fb2; n_fb_dense = ov.n_fb2;
 		}
-#undef PFW_ARGS
-		if (two_pass) { fb_dense = fb2; n_fb_dense = &dc->n_fb2; }
 	} else {
 #define PFM_LAUNCH(B) hipLaunchKernelGGL(k_prefilter_mask<B>, dim3(grid), dim3(64), 0, st, L->ranges_c[cls].as<uint2>(), L->hdr_c[cls].as<uint2>(), W16, n_list, \
 		h->acx_view().rec, h->bad.as<uint32_t>(), h->n_bad, \
 		h->clump_len.as<uint32_t>(), h->tot_refs, L->tasks.as<uint2>(), n_tasks_dev, (uint32_t)L->task_cap, &dc->ent_read, \
-		fb1, &dc->n_fb, &dc->unit_sum, &dc->col_sum, &dc->qlen_sum, L->cand.as<uint2>(), n_cand_dev, (uint32_t)L->cand_cap)
-		if (htb == 9) PFM_LAUNCH(9); else if (htb == 10) PFM_LAUNCH(10); else PFM_LAUNCH(11);
+		ov.fb1, ov.n_fb1, &dc->unit_sum, &dc->col_sum, &dc->qlen_sum, L->cand.as<uint2>(), n_cand_dev, (uint32_t)L->cand_cap)
+		if (c.htb == 9) PFM_LAUNCH(9); else if (c.htb == 10) PFM_LAUNCH(10); else PFM_LAUNCH(11);
 #undef PFM_LAUNCH
 	}
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(L->ev_pf[cls][2], st));
 	++L->pf_launches;
-	L->pf_algo_used = cq ? 3 : cw ? 2 : algo;
-	// dense fallback for overflowed queries (clump-level pairs)
-	const uint32_t *bad = h->bad.as<uint32_t>();
-	const bool narrow = h->cur->st_maxlen < 255u + (uint32_t)h->K;
-	const size_t lds_w = ((size_t)(h->n_clumps + (narrow ? 3 : 1)) / (narrow ? 4 : 2)) * 4 + 1536u * 4 + 512u * 8 + 512u * 4 + 16;
-	const uint32_t nw32 = (h->n_clumps + 1) / 2;
-	if (lds_w <= 64 * 1024) {
-		const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(16, (160 * 1024) / lds_w));
-		const uint32_t g2 = std::min<uint32_t>(n_list, (uint32_t)h->n_cu * per_cu);
-		if (narrow) hipLaunchKernelGGL(k_prefilter_wave<uint8_t>, dim3(g2), dim3(64), lds_w, st, h->s_codes(), h->s_off(),
-			h->s_emac(), d_qlist, n_list, h->acx_view(), h->K, h->n_clumps, bad, h->n_bad, L->cand.as<uint2>(),
-			(uint32_t *)nullptr, n_cand_dev, (uint32_t)L->cand_cap, &dc->ent_read, h->cur->plan.as<uint32_t>(), fb_dense, n_fb_dense);
-		else hipLaunchKernelGGL(k_prefilter_wave<uint16_t>, dim3(g2), dim3(64), lds_w, st, h->s_codes(), h->s_off(),
-			h->s_emac(), d_qlist, n_list, h->acx_view(), h->K, h->n_clumps, bad, h->n_bad, L->cand.as<uint2>(),
-			(uint32_t *)nullptr, n_cand_dev, (uint32_t)L->cand_cap, &dc->ent_read, h->cur->plan.as<uint32_t>(), fb_dense, n_fb_dense);
-	} else {
-		uint32_t g2 = std::min<uint32_t>(n_list, (uint32_t)h->n_cu * 2);
-		if ((rc = L->gcnt.reserve((size_t)g2 * nw32 * 4))) return rc;
-		hipLaunchKernelGGL(k_prefilter<false>, dim3(g2), dim3(256), 0, st, h->s_codes(), h->s_off(),
-			h->s_emac(), d_qlist, n_list, h->acx_view(), h->K, h->n_clumps,
-			L->gcnt.as<uint32_t>(), bad, h->n_bad, L->cand.as<uint2>(), (uint32_t *)nullptr, n_cand_dev, (uint32_t)L->cand_cap, &dc->ent_read,
-			fb_dense, n_fb_dense, h->cur->plan.as<uint32_t>());
-	}
-	HIPCHK(hipGetLastError());
-	return 0;
+	L->pf_algo_used = c.kind;
+	// dense fallback for the queries that overflowed the last pass (clump-level pairs)
+	return launch_dense_fallback(h, L, st, d_qlist, n_list, h->bad.as<uint32_t>(), h->n_bad, L->cand.as<uint2>(), nullptr, n_cand_dev, (uint32_t)L->cand_cap, dc, fb_dense, n_fb_dense);
 }
 
+// the work buffers of a lane's chain at the lane's present capacities (candidates, tasks, windows, raw hits, re-scorer lists)
+static int lane_reserve_work(Lane *L) {
+	int rc;
+	if ((rc = L->cand.reserve(L->cand_cap * sizeof(uint2))) || (rc = L->raw.reserve(L->raw_cap * sizeof(BhipRawHit))) || (rc = L->wide.reserve(L->raw_cap * sizeof(uint32_t))) ||
+	    (rc = L->rs_lists.reserve(L->raw_cap * sizeof(uint32_t) * 10)) || (rc = L->scratch.reserve(L->scratch_cap * sizeof(uint32_t))) || (rc = L->wins.reserve(L->win_cap * sizeof(BhipWin))) ||
+	    (rc = L->tasks.reserve(L->task_cap * sizeof(uint2))) || (rc = L->tasks2.reserve(L->task_cap * sizeof(uint2))) || (rc = L->tasks2k.reserve(L->task_cap * sizeof(uint2))) ||
+	    (rc = L->wins2.reserve(L->win_cap * sizeof(BhipWin)))) return rc;
+	return 0;
+}
 // Allocate, ahead of the first batch, what batches of up to n_entries entries of up to max_len symbols need (both staging slots,
 // the scratch of the alignment kernels, the record buffers): a batch scheduler calls it once so that no allocation -- each one
 // synchronises the device -- falls into its first batches.
@@ -552,10 +514,7 @@ extern "C" int bhip_reserve_symbols(void *handle, uint32_t n_entries, uint32_t m
 	Lane *L = h->lanes[0];
 	lane_capacity_floor(h, L, n);
 	const int cls = class_of_len(max_len);
-	if ((rc = L->cand.reserve(L->cand_cap * sizeof(uint2))) || (rc = L->raw.reserve(L->raw_cap * sizeof(BhipRawHit))) || (rc = L->wide.reserve(L->raw_cap * sizeof(uint32_t))) ||
-	    (rc = L->rs_lists.reserve(L->raw_cap * sizeof(uint32_t) * 10)) || (rc = L->scratch.reserve(L->scratch_cap * sizeof(uint32_t))) || (rc = L->wins.reserve(L->win_cap * sizeof(BhipWin))) ||
-	    (rc = L->tasks.reserve(L->task_cap * sizeof(uint2))) || (rc = L->tasks2.reserve(L->task_cap * sizeof(uint2))) || (rc = L->tasks2k.reserve(L->task_cap * sizeof(uint2))) ||
-	    (rc = L->wins2.reserve(L->win_cap * sizeof(BhipWin))) || (rc = L->peq.reserve(peq_words * 16 * 4)) || (rc = L->peqp.reserve(n * 16 * 6 * 4)) ||
+	if ((rc = lane_reserve_work(L)) || (rc = L->peq.reserve(peq_words * 16 * 4)) || (rc = L->peqp.reserve(n * 16 * 6 * 4)) ||
 	    (rc = L->peq_alt.reserve(peq_words * 16 * 4)) || (rc = L->peqp_alt.reserve(n * 16 * 6 * 4)) ||
 	    (rc = L->fb_list.reserve(n * 8 + 64)) || (rc = L->ranges_c[cls].reserve(n * 16 * 8 + 16)) || (rc = L->hdr_c[cls].reserve(n * 8 + 16))) return rc;
 	// (BEST on the device: its per-entry keys and the read-back word as well -- nothing is allocated inside the first batch)
@@ -641,16 +600,7 @@ extern "C" int bhip_reserve_symbols(void *handle, uint32_t n_entries, uint32_t m
 // enqueue one lane's whole chain (no host synchronisation).  `start` = event every stream must wait for (buffers reset).
 static int enqueue_lane(Handle *h, Lane *L, int all_hits, hipEvent_t start, uint32_t band_rows, uint32_t qw, uint32_t rw) {
 	int rc;
-	if ((rc = L->cand.reserve(L->cand_cap * sizeof(uint2)))) return rc;
-	if ((rc = L->raw.reserve(L->raw_cap * sizeof(BhipRawHit)))) return rc;
-	if ((rc = L->wide.reserve(L->raw_cap * sizeof(uint32_t)))) return rc;
-	if ((rc = L->rs_lists.reserve(L->raw_cap * sizeof(uint32_t) * 10))) return rc;
-	if ((rc = L->scratch.reserve(L->scratch_cap * sizeof(uint32_t)))) return rc;
-	if ((rc = L->wins.reserve(L->win_cap * sizeof(BhipWin)))) return rc;
-	if ((rc = L->tasks.reserve(L->task_cap * sizeof(uint2)))) return rc;
-	if ((rc = L->tasks2.reserve(L->task_cap * sizeof(uint2)))) return rc;
-	if ((rc = L->tasks2k.reserve(L->task_cap * sizeof(uint2)))) return rc;
-	if ((rc = L->wins2.reserve(L->win_cap * sizeof(BhipWin)))) return rc;
+	if ((rc = lane_reserve_work(L))) return rc;
 	hipStream_t pf = h->pf_stream, sw = h->sweep_stream, po = h->post_stream;
 	HIPCHK(hipMemsetAsync(L->counters.p, 0, sizeof(Counters), pf));
 	Counters *dc = L->counters.as<Counters>();
@@ -683,9 +633,10 @@ static int enqueue_lane(Handle *h, Lane *L, int all_hits, hipEvent_t start, uint
 		const bool masked = NWP && n_pf && h->has_masks && h->opt_lane_masks;
 		// lower-bound pruning (second sweep) only when the minimum per shared slot is all that is wanted, with the counting-filter
 		// kernel (it sees all lane counts of a query at once) and while a list position fits the 24 bits next to the bound
-		const int prune = masked && !all_hits && h->opt_prune && n_list < (1u << 24) && (h->opt_pf_algo >= 0 ? h->opt_pf_algo : L->pf_algo) == 0;
+		const int pf_algo = bhip_pf_algo(h->opt_pf_algo, L->pf_algo);
+		const int prune = masked && !all_hits && h->opt_prune && n_list < (1u << 24) && pf_algo == 0;
 		if (n_pf) {
-			if (masked) { if ((rc = launch_prefilter_mask(h, L, pf, cls, qlist, n_pf, L->maxwords[cls], &dc->n_tasks_cls[cls], &dc->n_cand_cls[cls], dc, prune))) return rc; }
+			if (masked) { if ((rc = launch_prefilter_mask(h, L, pf, cls, qlist, n_pf, L->maxwords[cls], &dc->n_tasks_cls[cls], &dc->n_cand_cls[cls], dc, pf_algo, prune))) return rc; }
 			else if ((rc = launch_prefilter(h, L, pf, qlist, n_pf, L->cand.as<uint2>(), nullptr, (uint32_t)L->cand_cap, true, &dc->n_cand_cls[cls], dc))) return rc;
 		}
 		// (query, length, budget) per list position, written by this batch's k_seed_ranges: what the prefix sweeps of the tasks start from

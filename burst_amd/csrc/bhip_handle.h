@@ -54,9 +54,7 @@ __global__ void k_attach_masks(BhipAcxView, uint64_t, const unsigned long long *
 template <int HTB> __global__ void k_prefilter_mask(const uint2 *, const uint2 *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, uint32_t, const uint32_t *, uint32_t,
 	uint2 *, uint32_t *, uint32_t, unsigned long long *, uint32_t *, uint32_t *, unsigned long long *, unsigned long long *, unsigned long long *,
 	uint2 *, uint32_t *, uint32_t);
-template <int CB, int RBT> __global__ void k_prefilter_cf(const uint2 *, const uint2 *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, uint32_t, const uint32_t *, uint32_t,
-	uint2 *, uint32_t *, uint32_t, unsigned long long *, uint32_t *, uint32_t *, unsigned long long *, unsigned long long *, unsigned long long *, unsigned long long *,
-	uint2 *, uint32_t *, int, const uint32_t *, const uint32_t *, int);
+// (the counting-filter kernels: every instantiation is a bhip_pf_kernel_t, bhip_internal.h; k_prefilter_cf and k_prefilter_cw<0 / 1> come from the test-only library)
 template <int MODE, int BIG> __global__ void k_prefilter_cq(const uint2 *, const uint2 *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, uint32_t, const uint32_t *, uint32_t,
 	uint2 *, uint32_t *, uint32_t, unsigned long long *, uint32_t *, uint32_t *, unsigned long long *, unsigned long long *, unsigned long long *, unsigned long long *,
 	uint2 *, uint32_t *, int, const uint32_t *, const uint32_t *, int);

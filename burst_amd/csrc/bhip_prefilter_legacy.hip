@@ -2,8 +2,9 @@
 // queries per wave, 16 lanes each, 16-bit counters + exact lane table) and k_prefilter_cw<0 / 1> (round 5: one query per wave).  NOT part of
 // libburst_hip.so: built into libburst_hip_legacy.so, which the TESTS load in front of the product library (tests/conftest.py ->
 // burst_amd.capi: RTLD_GLOBAL) so that the options prefilter_cw = 0 / 1 keep running them as independent implementations of the same
-// candidate set (test_tuning_options_do_not_change_results, the fuzzer).  The product library reaches them through two weak symbols
-// (bhip_internal.h: BhipPfLaunch) and refuses those options when the library is not loaded.
+// candidate set (test_tuning_options_do_not_change_results, the fuzzer).  The product library asks for them by selector through one weak symbol
+// (bhip_internal.h: bhip_legacy_pf_kernel), queries and launches the kernel it gets back itself, and refuses those options when the library
+// is not loaded.
 #undef PFM_PROF
 #include "bhip_pf_common.h"
 #include "bhip_prefilter_cw.h"
@@ -471,35 +472,13 @@ BHIP_INST_PFCF(9, 2) BHIP_INST_PFCF(9, 3) BHIP_INST_PFCF(9, 4) BHIP_INST_PFCF(10
 
 BHIP_INST_PFCW(0, 0) BHIP_INST_PFCW(1, 0) BHIP_INST_PFCW(0, 1) BHIP_INST_PFCW(1, 1)
 
-// ---- the two entry points the product library looks for (weak there, defined here) ----
-template <typename F> static int pf_attrs(F fn, size_t *lds, int *regs) {
-	hipFuncAttributes fa;
-	if (hipFuncGetAttributes(&fa, (const void *)fn) != hipSuccess) { (void)hipGetLastError(); return -1; }
-	*lds = fa.sharedSizeBytes; *regs = fa.numRegs;
-	return 0;
-}
-extern "C" __attribute__((visibility("default"))) int bhip_legacy_pf_attrs(int kind, int htb, int rb, int cw_mode, size_t *lds, int *regs) {
-	if (kind == 0) {
-		if (htb == 9) return rb == 2 ? pf_attrs(k_prefilter_cf<9, 2>, lds, regs) : rb == 3 ? pf_attrs(k_prefilter_cf<9, 3>, lds, regs) : pf_attrs(k_prefilter_cf<9, 4>, lds, regs);
-		if (htb == 10) return rb == 2 ? pf_attrs(k_prefilter_cf<10, 2>, lds, regs) : pf_attrs(k_prefilter_cf<10, 4>, lds, regs);
-		return rb == 2 ? pf_attrs(k_prefilter_cf<11, 2>, lds, regs) : pf_attrs(k_prefilter_cf<11, 4>, lds, regs);
+// ---- the entry point the product library looks for (weak there, defined here): the kernel behind a selector, or null ----
+extern "C" __attribute__((visibility("default"))) bhip_pf_kernel_t bhip_legacy_pf_kernel(int kind, int htb, int rb, int cw_mode, int big) {
+	switch (kind == 0 ? htb * 10 + rb : kind == 2 ? cw_mode * 2 + (big ? 1 : 0) : -1) {      // (table bits 9 .. 11 and record blocks 2 .. 4 | slot mode 0 / 1 and BIG)
+		case 92: return k_prefilter_cf<9, 2>; case 93: return k_prefilter_cf<9, 3>; case 94: return k_prefilter_cf<9, 4>;
+		case 102: return k_prefilter_cf<10, 2>; case 104: return k_prefilter_cf<10, 4>;
+		case 112: return k_prefilter_cf<11, 2>; case 114: return k_prefilter_cf<11, 4>;
+		case 0: return k_prefilter_cw<0, 0>; case 1: return k_prefilter_cw<0, 1>; case 2: return k_prefilter_cw<1, 0>; case 3: return k_prefilter_cw<1, 1>;
 	}
-	return cw_mode == 0 ? pf_attrs(k_prefilter_cw<0, 0>, lds, regs) : pf_attrs(k_prefilter_cw<1, 0>, lds, regs);
-}
-extern "C" __attribute__((visibility("default"))) int bhip_legacy_pf_launch(const BhipPfLaunch *a) {
-	hipStream_t st = (hipStream_t)a->stream;
-#define PF_ARGS a->ranges, a->hdr, a->W16, a->n_list, a->ent, a->bad, a->n_bad, a->clump_len, a->tot_refs, a->tasks, a->n_tasks, a->task_cap, a->ent_read, a->fb, a->n_fb, \
-	a->unit_sum, a->col_sum, a->qlen_sum, a->surv_sum, a->tasks2, a->n_tasks2, a->prune, a->sel, a->n_sel, a->bytes
-#define CF(B, R) hipLaunchKernelGGL((k_prefilter_cf<B, R>), dim3(a->grid), dim3(64), 0, st, PF_ARGS)
-#define CW(M, G) hipLaunchKernelGGL((k_prefilter_cw<M, G>), dim3(a->grid), dim3(64), 0, st, PF_ARGS)
-	if (a->kind == 0) {
-		if (a->htb == 9) { if (a->rb == 2) CF(9, 2); else if (a->rb == 3) CF(9, 3); else CF(9, 4); }
-		else if (a->htb == 10) { if (a->rb == 2) CF(10, 2); else CF(10, 4); }
-		else { if (a->rb == 2) CF(11, 2); else CF(11, 4); }
-	} else if (a->cw_mode == 0) { if (a->big) CW(0, 1); else CW(0, 0); }
-	else { if (a->big) CW(1, 1); else CW(1, 0); }
-#undef CF
-#undef CW
-#undef PF_ARGS
-	return (int)hipGetLastError();
+	return nullptr;
 }

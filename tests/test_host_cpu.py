@@ -443,3 +443,81 @@ def test_accelerator_window_walk_eight_symbols_at_a_time(tmp_path):
     for seed in (5, 11):
         r = subprocess.run([exe, "12000", str(seed)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
         assert r.returncode == 0 and " 0 mismatches" in r.stdout, r.stdout[-2000:]
+
+
+def test_prefilter_variant_table_keeps_the_rules_it_was_made_from(tmp_path):
+    """burst_amd/csrc/bhip_pf_select.h on the host: which lane-resolved prefilter kernel a (lane, class) list runs, and whether the seed
+    lookups leave out a query's longest list.  The expected rows are worked out by hand from the rules the launch code had spelled out in
+    place before the table existed: table bits 9 / 10 / 11 at <= 600 / <= 1200 expected records for the counting filter and <= 230 / <= 470
+    for the exact table (option prefilter_table overrides); record blocks 2 / 3 / 4 at <= 110 / <= 230 (prefilter_rb overrides), 3 becoming 4
+    unless the table is 2^9; slot mode 0 / 1 / 2 for rows of <= 8 / <= 16 / more words; k_prefilter_cq only for prefilter_cw = 2 below slot
+    mode 2; superseded (test-only library) = counting filter that is neither k_prefilter_cq nor k_prefilter_cw<2>; a second pass unless the
+    first one already ran k_prefilter_cf with the largest table."""
+    exe = str(tmp_path / "pf_select_host")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "burst_amd", "csrc"), os.path.join(ROOT, "tests", "csrc", "pf_select_host.cpp"), "-o", exe])
+
+    def ask(lines):
+        r = subprocess.run([exe], input="".join(l + "\n" for l in lines), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=60)
+        assert r.returncode == 0, r.stderr
+        out = r.stdout.split("\n")[:-1]
+        assert len(out) == len(lines)
+        return out
+
+    CF, MASK, CW, CQ = 0, 1, 2, 3          # BhipStats.prefilter_algo
+    ANY = (50.0, 5000.0)
+    # (algo, prefilter_cw, prefilter_table, prefilter_rb, W16, expected records per query) -> fields of the choice that matter for the kernel
+    rows = []
+    for e in ANY:
+        rows += [((0, 2, 0, 0, 8, e), dict(kind=CQ, cw_mode=0, legacy=0, two_pass=1)),        # k_prefilter_cq<0>
+                 ((0, 2, 0, 0, 16, e), dict(kind=CQ, cw_mode=1, legacy=0, two_pass=1)),       # k_prefilter_cq<1>
+                 ((0, 2, 0, 0, 32, e), dict(kind=CW, cw_mode=2, legacy=0, two_pass=1)),       # beyond 16 lists: k_prefilter_cw<2>, in the product
+                 ((0, 1, 0, 0, 8, e), dict(kind=CW, cw_mode=0, legacy=1, two_pass=1)),        # k_prefilter_cw<0>
+                 ((0, 1, 0, 0, 16, e), dict(kind=CW, cw_mode=1, legacy=1, two_pass=1)),       # k_prefilter_cw<1>
+                 ((0, 1, 0, 0, 32, e), dict(kind=CW, cw_mode=2, legacy=0, two_pass=1)),       # k_prefilter_cw<2> again: not superseded
+                 ((0, 0, 11, 3, 8, e), dict(kind=CF, htb=11, rb=4, legacy=1, two_pass=0)),    # 3 blocks only with the 2^9 table
+                 ((0, 0, 9, 3, 8, e), dict(kind=CF, htb=9, rb=3, legacy=1, two_pass=1))]
+    rows += [((0, 0, 0, 0, 8, 100.0), dict(kind=CF, htb=9, rb=2, legacy=1, two_pass=1)),      # 100 <= 110: 2 blocks; <= 600: 2^9
+             ((0, 0, 0, 0, 8, 200.0), dict(kind=CF, htb=9, rb=3, legacy=1, two_pass=1)),      # 110 < 200 <= 230: 3 blocks
+             ((0, 0, 0, 0, 8, 500.0), dict(kind=CF, htb=9, rb=4, legacy=1, two_pass=1)),      # > 230: 4 blocks
+             ((0, 0, 0, 0, 8, 700.0), dict(kind=CF, htb=10, rb=4, legacy=1, two_pass=1)),     # 600 < 700 <= 1200: 2^10
+             ((0, 0, 0, 0, 8, 1500.0), dict(kind=CF, htb=11, rb=4, legacy=1, two_pass=0)),    # > 1200: 2^11, the largest already
+             ((0, 0, 10, 0, 8, 200.0), dict(kind=CF, htb=10, rb=4, legacy=1, two_pass=1)),    # 3 blocks by the stream, 4 because the table is not 2^9
+             ((0, 0, 0, 2, 8, 1500.0), dict(kind=CF, htb=11, rb=2, legacy=1, two_pass=0)),
+             # the thresholds themselves are "<="
+             ((0, 0, 0, 0, 8, 110.0), dict(kind=CF, htb=9, rb=2)), ((0, 0, 0, 0, 8, 110.5), dict(kind=CF, htb=9, rb=3)),
+             ((0, 0, 0, 0, 8, 230.0), dict(kind=CF, htb=9, rb=3)), ((0, 0, 0, 0, 8, 230.5), dict(kind=CF, htb=9, rb=4)),
+             ((0, 0, 0, 0, 8, 600.0), dict(kind=CF, htb=9, rb=4, two_pass=1)), ((0, 0, 0, 0, 8, 600.5), dict(kind=CF, htb=10, rb=4, two_pass=1)),
+             ((0, 0, 0, 0, 8, 1200.0), dict(kind=CF, htb=10, rb=4, two_pass=1)), ((0, 0, 0, 0, 8, 1200.5), dict(kind=CF, htb=11, rb=4, two_pass=0))]
+    for cw in (0, 1, 2):                   # the exact table: whatever prefilter_cw and the row width say
+        for w16 in (8, 16, 32):
+            rows += [((1, cw, 0, 0, w16, 200.0), dict(kind=MASK, htb=9, legacy=0)), ((1, cw, 0, 0, w16, 300.0), dict(kind=MASK, htb=10, legacy=0)),
+                     ((1, cw, 0, 0, w16, 500.0), dict(kind=MASK, htb=11, legacy=0)),
+                     ((1, cw, 0, 0, w16, 230.0), dict(kind=MASK, htb=9)), ((1, cw, 0, 0, w16, 230.5), dict(kind=MASK, htb=10)),
+                     ((1, cw, 0, 0, w16, 470.0), dict(kind=MASK, htb=10)), ((1, cw, 0, 0, w16, 470.5), dict(kind=MASK, htb=11)),
+                     ((1, cw, 9, 0, w16, 5000.0), dict(kind=MASK, htb=9, legacy=0))]
+    got = ask(["choose %d %d %d %d %d %r" % k for k, _ in rows])
+    for (k, want), line in zip(rows, got):
+        f = dict(zip(("kind", "htb", "rb", "cw_mode", "legacy", "two_pass"), map(int, line.split())))
+        assert {n: f[n] for n in want} == want, (k, want, f)
+
+    # the rule for leaving out a query's longest list: 3 when the stream is at least 100 records and, without its longest list (x 0.93), loads
+    # the counters of the kernel the options name to at most 0.35; else 0
+    # (seed_min_need, prefilter_cw, prefilter_table, prefilter_bytes, acx_wmean, mean_words, W16) -> need
+    W = 61.5
+    needs = [((0, 2, 0, 1, W, 4.0, 8), 0), ((2, 2, 0, 1, W, 8.0, 8), 2), ((5, 0, 0, 0, W, 1.0, 8), 5),      # an explicit value wins
+             # 4 words: t_all = 4 x 61.5 = 246, t_less = 246 x 3/4 x 0.93 = 171.585
+             ((-1, 1, 0, 1, W, 4.0, 8), 3), ((-1, 2, 0, 1, W, 4.0, 8), 3),     # 1 024 byte slots: 171.585 / 1024 = 0.168
+             ((-1, 1, 0, 1, W, 4.0, 16), 3), ((-1, 2, 0, 1, W, 4.0, 16), 3),   # 512 halfword slots: 171.585 / 512 = 0.335
+             ((-1, 0, 0, 1, W, 4.0, 8), 3),                                    # k_prefilter_cf: 246 <= 600 -> 2^9, x 2 as bytes (171.585 <= 200): 0.168
+             ((-1, 0, 0, 0, W, 4.0, 8), 3),                                    # ... 16-bit counters: 171.585 / 512 = 0.335
+             # 8 words: t_all = 492, t_less = 492 x 7/8 x 0.93 = 400.365
+             ((-1, 1, 0, 1, W, 8.0, 8), 0), ((-1, 2, 0, 1, W, 8.0, 8), 0),     # 400.365 / 1024 = 0.391 > 0.35
+             ((-1, 2, 0, 1, W, 8.0, 16), 0),                                   # 400.365 / 512 = 0.782
+             ((-1, 0, 0, 1, W, 8.0, 8), 0),                                    # 2^9 (492 <= 600), no bytes (400.365 > 200): 0.782
+             ((-1, 0, 11, 1, W, 8.0, 8), 3),                                   # prefilter_table = 11: 400.365 / 2048 = 0.195
+             # streams below 100 records: never
+             ((-1, 2, 0, 1, W, 1.0, 8), 0),                                    # t_all = 61.5
+             ((-1, 2, 0, 1, W, 1.6, 8), 0), ((-1, 0, 0, 1, W, 1.6, 8), 0),     # t_all = 98.4
+             ((-1, 2, 0, 1, 25.0, 4.0, 8), 3)]                                 # t_all = 100 counts as long enough: 100 x 3/4 x 0.93 = 69.75, / 1024 = 0.068
+    got = ask(["need %d %d %d %d %r %r %d" % k for k, _ in needs])
+    assert [int(x) for x in got] == [w for _, w in needs], [(k, w, int(g)) for (k, w), g in zip(needs, got) if int(g) != w]
