@@ -148,37 +148,64 @@ extern "C" int bhip_set_ref_order(void *handle, const uint32_t *order, uint32_t 
 }
 
 // ---- kernel launch helpers (st = stream to launch on) ---------------------------------------------------------------
+// A run-time word count as a template argument.  dispatch_int: f(std::integral_constant<int, N>) for the N of the list that equals v, for
+// the last N of the list when none does (the widest kernel takes the rest); for_each_int: f for every N, in list order.  One list per
+// template parameter: exactly the instances bhip_kernels.hip and bhip_prefilter.hip define.
+template <int... Ns> struct IntList {};
+using NwList = IntList<2, 4, 6, 8, 10, 16, 32>;      // k_myers<NW>, k_myers_window<NW>: words of the query vector
+using NwpList = IntList<1, 2, 3, 4, 6>;              // k_myers_prefix<NWP>, k_myers_prefix_task<NWP>: words of the prefix
+using BwList = IntList<2, 3, 4>;                     // k_myers_window_band<BW>: words of the band
+using HtbList = IntList<9, 10, 11>;                  // k_prefilter_mask<HTB>: log2 of the hash table
+// k_rescore_reg<SET>, in launch order.  3 = 12 diagonals: a kernel of its own, so that the 4 / 6 / 8 variants run at 80 registers (6 waves per
+// SIMD instead of 4); 2 = 32 / 40 / 48 diagonals (usually empty lists: large budgets, or repeats that stretch the end-column range)
+using SetList = IntList<0, 3, 1, 2>;
+template <int N, class F> static void dispatch_int(IntList<N>, int, F &&f) { f(std::integral_constant<int, N>{}); }
+template <int N, int M, int... Ns, class F> static void dispatch_int(IntList<N, M, Ns...>, int v, F &&f) {
+	if (v == N) f(std::integral_constant<int, N>{}); else dispatch_int(IntList<M, Ns...>{}, v, f);
+}
+template <int... Ns, class F> static void for_each_int(IntList<Ns...>, F &&f) { (f(std::integral_constant<int, Ns>{}), ...); }
+
+// argument groups many launches share: shared-slot numbers and strand flags of the current batch (null: it has none), the reference arrays
+static const uint32_t *six_or_null(const Handle *h) { return h->cur->st_has_six ? h->cur->qsix.as<uint32_t>() : nullptr; }
+static const uint8_t *rc_or_null(const Handle *h) { return h->cur->st_has_rc ? h->cur->qrc.as<uint8_t>() : nullptr; }
+struct RefArgs {
+	const void *lanes; const uint64_t *off; const uint32_t *len;      // ref_lane, ref_off, clump_len
+	const uint4 *chunks() const { return (const uint4 *)lanes; }      // as the sweeps read them: 16-byte chunks of 32 columns
+	const uint8_t *bytes() const { return (const uint8_t *)lanes; }   // as the re-scorers do
+};
+static RefArgs ref_args(const Handle *h) { return {h->ref_lane.p, h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>()}; }
+
 static void launch_myers(Handle *h, Lane *L, hipStream_t st, int NW, uint32_t grid, const uint2 *pairs, const uint32_t *n_pairs_dev,
 		uint64_t n_pairs_host, uint32_t li_base, const uint32_t *qlist, BhipRawHit *raw, uint32_t *n_raw, uint32_t raw_cap, uint32_t *best,
 		uint8_t *mins, Counters *dc) {
+	const RefArgs R = ref_args(h);
+	const uint32_t *six = best ? six_or_null(h) : nullptr;
 	if (NW > 32) {      // queries beyond 1 024 symbols: the vector lives in LDS (2 x NW words per thread, one wave per block)
 		hipLaunchKernelGGL(k_myers_long, dim3(grid * 4u), dim3(64), (size_t)NW * 512u, st, pairs, n_pairs_dev, n_pairs_host, h->n_clumps, li_base, qlist,
-			L->peq.as<uint32_t>(), h->s_off(), h->s_emac(), (best && h->cur->st_has_six) ? h->cur->qsix.as<uint32_t>() : nullptr,
-			h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), h->tot_refs, raw, n_raw, raw_cap, best, mins, &dc->col_sum, &dc->qlen_sum, (uint32_t)NW);
+			L->peq.as<uint32_t>(), h->s_off(), h->s_emac(), six, R.chunks(), R.off, R.len, h->tot_refs, raw, n_raw, raw_cap, best, mins, &dc->col_sum, &dc->qlen_sum, (uint32_t)NW);
 		return;
 	}
-	#define LM(N) hipLaunchKernelGGL(k_myers<N>, dim3(grid), dim3(256), 0, st, pairs, n_pairs_dev, n_pairs_host, h->n_clumps, li_base, qlist, \
-		L->peq.as<uint32_t>(), h->s_off(), h->s_emac(), (best && h->cur->st_has_six) ? h->cur->qsix.as<uint32_t>() : nullptr, \
-		h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), h->tot_refs, raw, n_raw, raw_cap, best, mins, &dc->col_sum, &dc->qlen_sum)
-	switch (NW) { case 2: LM(2); break; case 4: LM(4); break; case 6: LM(6); break; case 8: LM(8); break; case 10: LM(10); break;
-		case 16: LM(16); break; default: LM(32); break; }
-	#undef LM
+	dispatch_int(NwList{}, NW, [&](auto nw) {
+		hipLaunchKernelGGL(k_myers<decltype(nw)::value>, dim3(grid), dim3(256), 0, st, pairs, n_pairs_dev, n_pairs_host, h->n_clumps, li_base, qlist,
+			L->peq.as<uint32_t>(), h->s_off(), h->s_emac(), six, R.chunks(), R.off, R.len, h->tot_refs, raw, n_raw, raw_cap, best, mins, &dc->col_sum, &dc->qlen_sum);
+	});
 }
 static void launch_prefix(Handle *h, Lane *L, hipStream_t st, int NWP, uint32_t grid, const uint2 *pairs, const uint32_t *n_pairs_dev,
 		uint64_t n_pairs_host, uint32_t li_base, const uint32_t *qlist, uint32_t *n_wins, Counters *dc) {
-	#define LP(N) hipLaunchKernelGGL(k_myers_prefix<N>, dim3(grid), dim3(256), 0, st, pairs, n_pairs_dev, n_pairs_host, h->n_clumps, li_base, qlist, \
-		L->peqp.as<uint32_t>(), h->s_off(), h->s_emac(), h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), \
-		h->tot_refs, L->wins.as<BhipWin>(), n_wins, (uint32_t)L->win_cap, &dc->col_sum, &dc->qlen_sum, dc->win_class_seen, h->cur->st_has_six ? h->cur->qsix.as<uint32_t>() : nullptr)
-	if (NWP == 1) LP(1); else if (NWP == 2) LP(2); else if (NWP == 3) LP(3); else if (NWP == 4) LP(4); else LP(6);
-	#undef LP
+	const RefArgs R = ref_args(h);
+	dispatch_int(NwpList{}, NWP, [&](auto nwp) {
+		hipLaunchKernelGGL(k_myers_prefix<decltype(nwp)::value>, dim3(grid), dim3(256), 0, st, pairs, n_pairs_dev, n_pairs_host, h->n_clumps, li_base, qlist,
+			L->peqp.as<uint32_t>(), h->s_off(), h->s_emac(), R.chunks(), R.off, R.len, h->tot_refs, L->wins.as<BhipWin>(), n_wins, (uint32_t)L->win_cap,
+			&dc->col_sum, &dc->qlen_sum, dc->win_class_seen, six_or_null(h));
+	});
 }
 static void launch_prefix_task(Handle *h, Lane *L, hipStream_t st, int NWP, uint32_t grid, const uint2 *tasks, const uint32_t *n_tasks_dev, const uint32_t *qlist,
 		BhipWin *wins, uint32_t *n_wins, Counters *dc, const uint4 *qmeta) {
-	#define LT(N) hipLaunchKernelGGL(k_myers_prefix_task<N>, dim3(grid), dim3(64), 0, st, tasks, n_tasks_dev, (uint32_t)L->task_cap, qlist, \
-		L->peqp.as<uint32_t>(), h->s_off(), h->s_emac(), h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), \
-		wins, n_wins, (uint32_t)L->win_cap, &dc->tcol_sum, dc->win_class_seen, qmeta, h->cur->st_has_six ? h->cur->qsix.as<uint32_t>() : nullptr)
-	if (NWP == 1) LT(1); else if (NWP == 2) LT(2); else if (NWP == 3) LT(3); else if (NWP == 4) LT(4); else LT(6);
-	#undef LT
+	const RefArgs R = ref_args(h);
+	dispatch_int(NwpList{}, NWP, [&](auto nwp) {
+		hipLaunchKernelGGL(k_myers_prefix_task<decltype(nwp)::value>, dim3(grid), dim3(64), 0, st, tasks, n_tasks_dev, (uint32_t)L->task_cap, qlist,
+			L->peqp.as<uint32_t>(), h->s_off(), h->s_emac(), R.chunks(), R.off, R.len, wins, n_wins, (uint32_t)L->win_cap, &dc->tcol_sum, dc->win_class_seen, qmeta, six_or_null(h));
+	});
 }
 // Resident blocks per CU of a kernel from its static register / LDS use (512 VGPRs per SIMD lane granted in steps of 8, at
 // most 8 waves per SIMD; about 148 KB of the 160 KB of LDS -- measured on gfx950: 11 single-wave blocks of 13 144 B fit a CU and 12 do
@@ -196,30 +223,28 @@ static uint32_t blocks_per_cu(const void *fn, uint32_t threads, size_t dyn_lds, 
 }
 
 static void launch_window(Handle *h, Lane *L, hipStream_t wst, int cls, int NWP, uint32_t grid_cap, const BhipWin *wins, const uint32_t *n_wins, Counters *dc) {
-	const uint32_t *six = h->cur->st_has_six ? h->cur->qsix.as<uint32_t>() : nullptr;
+	const uint32_t *six = six_or_null(h);
+	const uint4 *ref = ref_args(h).chunks();
 	const int NWc = kClasses[cls];
-	// queries of three words and more: the windows whose flagged diagonals fit the two-word band go to k_myers_window_band, the
-	// full-column kernel takes the rest (flag BHIP_WIN_WIDE, set by the prefix kernels)
 	// the windows whose flagged diagonals fit a band of 2, 3 or 4 words (class 0 .. 2 in the record, set by the prefix kernels) go to
 	// k_myers_window_band<2 .. 4> where the query has more words than that; the full-column kernel takes the rest
 	const int min_class = h->opt_no_band ? 0 : NWc >= 8 ? 3 : NWc >= 6 ? 2 : NWc >= 4 ? 1 : 0;
-	#define LB(BW) { uint32_t per_cu = blocks_per_cu((const void *)k_myers_window_band<BW>, 64u, 0); \
-		if (h->opt_band_blocks > 0) per_cu = (uint32_t)h->opt_band_blocks; \
-		const uint32_t grid = (uint32_t)h->n_cu * per_cu * (uint32_t)h->opt_oversub; \
-		hipLaunchKernelGGL(k_myers_window_band<BW>, dim3(grid), dim3(64), 0, wst, wins, n_wins, (uint32_t)L->win_cap, NWP, NWc, L->peq.as<uint32_t>(), six, \
-			h->ref_lane.as<uint4>(), L->raw.as<BhipRawHit>(), &dc->n_raw, (uint32_t)L->raw_cap, h->best.as<uint32_t>(), &dc->wcol_sum, dc->win_class_seen); }
-	if (min_class >= 1) LB(2);
-	if (min_class >= 2) LB(3);
-	if (min_class >= 3) LB(4);
-	#undef LB
-	#define LW(N) { const uint32_t thr = (N) <= 8 ? 64u : 256u;      /* NW <= 8: per-thread A/C/G/T profile rows in LDS, 64-thread blocks */ \
-		const uint32_t grid = std::min<uint32_t>(grid_cap * (256u / thr), (uint32_t)h->n_cu * blocks_per_cu((const void *)k_myers_window<N>, thr, 0)); \
-		hipLaunchKernelGGL(k_myers_window<N>, dim3(grid), dim3(thr), 0, wst, wins, n_wins, (uint32_t)L->win_cap, NWP, min_class, \
-		L->peq.as<uint32_t>(), six, h->ref_lane.as<uint4>(), \
-		L->raw.as<BhipRawHit>(), &dc->n_raw, (uint32_t)L->raw_cap, h->best.as<uint32_t>(), &dc->wcol_sum, dc->win_class_seen); }
-	switch (NWc) { case 2: LW(2); break; case 4: LW(4); break; case 6: LW(6); break; case 8: LW(8); break; case 10: LW(10); break;
-		case 16: LW(16); break; default: LW(32); break; }
-	#undef LW
+	for_each_int(BwList{}, [&](auto bw) {
+		constexpr int BW = decltype(bw)::value;
+		if (min_class < BW - 1) return;
+		uint32_t per_cu = blocks_per_cu((const void *)k_myers_window_band<BW>, 64u, 0);
+		if (h->opt_band_blocks > 0) per_cu = (uint32_t)h->opt_band_blocks;
+		const uint32_t grid = (uint32_t)h->n_cu * per_cu * (uint32_t)h->opt_oversub;
+		hipLaunchKernelGGL(k_myers_window_band<BW>, dim3(grid), dim3(64), 0, wst, wins, n_wins, (uint32_t)L->win_cap, NWP, NWc, L->peq.as<uint32_t>(), six,
+			ref, L->raw.as<BhipRawHit>(), &dc->n_raw, (uint32_t)L->raw_cap, h->best.as<uint32_t>(), &dc->wcol_sum, dc->win_class_seen);
+	});
+	dispatch_int(NwList{}, NWc, [&](auto nw) {
+		constexpr int N = decltype(nw)::value;
+		const uint32_t thr = N <= 8 ? 64u : 256u;      // NW <= 8: per-thread A/C/G/T profile rows in LDS, 64-thread blocks
+		const uint32_t grid = std::min<uint32_t>(grid_cap * (256u / thr), (uint32_t)h->n_cu * blocks_per_cu((const void *)k_myers_window<N>, thr, 0));
+		hipLaunchKernelGGL(k_myers_window<N>, dim3(grid), dim3(thr), 0, wst, wins, n_wins, (uint32_t)L->win_cap, NWP, min_class, L->peq.as<uint32_t>(), six,
+			ref, L->raw.as<BhipRawHit>(), &dc->n_raw, (uint32_t)L->raw_cap, h->best.as<uint32_t>(), &dc->wcol_sum, dc->win_class_seen);
+	});
 }
 
 
@@ -246,10 +271,9 @@ static int upload_queries(Handle *h, const uint8_t *q_codes, const uint64_t *q_o
 	return 0;
 }
 
-static int upload_plan(Handle *h, const uint8_t *q_codes, const uint64_t *q_off, const uint16_t *q_emac, uint32_t n_q, std::vector<uint32_t> &plan) {
+static int upload_plan(Handle *h, uint32_t n_q, std::vector<uint32_t> &plan) {
 	int rc;
 	if ((rc = h->cur->plan.reserve((size_t)n_q * 4 + 16))) return rc;
-	(void)q_codes; (void)q_off; (void)q_emac;
 	HIPCHK(hipMemcpyAsync(h->cur->plan.p, plan.data(), (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
 	HIPCHK(hipStreamSynchronize(h->stream));
 	return 0;
@@ -380,7 +404,7 @@ static int launch_seed(Handle *h, Lane *L, hipStream_t st, StageSlot *S, int cls
 	const uint64_t n_thr = (uint64_t)n_list * W16;
 	hipEvent_t *ev = L->ev_seed[S->seq & 1][cls];
 	const bool junk = S->st_has_junk;
-	HIPCHK(hipEventRecord(ev[0], st));
+	HIPCHK(hipEventRecord(ev[SPAN_START], st));
 	// ahead of its batch the kernel shares the device with the sweeps of the batch before: a few blocks per CU leave them their
 	// wave slots (option "seed_ahead_blocks"), and it still ends long before it is needed
 	const uint64_t full = (n_thr + 255) / 256;
@@ -391,7 +415,7 @@ static int launch_seed(Handle *h, Lane *L, hipStream_t st, StageSlot *S, int cls
 		junk ? S->qpack_s.as<uint32_t>() : S->qpack.as<uint32_t>(), (S->st_maxlen + 7) / 8, junk ? S->qemac_s.as<uint16_t>() : S->qemac.as<uint16_t>(), qm.as<uint4>(), S->st_has_six ? S->qsix.as<uint32_t>() : nullptr,
 		seed_min_need_for(h, mean_words, W16), (uint32_t)h->opt_seed_drop_len, h->alt);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(ev[1], st));
+	HIPCHK(hipEventRecord(ev[SPAN_DONE], st));
 	L->qmeta_seq[S->seq & 1][cls] = S->seq + 1;
 	L->seeded_ok[cls] = true; L->seeded_seq[cls] = S->seq; L->seeded_n[cls] = n_list; L->seeded_W16[cls] = W16;
 	return 0;
@@ -434,7 +458,7 @@ static int launch_prefilter_mask(Handle *h, Lane *L, hipStream_t st, int cls, co
 	}
 	const uint32_t waves = h->opt_pf_waves ? std::min<uint32_t>((uint32_t)h->opt_pf_waves, fit) : fit;
 	const uint32_t grid = std::min<uint32_t>(c.kind == BHIP_PF_CW ? n_list : (n_list + 3) / 4, (uint32_t)h->n_cu * waves);
-	HIPCHK(hipEventRecord(L->ev_pf[cls][1], st));
+	HIPCHK(hipEventRecord(L->ev_pf[cls][PF_HASH_START], st));
 	const uint32_t *fb_dense = ov.fb1, *n_fb_dense = ov.n_fb1;
 	if (filter) {
 		auto launch = [&](bhip_pf_kernel_t k, uint32_t g, uint32_t *fb, uint32_t *n_fb, const uint32_t *sel, const uint32_t *n_sel) {
@@ -456,15 +480,15 @@ static int launch_prefilter_mask(Handle *h, Lane *L, hipStream_t st, int cls, co
 			fb_dense = ov.fb2; n_fb_dense = ov.n_fb2;
 		}
 	} else {
-#define PFM_LAUNCH(B) hipLaunchKernelGGL(k_prefilter_mask<B>, dim3(grid), dim3(64), 0, st, L->ranges_c[cls].as<uint2>(), L->hdr_c[cls].as<uint2>(), W16, n_list, \
-		h->acx_view().rec, h->bad.as<uint32_t>(), h->n_bad, \
-		h->clump_len.as<uint32_t>(), h->tot_refs, L->tasks.as<uint2>(), n_tasks_dev, (uint32_t)L->task_cap, &dc->ent_read, \
-		ov.fb1, ov.n_fb1, &dc->unit_sum, &dc->col_sum, &dc->qlen_sum, L->cand.as<uint2>(), n_cand_dev, (uint32_t)L->cand_cap)
-		if (c.htb == 9) PFM_LAUNCH(9); else if (c.htb == 10) PFM_LAUNCH(10); else PFM_LAUNCH(11);
-#undef PFM_LAUNCH
+		dispatch_int(HtbList{}, c.htb, [&](auto htb) {
+			hipLaunchKernelGGL(k_prefilter_mask<decltype(htb)::value>, dim3(grid), dim3(64), 0, st, L->ranges_c[cls].as<uint2>(), L->hdr_c[cls].as<uint2>(), W16, n_list,
+				h->acx_view().rec, h->bad.as<uint32_t>(), h->n_bad,
+				h->clump_len.as<uint32_t>(), h->tot_refs, L->tasks.as<uint2>(), n_tasks_dev, (uint32_t)L->task_cap, &dc->ent_read,
+				ov.fb1, ov.n_fb1, &dc->unit_sum, &dc->col_sum, &dc->qlen_sum, L->cand.as<uint2>(), n_cand_dev, (uint32_t)L->cand_cap);
+		});
 	}
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(L->ev_pf[cls][2], st));
+	HIPCHK(hipEventRecord(L->ev_pf[cls][PF_HASH_DONE], st));
 	++L->pf_launches;
 	L->pf_algo_used = c.kind;
 	// dense fallback for the queries that overflowed the last pass (clump-level pairs)
@@ -597,99 +621,121 @@ extern "C" int bhip_reserve_symbols(void *handle, uint32_t n_entries, uint32_t m
 	}
 	return BHIP_OK;
 }
-// enqueue one lane's whole chain (no host synchronisation).  `start` = event every stream must wait for (buffers reset).
-static int enqueue_lane(Handle *h, Lane *L, int all_hits, hipEvent_t start, uint32_t band_rows, uint32_t qw, uint32_t rw) {
+// ---- one batch call (bhip_align_staged) ------------------------------------------------------------------------------
+// What the steps of a call share.  A step returns BHIP_OK, an error (< 0) or STEP_REDO: a buffer was too small for what the chain
+// produced, it has grown, the chain is enqueued again.
+enum { STEP_REDO = 1 };
+struct BatchCall {
+	StageSlot *slot = nullptr;
+	int mode = 0;                        // all_hits as the caller gave it (BHIP_HITS_*)
+	int all_hits = 0;                    // what the kernels are told: every hit within budget, or the minimum per shared slot
+	bool sel_best = false;               // ... and of those one record per entry, chosen on the device
+	BhipHit *hits = nullptr; uint64_t cap = 0; uint64_t *n_hits = nullptr;      // the caller's buffer
+	uint32_t n_q = 0, n_shared = 0, nl = 0;
+	uint32_t band_rows = 0, qw = 0, rw = 0;      // LDS plan of the re-scorer: band rows, query and reference staging (dwords per thread)
+	SharedCtr hsc = {};                  // the shared counters behind the last re-scorer
+	uint32_t n_deliver = 0;              // records the caller gets: all of them, or one per entry (sel_best)
+	bool sorted_ahead = false; int o_ahead = 0;      // the records were grouped behind the re-scorer, into out_sorted (0) or out_sorted2 (1)
+	size_t tmp_bytes = 0;                // scratch of the scan over the per-entry counters
+	std::chrono::steady_clock::time_point t0; double t_host[4] = {0, 0, 0, 0};      // delivery, host side (BHIP_DEBUG_TIMES)
+	void mark(int i) { t_host[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// Enqueue one length class of a lane (no host synchronisation): match profiles on the sweep stream, the prefilter on its own, the sweeps of the
+// prefiltered and of the exhaustive queries behind it, the window stage on the post stream and -- with pruning -- the second sweep.
+static int enqueue_class(Handle *h, Lane *L, int cls, int all_hits) {
 	int rc;
-	if ((rc = lane_reserve_work(L))) return rc;
 	hipStream_t pf = h->pf_stream, sw = h->sweep_stream, po = h->post_stream;
-	HIPCHK(hipMemsetAsync(L->counters.p, 0, sizeof(Counters), pf));
+	Counters *dc = L->counters.as<Counters>();
+	const uint32_t n_pf = L->npf[cls], n_ex = L->nex[cls], n_list = n_pf + n_ex;
+	const uint32_t grid_my = (uint32_t)h->n_cu * (uint32_t)h->opt_sweep_blocks;   // < 8 leaves wave slots for the other stages' kernels
+	const uint32_t grid_task = (uint32_t)h->n_cu * 4u * (uint32_t)h->opt_sweep_blocks * (uint32_t)h->opt_oversub;      // 64-thread blocks of the task sweeps
+	const int NW = class_words(cls, L->maxlen);
+	const uint32_t *qlist = L->qlist[cls];
+	hipEvent_t *ce = L->ev_cls[cls];
+	// the lane's peq buffers are reused class after class: do not rebuild them before the previous class's window stage is done
+	// (the profiles are built on the sweep stream, which is idle while this class's seeds and prefilter run on theirs)
+	if (L->launches) { HIPCHK(hipStreamWaitEvent(pf, L->ev_rs[RS_START], 0)); HIPCHK(hipStreamWaitEvent(sw, L->ev_rs[RS_START], 0)); }
+	const int NWP = class_prefix_words(h, L->maxE[cls], NW);   // two-stage edit distance when a prefix of 32*NWP symbols is selective for this class's budgets
+	HIPCHK(hipEventRecord(ce[CE_START], sw));
+	L->peq_ahead[cls] = false;
+	if (L->alt_ok && L->alt_seq == h->cur->seq && L->alt_cls == cls && L->alt_n == n_list && L->alt_nwp == NWP && !L->launches) {
+		// built ahead during the previous batch (seed_next_batch): that batch is through, its profiles are not needed any more
+		std::swap(L->peq, L->peq_alt); std::swap(L->peqp, L->peqp_alt);
+		std::swap(L->ev_peq_cur[SPAN_START], L->ev_peq_alt[SPAN_START]); std::swap(L->ev_peq_cur[SPAN_DONE], L->ev_peq_alt[SPAN_DONE]);
+		L->alt_ok = false; L->peq_ahead[cls] = true;
+	} else if ((rc = launch_peq(h, sw, h->cur, qlist, n_list, NW, NWP, L->peq, L->peqp))) return rc;
+	L->prefix_words = (uint32_t)NWP;
+	HIPCHK(hipEventRecord(ce[CE_PEQ_DONE], sw));
+	HIPCHK(hipEventRecord(ce[CE_PF_START], pf));
+	const bool masked = NWP && n_pf && h->has_masks && h->opt_lane_masks;
+	// lower-bound pruning (second sweep) only when the minimum per shared slot is all that is wanted, with the counting-filter
+	// kernel (it sees all lane counts of a query at once) and while a list position fits the 24 bits next to the bound
+	const int pf_algo = bhip_pf_algo(h->opt_pf_algo, L->pf_algo);
+	const int prune = masked && !all_hits && h->opt_prune && n_list < (1u << 24) && pf_algo == 0;
+	if (n_pf) {
+		if (masked) { if ((rc = launch_prefilter_mask(h, L, pf, cls, qlist, n_pf, L->maxwords[cls], &dc->n_tasks_cls[cls], &dc->n_cand_cls[cls], dc, pf_algo, prune))) return rc; }
+		else if ((rc = launch_prefilter(h, L, pf, qlist, n_pf, L->cand.as<uint2>(), nullptr, (uint32_t)L->cand_cap, true, &dc->n_cand_cls[cls], dc))) return rc;
+	}
+	// (query, length, budget) per list position, written by this batch's k_seed_ranges: what the prefix sweeps of the tasks start from
+	const uint4 *qmeta_cls = (masked && L->qmeta_seq[h->cur->seq & 1][cls] == h->cur->seq + 1) ? L->qmeta_c[h->cur->seq & 1][cls].as<uint4>() : nullptr;
+	L->masked = masked;
+	L->pf_masked[cls] = masked && n_pf;
+	HIPCHK(hipEventRecord(ce[CE_PF_DONE], pf));
+	// column sweep on the sweep stream, behind this lane's prefilter
+	HIPCHK(hipStreamWaitEvent(sw, ce[CE_PF_DONE], 0));
+	HIPCHK(hipEventRecord(ce[CE_SWEEP_START], sw));
+	if (n_pf) {
+		if (masked) launch_prefix_task(h, L, sw, NWP, grid_task, L->tasks.as<uint2>(), &dc->n_tasks_cls[cls], qlist, L->wins.as<BhipWin>(), &dc->n_wins_cls[cls], dc, qmeta_cls);
+		// (beside the lane tasks the clump-level pairs are the rare overflow of the prefilter, usually none at all: a small grid --
+		// an empty launch of 2 048 workgroups waited ~0.24 ms for slots on a device busy with the next batch's seed lookups and staging)
+		if (NWP) launch_prefix(h, L, sw, NWP, masked ? std::min<uint32_t>(grid_my, (uint32_t)h->n_cu) : grid_my, L->cand.as<uint2>(), &dc->n_cand_cls[cls], L->cand_cap, 0, qlist, &dc->n_wins_cls[cls], dc);
+		else launch_myers(h, L, sw, NW, grid_my, L->cand.as<uint2>(), &dc->n_cand_cls[cls], L->cand_cap, 0, qlist, L->raw.as<BhipRawHit>(),
+			&dc->n_raw, (uint32_t)L->raw_cap, h->best.as<uint32_t>(), nullptr, dc);
+		HIPCHK(hipGetLastError());
+		++L->launches;
+	}
+	HIPCHK(hipEventRecord(ce[CE_SWEEP_PF_DONE], sw));
+	if (n_ex) {
+		const uint64_t np = (uint64_t)n_ex * h->n_clumps;
+		const uint32_t g = (uint32_t)std::min<uint64_t>((np + 15) / 16, grid_my);
+		if (NWP) launch_prefix(h, L, sw, NWP, g, nullptr, nullptr, np, n_pf, qlist, &dc->n_wins_cls[cls], dc);
+		else launch_myers(h, L, sw, NW, g, nullptr, nullptr, np, n_pf, qlist, L->raw.as<BhipRawHit>(), &dc->n_raw, (uint32_t)L->raw_cap,
+			h->best.as<uint32_t>(), nullptr, dc);
+		HIPCHK(hipGetLastError());
+		++L->launches;
+		L->n_pairs_ex += np;
+	}
+	HIPCHK(hipEventRecord(ce[CE_SWEEP_EX_DONE], sw));
+	HIPCHK(hipStreamWaitEvent(po, ce[CE_SWEEP_EX_DONE], 0));
+	if (NWP) { launch_window(h, L, po, cls, NWP, grid_my, L->wins.as<BhipWin>(), &dc->n_wins_cls[cls], dc); HIPCHK(hipGetLastError()); }
+	L->pruned[cls] = masked && prune && n_pf;
+	if (L->pruned[cls]) {
+		// second sweep: the deferred lanes whose lower bound is not above the minimum found by the first sweep
+		HIPCHK(hipEventRecord(L->ev_ph[cls][PH_WIN_DONE], po));
+		HIPCHK(hipStreamWaitEvent(sw, L->ev_ph[cls][PH_WIN_DONE], 0));
+		hipLaunchKernelGGL(k_task_filter, dim3((uint32_t)h->n_cu * 8), dim3(256), 0, sw, L->tasks2.as<uint2>(), &dc->n_tasks2_cls[cls], (uint32_t)L->task_cap, qlist,
+			six_or_null(h), h->best.as<uint32_t>(), L->tasks2k.as<uint2>(), &dc->n_tasks2k_cls[cls]);
+		launch_prefix_task(h, L, sw, NWP, grid_task, L->tasks2k.as<uint2>(), &dc->n_tasks2k_cls[cls], qlist, L->wins2.as<BhipWin>(), &dc->n_wins2_cls[cls], dc, qmeta_cls);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(L->ev_ph[cls][PH_SWEEP2_DONE], sw));
+		HIPCHK(hipStreamWaitEvent(po, L->ev_ph[cls][PH_SWEEP2_DONE], 0));
+		launch_window(h, L, po, cls, NWP, grid_my, L->wins2.as<BhipWin>(), &dc->n_wins2_cls[cls], dc);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipEventRecord(ce[CE_WIN_DONE], po));
+	HIPCHK(hipEventRecord(L->ev_rs[RS_START], po));
+	return 0;
+}
+
+// Enqueue the re-scoring of the kept reference lanes of a lane's shared slots on the post stream, behind its last class, and the read-back of
+// the lane's counters.
+static int enqueue_rescore(Handle *h, Lane *L, const BatchCall &b) {
+	hipStream_t po = h->post_stream;
 	Counters *dc = L->counters.as<Counters>();
 	SharedCtr *sc = h->shared_ctr.as<SharedCtr>();
-	L->launches = 0; L->prefix_words = 0; L->n_pairs_ex = 0; L->pf_launches = 0; L->fb_dirty = false;
-	for (int c = 0; c < kNumClasses; ++c) { L->pf_masked[c] = false; L->pruned[c] = false; }
-	const uint32_t grid_my = (uint32_t)h->n_cu * (uint32_t)h->opt_sweep_blocks;   // < 8 leaves wave slots for the other stages' kernels
-	(void)start;
-	for (int cls = 0; cls < kNumClasses; ++cls) {
-		const uint32_t n_pf = L->npf[cls], n_ex = L->nex[cls], n_list = n_pf + n_ex;
-		if (!n_list) continue;
-		const int NW = class_words(cls, L->maxlen);
-		const uint32_t *qlist = L->qlist[cls];
-		hipEvent_t *ce = L->ev_cls[cls];
-		// the lane's peq buffers are reused class after class: do not rebuild them before the previous class's window stage is done
-		// (the profiles are built on the sweep stream, which is idle while this class's seeds and prefilter run on theirs)
-		if (L->launches) { HIPCHK(hipStreamWaitEvent(pf, L->ev_rs[0], 0)); HIPCHK(hipStreamWaitEvent(sw, L->ev_rs[0], 0)); }
-		const int NWP = class_prefix_words(h, L->maxE[cls], NW);   // two-stage edit distance when a prefix of 32*NWP symbols is selective for this class's budgets
-		HIPCHK(hipEventRecord(ce[0], sw));
-		L->peq_ahead[cls] = false;
-		if (L->alt_ok && L->alt_seq == h->cur->seq && L->alt_cls == cls && L->alt_n == n_list && L->alt_nwp == NWP && !L->launches) {
-			// built ahead during the previous batch (seed_next_batch): that batch is through, its profiles are not needed any more
-			std::swap(L->peq, L->peq_alt); std::swap(L->peqp, L->peqp_alt);
-			std::swap(L->ev_peq_cur[0], L->ev_peq_alt[0]); std::swap(L->ev_peq_cur[1], L->ev_peq_alt[1]);
-			L->alt_ok = false; L->peq_ahead[cls] = true;
-		} else if ((rc = launch_peq(h, sw, h->cur, qlist, n_list, NW, NWP, L->peq, L->peqp))) return rc;
-		L->prefix_words = (uint32_t)NWP;
-		HIPCHK(hipEventRecord(ce[1], sw));
-		HIPCHK(hipEventRecord(ce[7], pf));
-		const bool masked = NWP && n_pf && h->has_masks && h->opt_lane_masks;
-		// lower-bound pruning (second sweep) only when the minimum per shared slot is all that is wanted, with the counting-filter
-		// kernel (it sees all lane counts of a query at once) and while a list position fits the 24 bits next to the bound
-		const int pf_algo = bhip_pf_algo(h->opt_pf_algo, L->pf_algo);
-		const int prune = masked && !all_hits && h->opt_prune && n_list < (1u << 24) && pf_algo == 0;
-		if (n_pf) {
-			if (masked) { if ((rc = launch_prefilter_mask(h, L, pf, cls, qlist, n_pf, L->maxwords[cls], &dc->n_tasks_cls[cls], &dc->n_cand_cls[cls], dc, pf_algo, prune))) return rc; }
-			else if ((rc = launch_prefilter(h, L, pf, qlist, n_pf, L->cand.as<uint2>(), nullptr, (uint32_t)L->cand_cap, true, &dc->n_cand_cls[cls], dc))) return rc;
-		}
-		// (query, length, budget) per list position, written by this batch's k_seed_ranges: what the prefix sweeps of the tasks start from
-		const uint4 *qmeta_cls = (masked && L->qmeta_seq[h->cur->seq & 1][cls] == h->cur->seq + 1) ? L->qmeta_c[h->cur->seq & 1][cls].as<uint4>() : nullptr;
-		L->masked = masked;
-		L->pf_masked[cls] = masked && n_pf;
-		HIPCHK(hipEventRecord(ce[2], pf));
-		// column sweep on the sweep stream, behind this lane's prefilter
-		HIPCHK(hipStreamWaitEvent(sw, ce[2], 0));
-		HIPCHK(hipEventRecord(ce[6], sw));
-		if (n_pf) {
-			if (masked) launch_prefix_task(h, L, sw, NWP, (uint32_t)h->n_cu * 4u * (uint32_t)h->opt_sweep_blocks * (uint32_t)h->opt_oversub, L->tasks.as<uint2>(), &dc->n_tasks_cls[cls], qlist, L->wins.as<BhipWin>(), &dc->n_wins_cls[cls], dc, qmeta_cls);
-			// (beside the lane tasks the clump-level pairs are the rare overflow of the prefilter, usually none at all: a small grid --
-			// an empty launch of 2 048 workgroups waited ~0.24 ms for slots on a device busy with the next batch's seed lookups and staging)
-			if (NWP) launch_prefix(h, L, sw, NWP, masked ? std::min<uint32_t>(grid_my, (uint32_t)h->n_cu) : grid_my, L->cand.as<uint2>(), &dc->n_cand_cls[cls], L->cand_cap, 0, qlist, &dc->n_wins_cls[cls], dc);
-			else launch_myers(h, L, sw, NW, grid_my, L->cand.as<uint2>(), &dc->n_cand_cls[cls], L->cand_cap, 0, qlist, L->raw.as<BhipRawHit>(),
-				&dc->n_raw, (uint32_t)L->raw_cap, h->best.as<uint32_t>(), nullptr, dc);
-			HIPCHK(hipGetLastError());
-			++L->launches;
-		}
-		HIPCHK(hipEventRecord(ce[3], sw));
-		if (n_ex) {
-			const uint64_t np = (uint64_t)n_ex * h->n_clumps;
-			const uint32_t g = (uint32_t)std::min<uint64_t>((np + 15) / 16, grid_my);
-			if (NWP) launch_prefix(h, L, sw, NWP, g, nullptr, nullptr, np, n_pf, qlist, &dc->n_wins_cls[cls], dc);
-			else launch_myers(h, L, sw, NW, g, nullptr, nullptr, np, n_pf, qlist, L->raw.as<BhipRawHit>(), &dc->n_raw, (uint32_t)L->raw_cap,
-				h->best.as<uint32_t>(), nullptr, dc);
-			HIPCHK(hipGetLastError());
-			++L->launches;
-			L->n_pairs_ex += np;
-		}
-		HIPCHK(hipEventRecord(ce[4], sw));
-		HIPCHK(hipStreamWaitEvent(po, ce[4], 0));
-		if (NWP) { launch_window(h, L, po, cls, NWP, grid_my, L->wins.as<BhipWin>(), &dc->n_wins_cls[cls], dc); HIPCHK(hipGetLastError()); }
-		L->pruned[cls] = masked && prune && n_pf;
-		if (masked && prune && n_pf) {
-			// second sweep: the deferred lanes whose lower bound is not above the minimum found by the first sweep
-			HIPCHK(hipEventRecord(L->ev_ph[cls][0], po));
-			HIPCHK(hipStreamWaitEvent(sw, L->ev_ph[cls][0], 0));
-			hipLaunchKernelGGL(k_task_filter, dim3((uint32_t)h->n_cu * 8), dim3(256), 0, sw, L->tasks2.as<uint2>(), &dc->n_tasks2_cls[cls], (uint32_t)L->task_cap, qlist,
-				h->cur->st_has_six ? h->cur->qsix.as<uint32_t>() : nullptr, h->best.as<uint32_t>(), L->tasks2k.as<uint2>(), &dc->n_tasks2k_cls[cls]);
-			launch_prefix_task(h, L, sw, NWP, (uint32_t)h->n_cu * 4u * (uint32_t)h->opt_sweep_blocks * (uint32_t)h->opt_oversub, L->tasks2k.as<uint2>(), &dc->n_tasks2k_cls[cls], qlist, L->wins2.as<BhipWin>(), &dc->n_wins2_cls[cls], dc, qmeta_cls);
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipEventRecord(L->ev_ph[cls][1], sw));
-			HIPCHK(hipStreamWaitEvent(po, L->ev_ph[cls][1], 0));
-			launch_window(h, L, po, cls, NWP, grid_my, L->wins2.as<BhipWin>(), &dc->n_wins2_cls[cls], dc);
-			HIPCHK(hipGetLastError());
-		}
-		HIPCHK(hipEventRecord(ce[5], po));
-		HIPCHK(hipEventRecord(L->ev_rs[0], po));
-	}
-	// re-scoring of the kept reference lanes of this lane's shared slots
-	HIPCHK(hipEventRecord(L->ev_rs[0], po));
+	const RefArgs R = ref_args(h);
+	HIPCHK(hipEventRecord(L->ev_rs[RS_START], po));
 	if (h->cur->st_has_junk) {       // back to the units of the original queries (see Handle::qcodes_s); this lane owns the shared slots [s0, s1)
 		const uint32_t nl_ = h->cur->st_lanes, nsh_ = h->cur->st_nshared;
 		uint32_t li_ = 0;
@@ -702,35 +748,41 @@ static int enqueue_lane(Handle *h, Lane *L, int all_hits, hipEvent_t start, uint
 	// classify (exact matches leave here), register-band variants for the narrow bands, LDS band for the rest
 	const uint32_t qw_g = (h->cur->st_maxlen + 7) / 8;
 	hipLaunchKernelGGL(k_rescore_classify, dim3((uint32_t)h->n_cu * 8), dim3(256), 0, po, L->raw.as<BhipRawHit>(), &dc->n_raw, (uint32_t)L->raw_cap,
-		h->best.as<uint32_t>(), all_hits, h->cur->qoff.as<uint64_t>(), h->cur->st_has_six ? h->cur->qsix.as<uint32_t>() : nullptr, h->cur->st_has_rc ? h->cur->qrc.as<uint8_t>() : nullptr,
-		h->clump_len.as<uint32_t>(), h->out.as<BhipHit>(), &sc->n_out, (uint32_t)h->out_cap, L->rs_lists.as<uint32_t>(), dc->n_rs, L->wide.as<uint32_t>(), &dc->n_wide,
-		band_rows, h->opt_rescore_reg);
+		h->best.as<uint32_t>(), b.all_hits, h->cur->qoff.as<uint64_t>(), six_or_null(h), rc_or_null(h),
+		R.len, h->out.as<BhipHit>(), &sc->n_out, (uint32_t)h->out_cap, L->rs_lists.as<uint32_t>(), dc->n_rs, L->wide.as<uint32_t>(), &dc->n_wide,
+		b.band_rows, h->opt_rescore_reg);
 	HIPCHK(hipGetLastError());
 	if (h->opt_rescore_reg) {
-#define RS_LAUNCH(SET, BLOCKS) hipLaunchKernelGGL(k_rescore_reg<SET>, dim3((uint32_t)h->n_cu * std::min<uint32_t>(32u, blocks_per_cu((const void *)k_rescore_reg<SET>, 64, 0)) * (uint32_t)h->opt_oversub), dim3(64), 0, po, L->raw.as<BhipRawHit>(), L->rs_lists.as<uint32_t>(), dc->n_rs, (uint32_t)L->raw_cap, \
-			h->cur->qoff.as<uint64_t>(), h->cur->st_has_rc ? h->cur->qrc.as<uint8_t>() : nullptr, h->cur->qpack.as<uint32_t>(), qw_g, \
-			h->ref_lane.as<uint8_t>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), h->lut.as<uint8_t>(), h->out.as<BhipHit>(), &sc->n_out, (uint32_t)h->out_cap, &sc->err)
-		RS_LAUNCH(0, 16);
+		for_each_int(SetList{}, [&](auto set) {
+			constexpr int SET = decltype(set)::value;
+			const uint32_t grid = (uint32_t)h->n_cu * std::min<uint32_t>(32u, blocks_per_cu((const void *)k_rescore_reg<SET>, 64, 0)) * (uint32_t)h->opt_oversub;
+			hipLaunchKernelGGL(k_rescore_reg<SET>, dim3(grid), dim3(64), 0, po, L->raw.as<BhipRawHit>(), L->rs_lists.as<uint32_t>(), dc->n_rs, (uint32_t)L->raw_cap,
+				h->cur->qoff.as<uint64_t>(), rc_or_null(h), h->cur->qpack.as<uint32_t>(), qw_g,
+				R.bytes(), R.off, R.len, h->lut.as<uint8_t>(), h->out.as<BhipHit>(), &sc->n_out, (uint32_t)h->out_cap, &sc->err);
+		});
 		HIPCHK(hipGetLastError());
-		RS_LAUNCH(3, 16);         // 12 diagonals: a kernel of its own, so that the 4 / 6 / 8 variants run at 80 registers (6 waves per SIMD instead of 4)
-		HIPCHK(hipGetLastError());
-		RS_LAUNCH(1, 12);
-		HIPCHK(hipGetLastError());
-		RS_LAUNCH(2, 8);          // 32 / 40 / 48 diagonals (usually empty lists: large budgets, or repeats that stretch the end-column range)
-		HIPCHK(hipGetLastError());
-#undef RS_LAUNCH
 	}
 	const uint32_t grid_rs = (uint32_t)h->n_cu * (h->opt_rescore_reg ? 4 : 16);
-	const size_t lds_rs = (size_t)(band_rows + 1 + qw + rw) * 256;
+	const size_t lds_rs = (size_t)(b.band_rows + 1 + b.qw + b.rw) * 256;
 	hipLaunchKernelGGL(k_rescore<false>, dim3(grid_rs), dim3(64), lds_rs, po, L->raw.as<BhipRawHit>(), &dc->n_raw, (uint32_t)L->raw_cap,
-		L->rs_lists.as<uint32_t>() + (size_t)9 * L->raw_cap, &dc->n_rs[9], h->best.as<uint32_t>(), all_hits, h->cur->qcodes.as<uint8_t>(), h->cur->qoff.as<uint64_t>(),
-		h->cur->st_has_six ? h->cur->qsix.as<uint32_t>() : nullptr, h->cur->st_has_rc ? h->cur->qrc.as<uint8_t>() : nullptr, h->ref_lane.as<uint8_t>(), h->ref_off.as<uint64_t>(),
-		h->clump_len.as<uint32_t>(), h->lut.as<uint8_t>(), h->out.as<BhipHit>(), &sc->n_out, (uint32_t)h->out_cap, L->wide.as<uint32_t>(),
-		&dc->n_wide, (uint32_t *)nullptr, &dc->scratch_used, 0ull, &sc->err, qw ? h->cur->qpack.as<uint32_t>() : nullptr, band_rows, qw, rw);
+		L->rs_lists.as<uint32_t>() + (size_t)9 * L->raw_cap, &dc->n_rs[9], h->best.as<uint32_t>(), b.all_hits, h->cur->qcodes.as<uint8_t>(), h->cur->qoff.as<uint64_t>(),
+		six_or_null(h), rc_or_null(h), R.bytes(), R.off, R.len, h->lut.as<uint8_t>(), h->out.as<BhipHit>(), &sc->n_out, (uint32_t)h->out_cap, L->wide.as<uint32_t>(),
+		&dc->n_wide, (uint32_t *)nullptr, &dc->scratch_used, 0ull, &sc->err, b.qw ? h->cur->qpack.as<uint32_t>() : nullptr, b.band_rows, b.qw, b.rw);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(L->ev_rs[1], po));
+	HIPCHK(hipEventRecord(L->ev_rs[RS_DONE], po));
 	HIPCHK(hipMemcpyAsync(L->hc_pinned, dc, sizeof(Counters), hipMemcpyDeviceToHost, po));
 	return 0;
+}
+
+// enqueue one lane's whole chain (no host synchronisation): every class that has queries, then the re-scoring
+static int enqueue_lane(Handle *h, Lane *L, const BatchCall &b) {
+	int rc;
+	if ((rc = lane_reserve_work(L))) return rc;
+	HIPCHK(hipMemsetAsync(L->counters.p, 0, sizeof(Counters), h->pf_stream));
+	L->launches = 0; L->prefix_words = 0; L->n_pairs_ex = 0; L->pf_launches = 0; L->fb_dirty = false;
+	for (int c = 0; c < kNumClasses; ++c) { L->pf_masked[c] = false; L->pruned[c] = false; }
+	for (int cls = 0; cls < kNumClasses; ++cls) if (L->npf[cls] + L->nex[cls]) if ((rc = enqueue_class(h, L, cls, b.all_hits))) return rc;
+	return enqueue_rescore(h, L, b);
 }
 
 // Seed lookups of the NEXT staged batch, enqueued on the prefilter stream behind the current batch's prefilter: they run
@@ -772,9 +824,9 @@ static void seed_next_batch(Handle *h, StageSlot *cur, hipEvent_t cur_done) {
 			const uint32_t n_list = N->npf[l][only] + N->nex[l][only];
 			const int NW = class_words(only, N->maxlen_lane[l]), NWP = class_prefix_words(h, N->maxE[l][only], NW);
 			L->alt_ok = false;
-			if (hipEventRecord(L->ev_peq_alt[0], h->pf_stream) != hipSuccess ||
+			if (hipEventRecord(L->ev_peq_alt[SPAN_START], h->pf_stream) != hipSuccess ||
 			    launch_peq(h, h->pf_stream, N, N->idx_sorted.as<uint32_t>() + N->qlist_off[l][only], n_list, NW, NWP, L->peq_alt, L->peqp_alt, (uint32_t)h->opt_peq_ahead_blocks) ||
-			    hipEventRecord(L->ev_peq_alt[1], h->pf_stream) != hipSuccess) { (void)hipGetLastError(); return; }
+			    hipEventRecord(L->ev_peq_alt[SPAN_DONE], h->pf_stream) != hipSuccess) { (void)hipGetLastError(); return; }
 			L->alt_ok = true; L->alt_seq = N->seq; L->alt_cls = only; L->alt_nwp = NWP; L->alt_n = n_list;
 		}
 	}
@@ -787,282 +839,366 @@ extern "C" int bhip_set_enqueued_hook(void *handle, void (*fn)(void *), void *ct
 	return BHIP_OK;
 }
 
-extern "C" int bhip_align_staged(void *handle, int all_hits_arg, BhipHit *hits, uint64_t cap, uint64_t *n_hits) {
-	Handle *h = (Handle *)handle;
-	if (!h || !n_hits) return fail(BHIP_E_ARG, "null argument");
-	*n_hits = 0;
-	if (all_hits_arg < 0 || all_hits_arg > BHIP_HITS_BEST) return fail(BHIP_E_ARG, "all_hits must be 0, 1 or 2 (BHIP_HITS_BEST)");
-	const int all_hits = all_hits_arg == BHIP_HITS_ALL ? 1 : 0;      // what the kernels are told: every hit within budget, or the minimum per shared slot
-	const bool sel_best = all_hits_arg == BHIP_HITS_BEST;            // ... and of those one record per entry, chosen on the device
-	if (sel_best && !h->n_order) return fail(BHIP_E_ARG, "BHIP_HITS_BEST needs the reference order table (bhip_set_ref_order)");
-	memset(&h->stats, 0, sizeof h->stats);
-	HIPCHK(hipSetDevice(h->device));
-	// the batch: the oldest one staged and not aligned yet, else the one aligned last (staged once, run any number of times)
+// A capacity that the `seen` items of a chain did not fit grows past them (an eighth on top where `eighth`, and 1 024); the chain is then
+// redone.  lane < 0: a buffer of the whole batch.  One BHIP_DEBUG line per growth.
+static bool grow_cap(uint64_t &cap, uint64_t seen, bool eighth, int lane, const char *what) {
+	if (seen <= cap) return false;
+	const uint64_t to = seen + (eighth ? seen / 8 : 0) + 1024;
+	if (getenv("BHIP_DEBUG")) {
+		if (lane >= 0) fprintf(stderr, "[bhip] redo: lane %d %s %llu -> %llu\n", lane, what, (unsigned long long)cap, (unsigned long long)to);
+		else fprintf(stderr, "[bhip] redo: %s %llu -> %llu\n", what, (unsigned long long)cap, (unsigned long long)to);
+	}
+	cap = to;
+	return true;
+}
+
+// the batch: the oldest one staged and not aligned yet, else the one aligned last (staged once, run any number of times)
+static int pick_batch(Handle *h, BatchCall &b) {
 	StageSlot *slot = nullptr;
 	for (StageSlot &S : h->slots) if (S.state == 1 && (!slot || S.seq < slot->seq)) slot = &S;
 	if (!slot) for (StageSlot &S : h->slots) if (S.state == 2 && (!slot || S.seq > slot->seq)) slot = &S;
 	if (!slot) return fail(BHIP_E_ARG, "no staged queries (call bhip_stage_queries first)");
 	{ int rcs = resolve_slot(h, slot); if (rcs) { slot->state = 0; return rcs; } }
 	apply_slot(h, slot);
-	const uint32_t n_q = h->cur->st_nq, n_shared = h->cur->st_nshared, nl = h->cur->st_lanes;
-	if (!n_q) { slot->state = 2; return BHIP_OK; }
-	// LDS plan of the re-scorer: band rows for the widest expected band (2*maxE+1 plus slack), query and reference staging
-	const uint32_t band_rows = std::min<uint32_t>(BHIP_RESCORE_WMAX, 2 * h->cur->st_maxE + 1 + 9);
-	uint32_t qw = (h->cur->st_maxlen + 7) / 8, rw = (h->cur->st_maxlen + band_rows + 24) / 8 + 2;
-	if ((size_t)(band_rows + 1 + qw + rw) * 256 > 40 * 1024) { qw = 0; rw = 0; }      // long queries: per-row global reads instead
-	SharedCtr hsc;
-	uint32_t n_deliver = 0;                // records the caller gets: all of them, or one per entry (sel_best)
-	bool sorted_ahead = false; int o_ahead = 0;
-	if (sel_best) { int rcs; if ((rcs = h->best_key.reserve((size_t)(n_q + 1) * 8)) || (rcs = h->sort_idx.reserve(std::max<size_t>((size_t)h->out_cap, (size_t)n_q + 1) * 4))) return rcs;      // (the rank array doubles as the per-entry flags)
-		if (!h->nsel_pinned) HIPCHK(hipHostMalloc((void **)&h->nsel_pinned, 64, hipHostMallocDefault)); }
-	// the grouping of the records on `st` into `sorted`: the counting sort by entry (scatter + a rank sort inside every group), or -- sel_best --
-	// the choice of one record per entry (two streaming passes).  cnt = records per entry (from the re-scoring kernels, or k_hit_count)
-	auto enqueue_grouping = [&](hipStream_t st, uint32_t n_host, const uint32_t *n_dev, DBuf &sorted, uint32_t *cnt, uint32_t *off, uint32_t *rank, size_t tmp_bytes) -> int {
-		const uint32_t g = (uint32_t)h->n_cu * 8;
-		const uint32_t *qmap = h->cur->has_qmap ? h->cur->qmap.as<uint32_t>() : (const uint32_t *)nullptr;
-		if (sel_best) {
-			// (flags into the rank array: the ranks the re-scoring kernels took are not needed when nothing is sorted)
-			hipLaunchKernelGGL(k_best_key, dim3(g), dim3(256), 0, st, h->out.as<BhipHit>(), n_host, n_dev, h->ref_order.as<uint32_t>(), cnt, h->best_key.as<unsigned long long>());
-			hipLaunchKernelGGL(k_best_flag, dim3(std::min<uint32_t>((n_q + 256) / 256, g)), dim3(256), 0, st, cnt, n_q, rank);
-			HIPCHK(hipcub::DeviceScan::ExclusiveSum(h->sort_tmp.p, tmp_bytes, rank, off, (int)(n_q + 1), st));
-			hipLaunchKernelGGL(k_best_emit, dim3(g), dim3(256), 0, st, h->out.as<BhipHit>(), n_host, n_dev, h->ref_order.as<uint32_t>(), cnt, h->best_key.as<unsigned long long>(), off, sorted.as<BhipHit>(), qmap);
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipMemcpyAsync(h->nsel_pinned, off + n_q, 4, hipMemcpyDeviceToHost, st));      // (the scan runs over n_q + 1 counters, the last one zero: its offset is the total)
-			return 0;
-		}
-		HIPCHK(hipcub::DeviceScan::ExclusiveSum(h->sort_tmp.p, tmp_bytes, cnt, off, (int)(n_q + 1), st));
-		hipLaunchKernelGGL(k_hit_scatter, dim3(g), dim3(256), 0, st, h->out.as<BhipHit>(), n_host, n_dev, off, rank, sorted.as<BhipHit>(), qmap);
-		hipLaunchKernelGGL(k_hit_fix, dim3(std::min<uint32_t>((n_q + 255) / 256, (uint32_t)h->n_cu * 8)), dim3(256), 0, st, sorted.as<BhipHit>(), off, cnt, n_q, h->sort_scratch.as<BhipHit>(), (uint32_t)(h->sort_scratch.cap / sizeof(BhipHit)));
+	b.slot = slot; b.n_q = h->cur->st_nq; b.n_shared = h->cur->st_nshared; b.nl = h->cur->st_lanes;
+	return BHIP_OK;
+}
+// LDS plan of the re-scorer: band rows for the widest expected band (2*maxE+1 plus slack), query and reference staging; what BEST needs
+static int plan_batch(Handle *h, BatchCall &b) {
+	b.band_rows = std::min<uint32_t>(BHIP_RESCORE_WMAX, 2 * h->cur->st_maxE + 1 + 9);
+	b.qw = (h->cur->st_maxlen + 7) / 8; b.rw = (h->cur->st_maxlen + b.band_rows + 24) / 8 + 2;
+	if ((size_t)(b.band_rows + 1 + b.qw + b.rw) * 256 > 40 * 1024) { b.qw = 0; b.rw = 0; }      // long queries: per-row global reads instead
+	if (!b.sel_best) return BHIP_OK;
+	int rc;
+	if ((rc = h->best_key.reserve((size_t)(b.n_q + 1) * 8)) || (rc = h->sort_idx.reserve(std::max<size_t>((size_t)h->out_cap, (size_t)b.n_q + 1) * 4))) return rc;      // (the rank array doubles as the per-entry flags)
+	if (!h->nsel_pinned) HIPCHK(hipHostMalloc((void **)&h->nsel_pinned, 64, hipHostMallocDefault));
+	return BHIP_OK;
+}
+// the records of this batch are still resident when the previous call only failed for the size of the caller's buffer
+static bool records_resident(const Handle *h, const BatchCall &b) { return h->res_valid && h->res_seq == b.slot->seq && h->res_all_hits == b.mode; }
+static void take_resident(Handle *h, BatchCall &b) {
+	b.hsc.n_out = h->res_n_raw; b.hsc.err = 0; h->stats = h->res_stats; b.n_deliver = h->res_n; *b.n_hits = b.n_deliver; b.sorted_ahead = false;
+}
+
+// the scan over the n_q + 1 per-entry counters on `st`: its scratch
+static int plan_scan(Handle *h, BatchCall &b, hipStream_t st) {
+	b.tmp_bytes = 0;
+	HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, b.tmp_bytes, h->sort_keys.as<uint32_t>(), h->sort_keys2.as<uint32_t>(), (int)(b.n_q + 1), st));
+	return h->sort_tmp.reserve(b.tmp_bytes);
+}
+// the grouping of the records on `st` into `sorted`: the counting sort by entry (scatter + a rank sort inside every group), or -- sel_best --
+// the choice of one record per entry (two streaming passes).  sort_keys = records per entry (from the re-scoring kernels, or k_hit_count),
+// sort_keys2 = their offsets, sort_idx = rank of a record inside its entry; n_dev: the record count where it still lives on the device
+static int enqueue_grouping(Handle *h, const BatchCall &b, hipStream_t st, uint32_t n_host, const uint32_t *n_dev, DBuf &sorted) {
+	uint32_t *cnt = h->sort_keys.as<uint32_t>(), *off = h->sort_keys2.as<uint32_t>(), *rank = h->sort_idx.as<uint32_t>();
+	const uint32_t n_q = b.n_q, g = (uint32_t)h->n_cu * 8;
+	const uint32_t *qmap = h->cur->has_qmap ? h->cur->qmap.as<uint32_t>() : (const uint32_t *)nullptr;
+	size_t tmp_bytes = b.tmp_bytes;
+	if (b.sel_best) {
+		// (flags into the rank array: the ranks the re-scoring kernels took are not needed when nothing is sorted)
+		hipLaunchKernelGGL(k_best_key, dim3(g), dim3(256), 0, st, h->out.as<BhipHit>(), n_host, n_dev, h->ref_order.as<uint32_t>(), cnt, h->best_key.as<unsigned long long>());
+		hipLaunchKernelGGL(k_best_flag, dim3(std::min<uint32_t>((n_q + 256) / 256, g)), dim3(256), 0, st, cnt, n_q, rank);
+		HIPCHK(hipcub::DeviceScan::ExclusiveSum(h->sort_tmp.p, tmp_bytes, rank, off, (int)(n_q + 1), st));
+		hipLaunchKernelGGL(k_best_emit, dim3(g), dim3(256), 0, st, h->out.as<BhipHit>(), n_host, n_dev, h->ref_order.as<uint32_t>(), cnt, h->best_key.as<unsigned long long>(), off, sorted.as<BhipHit>(), qmap);
 		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(h->nsel_pinned, off + n_q, 4, hipMemcpyDeviceToHost, st));      // (the scan runs over n_q + 1 counters, the last one zero: its offset is the total)
 		return 0;
-	};
-	for (int attempt = 0; attempt < 24; ++attempt) {
-		int rc;
-		sorted_ahead = false;
-		// the records of this batch are still resident when the previous call only failed for the size of the caller's buffer
-		if (h->res_valid && h->res_seq == slot->seq && h->res_all_hits == all_hits_arg) { hsc.n_out = h->res_n_raw; hsc.err = 0; h->stats = h->res_stats; n_deliver = h->res_n; *n_hits = n_deliver; }
-		else {
-		h->res_valid = false;
-		if ((rc = h->best.reserve((size_t)(n_shared + 1) * 4))) return rc;
-		if ((rc = h->out.reserve(h->out_cap * sizeof(BhipHit)))) return rc;
-		if ((rc = h->shared_ctr.reserve(sizeof(SharedCtr)))) return rc;
-		HIPCHK(hipEventRecord(h->ev[0], h->stream));
-		HIPCHK(hipMemsetAsync(h->best.p, 0xFF, (size_t)n_shared * 4, h->stream));
-		HIPCHK(hipMemsetAsync(h->shared_ctr.p, 0, 2 * sizeof(uint32_t), h->stream));
-		{	// the counting sort's counters (zeroed here, off the critical path) and ranks, for the re-scoring kernels
-			if ((rc = h->sort_idx.reserve((size_t)h->out_cap * 4)) || (rc = h->sort_keys.reserve((size_t)(n_q + 1) * 4))) return rc;
-			HIPCHK(hipMemsetAsync(h->sort_keys.p, 0, (size_t)(n_q + 1) * 4, h->stream));
-			if (sel_best) HIPCHK(hipMemsetAsync(h->best_key.p, 0xFF, (size_t)(n_q + 1) * 8, h->stream));
-			hipLaunchKernelGGL(k_set_rank_ptrs, dim3(1), dim3(1), 0, h->stream, h->shared_ctr.as<SharedCtr>(), h->sort_keys.as<uint32_t>(), h->sort_idx.as<uint32_t>());
-		}
-		HIPCHK(hipEventRecord(h->ev[1], h->stream));
-		HIPCHK(hipStreamWaitEvent(h->sweep_stream, h->ev[1], 0));
-		// (the prefilter stream does not wait for these fills: nothing it runs touches `best` or the shared counters -- the sweeps and the
-		// re-scorer do, on the stream the fills are on -- and the previous batch has been waited for by the host: the prefilter starts
-		// ~75 us earlier)
-		HIPCHK(hipStreamWaitEvent(h->post_stream, h->ev[1], 0));
-		for (uint32_t l = 0; l < nl; ++l) if (h->lanes[l]->n_entries) if ((rc = enqueue_lane(h, h->lanes[l], all_hits, h->ev[1], band_rows, qw, rw))) return rc;
-		HIPCHK(hipEventRecord(h->ev[2], h->pf_stream));          // this batch's share of the prefilter stream ends here
-		// the records are grouped by query (counting sort) right behind the re-scorer, with the record count read on the device: no
-		// host round trip between the two.  Set aside when a lane needs the wide-band re-scorer afterwards (sorted again then).
-		sorted_ahead = false;
-		{
-			const bool async = h->opt_async_d2h && hits;
-			o_ahead = async ? (h->out_idx ^ 1) : 0;
-			DBuf &sorted = o_ahead ? h->out_sorted2 : h->out_sorted;
-			size_t tmp_bytes = 0;
-			uint32_t *cnt = nullptr, *off = nullptr, *rank = nullptr;
-			if ((rc = h->sort_idx.reserve((size_t)h->out_cap * 4)) || (rc = h->sort_keys.reserve((size_t)(n_q + 1) * 4)) || (rc = h->sort_keys2.reserve((size_t)(n_q + 1) * 4)) ||
-			    (rc = sorted.reserve((size_t)h->out_cap * sizeof(BhipHit))) || (rc = h->sort_scratch.reserve((size_t)h->out_cap * sizeof(BhipHit)))) return rc;
-			cnt = h->sort_keys.as<uint32_t>(); off = h->sort_keys2.as<uint32_t>(); rank = h->sort_idx.as<uint32_t>();
-			HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cnt, off, (int)(n_q + 1), h->post_stream));
-			if ((rc = h->sort_tmp.reserve(tmp_bytes))) return rc;
-			SharedCtr *sc = h->shared_ctr.as<SharedCtr>();
-			if (h->copy_pending[o_ahead]) HIPCHK(hipStreamWaitEvent(h->post_stream, h->ev_copied[o_ahead], 0));      // the copy that last read this buffer
-			HIPCHK(hipEventRecord(h->ev[4], h->post_stream));
-			// (counts and ranks were taken by the re-scoring kernels as they wrote the records)
-			if ((rc = enqueue_grouping(h->post_stream, (uint32_t)h->out_cap, &sc->n_out, sorted, cnt, off, rank, tmp_bytes))) return rc;
-			HIPCHK(hipEventRecord(h->ev[5], h->post_stream));
-			sorted_ahead = true;
-		}
-		if (!h->hsc_pinned) HIPCHK(hipHostMalloc((void **)&h->hsc_pinned, sizeof(SharedCtr), hipHostMallocDefault));
-		HIPCHK(hipMemcpyAsync(h->hsc_pinned, h->shared_ctr.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->post_stream));
-		HIPCHK(hipEventRecord(h->ev[3], h->post_stream));
-		seed_next_batch(h, slot, h->ev[3]);
-		if (h->enqueued_hook && attempt == 0) h->enqueued_hook(h->enqueued_ctx);      // the caller's host work for later batches, while the device is busy with this one
-		HIPCHK(hipEventSynchronize(h->ev[2]));
-		HIPCHK(hipStreamSynchronize(h->sweep_stream));
-		HIPCHK(hipStreamSynchronize(h->post_stream));
-		for (uint32_t l = 0; l < nl; ++l) if (h->lanes[l]->n_entries) h->lanes[l]->hc = *h->lanes[l]->hc_pinned;
-		for (uint32_t l = 0; l < nl; ++l) {      // a lane whose records mostly survive the counting filter does better with the exact table
-			Lane *L = h->lanes[l];
-			// (with the minimum-only semantics the counting-filter kernel also splits off the lanes that cannot hold a minimum --
-			// the second sweep -- which the exact-table kernel does not: it only takes over when most records survive)
-			// Round 6: measured again with k_prefilter_cq on a database with strain-level redundancy (57 % of the records survive its filter: a read
-			// of a 500-strain family meets the family's clumps in every one of its lists): the exact-table kernel took 61.5 ms per 2 M reads where
-			// k_prefilter_cq takes 8.5 (gpurun_out/r06a, r06b) -- with the minimum-only semantics the switch is off while that kernel is in use
-			const bool cq_min_only = !all_hits && h->opt_pf_cw == 2 && L->pf_algo_used == 3;
-			if (L->n_entries && L->pf_algo == 0 && !cq_min_only && L->hc.ent_read > 100000 && (double)L->hc.surv_sum > (all_hits ? 0.20 : 0.50) * (double)L->hc.ent_read) L->pf_algo = 1;
-		}
-		if (getenv("BHIP_DEBUG")) for (uint32_t l = 0; l < nl; ++l) {
-			const Lane *L = h->lanes[l];
-			if (!L->n_entries) continue;
-			fprintf(stderr, "[bhip] lane %u: %llu list records, %llu survived the counting filter, next prefilter algorithm %d\n", l, (unsigned long long)L->hc.ent_read, (unsigned long long)L->hc.surv_sum, L->pf_algo);
-			for (int cls = 0; cls < kNumClasses; ++cls) if (L->npf[cls] + L->nex[cls])
-				fprintf(stderr, "[bhip] lane %u class NW=%d: prefiltered %u exhaustive %u maxE %u maxwords %u | tasks %u + deferred %u (kept %u) clump pairs %u windows %u + %u | fallback queries(last class) %u raw %u\n",
-					l, kClasses[cls], L->npf[cls], L->nex[cls], L->maxE[cls], L->maxwords[cls], L->hc.n_tasks_cls[cls], L->hc.n_tasks2_cls[cls], L->hc.n_tasks2k_cls[cls], L->hc.n_cand_cls[cls], L->hc.n_wins_cls[cls], L->hc.n_wins2_cls[cls], L->hc.n_fb, L->hc.n_raw);
-			if (L->hc.n_fb) fprintf(stderr, "[bhip] lane %u: %u queries overflowed the first prefilter pass, %u the second (dense fallback)\n", l, L->hc.n_fb, L->hc.n_fb2);
-		}
-		// capacity checks (first call of a workload: grow and redo)
-		bool retry = false;
-		for (uint32_t l = 0; l < nl; ++l) {
-			Lane *L = h->lanes[l];
-			if (!L->n_entries) continue;
-			const Counters &c = L->hc;
-			for (int cls = 0; cls < kNumClasses; ++cls) {
-				if (c.n_cand_cls[cls] > L->cand_cap) { L->cand_cap = (uint64_t)c.n_cand_cls[cls] + c.n_cand_cls[cls] / 8 + 1024; retry = true; }
-				if (c.n_tasks_cls[cls] > L->task_cap) { L->task_cap = (uint64_t)c.n_tasks_cls[cls] + c.n_tasks_cls[cls] / 8 + 1024; retry = true; }
-				if (c.n_tasks2_cls[cls] > L->task_cap) { L->task_cap = (uint64_t)c.n_tasks2_cls[cls] + c.n_tasks2_cls[cls] / 8 + 1024; retry = true; }
-				if (c.n_wins2_cls[cls] > L->win_cap) { L->win_cap = (uint64_t)c.n_wins2_cls[cls] + c.n_wins2_cls[cls] / 8 + 1024; retry = true; }
-				if (c.n_wins_cls[cls] > L->win_cap) { L->win_cap = (uint64_t)c.n_wins_cls[cls] + c.n_wins_cls[cls] / 8 + 1024; retry = true; }
-			}
-			if (c.n_raw > L->raw_cap) { L->raw_cap = (uint64_t)c.n_raw + c.n_raw / 8 + 1024; retry = true; }
-		}
-		if (retry) continue;
-		// rare: bands wider than the LDS plan (repeats inside one shear) -> global-scratch variant, lane by lane
-		bool scratch_retry = false;
-		for (uint32_t l = 0; l < nl; ++l) {
-			Lane *L = h->lanes[l];
-			if (!L->n_entries || !L->hc.n_wide) continue;
-			sorted_ahead = false;                  // more records are on their way
-			Counters *dc = L->counters.as<Counters>();
-			SharedCtr *sc = h->shared_ctr.as<SharedCtr>();
-			hipLaunchKernelGGL(k_rescore<true>, dim3(std::min<uint32_t>((L->hc.n_wide + 63) / 64, (uint32_t)h->n_cu * 16)), dim3(64), 256, h->post_stream,
-				L->raw.as<BhipRawHit>(), &dc->n_raw, (uint32_t)L->raw_cap, L->wide.as<uint32_t>(), &dc->n_wide, h->best.as<uint32_t>(), all_hits,
-				h->cur->qcodes.as<uint8_t>(), h->cur->qoff.as<uint64_t>(), h->cur->st_has_six ? h->cur->qsix.as<uint32_t>() : nullptr, h->cur->st_has_rc ? h->cur->qrc.as<uint8_t>() : nullptr,
-				h->ref_lane.as<uint8_t>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), h->lut.as<uint8_t>(), h->out.as<BhipHit>(),
-				&sc->n_out, (uint32_t)h->out_cap, (uint32_t *)nullptr, (uint32_t *)nullptr, L->scratch.as<uint32_t>(), &dc->scratch_used,
-				(unsigned long long)L->scratch_cap, &sc->err, (const uint32_t *)nullptr, 0u, 0u, 0u);
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipMemcpyAsync(&L->hc, dc, sizeof(Counters), hipMemcpyDeviceToHost, h->post_stream));
-			HIPCHK(hipStreamSynchronize(h->post_stream));
-			if (L->hc.scratch_used > L->scratch_cap) { L->scratch_cap = (uint64_t)L->hc.scratch_used + 1024; scratch_retry = true; }
-		}
-		if (sorted_ahead) hsc = *h->hsc_pinned;      // (nothing ran after the chain: the copy behind it is current)
-		else HIPCHK(hipMemcpy(&hsc, h->shared_ctr.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-		if (scratch_retry || (hsc.err & 2u)) continue;
-		if (hsc.err & 1u) return fail(BHIP_E_RESCORE, "re-scoring could not reproduce a hit found by the edit-distance kernel (a query starting with a symbol outside the alphabet? the reference stops here as well: CRITICAL ERROR: Truncation within known good path, burst.c:812-816)");
-		if (hsc.n_out > h->out_cap) { h->out_cap = (uint64_t)hsc.n_out + hsc.n_out / 8 + 1024; continue; }
-		n_deliver = sel_best ? (sorted_ahead ? *h->nsel_pinned : std::min<uint32_t>(hsc.n_out, n_q)) : hsc.n_out;      // (not grouped yet: an upper bound; the grouping below gives the number)
-		*n_hits = n_deliver;
-		h->last_n_out = 0;
-		// statistics
-		BhipStats &S = h->stats;
-		S.n_queries = n_q; S.n_hits = n_deliver;
-		uint64_t qlen_sum = 0;
-		for (uint32_t l = 0; l < nl; ++l) {
-			Lane *L = h->lanes[l];
-			if (!L->n_entries) continue;
-			const Counters &c = L->hc;
-			S.n_pairs += L->n_pairs_ex + c.unit_sum; S.n_columns += c.col_sum; S.n_task_columns += c.tcol_sum; S.n_raw_hits += c.n_raw; S.acx_entries_read += c.ent_read;
-			S.myers_launches += L->launches; S.prefilter_launches += L->pf_launches; if (L->pf_launches) S.prefilter_algo = (uint32_t)L->pf_algo_used; S.n_window_columns += c.wcol_sum; qlen_sum += c.qlen_sum;
-			if (L->prefix_words) S.prefix_words = L->prefix_words;
-			for (int cls = 0; cls < kNumClasses; ++cls) {
-				S.n_pairs += c.n_cand_cls[cls]; S.n_windows += c.n_wins_cls[cls] + c.n_wins2_cls[cls]; S.n_lane_tasks += c.n_tasks_cls[cls] + c.n_tasks2k_cls[cls];
-				if (!(L->npf[cls] + L->nex[cls])) continue;
-				hipEvent_t *ce = L->ev_cls[cls];
-				S.ms_peq += L->peq_ahead[cls] ? ev_ms(L->ev_peq_cur[0], L->ev_peq_cur[1]) : ev_ms(ce[0], ce[1]);
-				if (L->npf[cls]) S.ms_prefilter += ev_ms(ce[7], ce[2]);
-				if (L->npf[cls] && L->pf_masked[cls]) { { hipEvent_t *es = L->ev_seed[h->cur->seq & 1][cls]; S.ms_seed += ev_ms(es[0], es[1]); } S.ms_prefilter_hash += ev_ms(L->ev_pf[cls][1], L->ev_pf[cls][2]); S.n_seed_words += L->seed_words[cls]; }
-				float sweep = ev_ms(ce[6], ce[4]), win = ev_ms(ce[4], ce[5]);
-				if (L->pruned[cls]) { const float second = ev_ms(L->ev_ph[cls][0], L->ev_ph[cls][1]); sweep += second; win -= second; }   // filter + second task sweep sit between the two window launches
-				S.ms_myers += sweep + win;
-				if (L->prefix_words) { S.ms_myers_prefix += sweep; S.ms_myers_window += win; }
-			}
-			S.ms_rescore += ev_ms(L->ev_rs[0], L->ev_rs[1]);
-		}
-		S.bytes_algorithmic = 8ull * S.n_columns + qlen_sum / 2 + 192ull * S.n_pairs;
-		h->res_valid = true; h->res_seq = slot->seq; h->res_all_hits = all_hits_arg; h->res_n = n_deliver; h->res_n_raw = hsc.n_out; h->res_stats = h->stats;
-		}
-		BhipStats &S = h->stats;
-		if (hits && n_deliver > cap) return fail(BHIP_E_CAPACITY, "hit buffer holds %llu records, %u needed", (unsigned long long)cap, n_deliver);
-		HIPCHK(hipEventRecord(h->ev[8], h->stream));
-		const bool dbg_t = getenv("BHIP_DEBUG_TIMES") != nullptr;
-		const auto tq0 = std::chrono::steady_clock::now();
-		auto tq = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count(); };
-		double tq1 = 0, tq2 = 0, tq3 = 0, tq4 = 0;
-		if (hsc.n_out) {
-			const uint32_t n = hsc.n_out;
-			if ((rc = h->sort_idx.reserve(std::max<size_t>((size_t)n, sel_best ? (size_t)n_q + 1 : 0) * 4)) || (rc = h->sort_keys.reserve((size_t)(n_q + 1) * 4)) || (rc = h->sort_keys2.reserve((size_t)(n_q + 1) * 4)) ||
-			    0) return rc;
-			const bool async = h->opt_async_d2h && hits;
-			const int o = async ? (h->out_idx ^= 1) : 0;
-			DBuf &sorted = o ? h->out_sorted2 : h->out_sorted;
-			if (sorted_ahead && o == o_ahead) tq1 = tq();          // grouped already, behind the re-scorer
-			else {
-			if (h->copy_pending[o]) { HIPCHK(hipEventSynchronize(h->ev_copied[o])); h->copy_pending[o] = false; }    // the copy that last read this buffer
-			if ((rc = sorted.reserve((size_t)n * sizeof(BhipHit))) || (rc = h->sort_scratch.reserve((size_t)n * sizeof(BhipHit)))) return rc;
-			uint32_t *cnt = h->sort_keys.as<uint32_t>(), *off = h->sort_keys2.as<uint32_t>(), *rank = h->sort_idx.as<uint32_t>();
-			const uint32_t g = std::min<uint32_t>((n + 255) / 256, (uint32_t)h->n_cu * 8);
-			HIPCHK(hipMemsetAsync(cnt, 0, (size_t)(n_q + 1) * 4, h->stream));
-			if (sel_best) HIPCHK(hipMemsetAsync(h->best_key.p, 0xFF, (size_t)(n_q + 1) * 8, h->stream));
-			tq1 = tq();
-			hipLaunchKernelGGL(k_hit_count, dim3(g), dim3(256), 0, h->stream, h->out.as<BhipHit>(), n, (const uint32_t *)nullptr, cnt, rank);
-			size_t tmp_bytes = 0;
-			HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cnt, off, (int)(n_q + 1), h->stream));
-			if ((rc = h->sort_tmp.reserve(tmp_bytes))) return rc;
-			if ((rc = enqueue_grouping(h->stream, n, (const uint32_t *)nullptr, sorted, cnt, off, rank, tmp_bytes))) return rc;
-			if (sel_best) {      // (the number of selected records is only known now: rare path -- records that stayed resident, wide bands)
-				HIPCHK(hipStreamSynchronize(h->stream));
-				n_deliver = *h->nsel_pinned; *n_hits = n_deliver; S.n_hits = n_deliver; h->res_n = n_deliver;
-				if (hits && n_deliver > cap) return fail(BHIP_E_CAPACITY, "hit buffer holds %llu records, %u needed", (unsigned long long)cap, n_deliver);
-			}
-			}
-			tq2 = tq();
-			const size_t bytes = (size_t)n_deliver * sizeof(BhipHit);
-			bool queued = false;
-			if (async) {
-				// page-lock the caller's buffer (kept registered: callers alternate between two buffers), then copy on the copy stream
-				if (!h->copy_stream) { HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&h->ev_sorted, hipEventDisableTiming));
-					for (auto &e : h->ev_copied) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
-				const size_t want = (size_t)cap * sizeof(BhipHit);
-				bool reg_ok = h->reg_ptr[o] == (void *)hits && h->reg_bytes[o] >= bytes;
-				if (!reg_ok) {      // already page-locked by the caller (bhip_alloc_host / bhip_host_register)?
-					hipPointerAttribute_t at;
-					memset(&at, 0, sizeof at);
-					if (hipPointerGetAttributes(&at, (const void *)hits) == hipSuccess && at.type == hipMemoryTypeHost) reg_ok = true;
-					else (void)hipGetLastError();
-				}
-				if (!reg_ok) {
-					if (h->reg_ptr[o]) { (void)hipHostUnregister(h->reg_ptr[o]); h->reg_ptr[o] = nullptr; }
-					if (h->reg_ptr[o ^ 1] == (void *)hits) { if (h->copy_pending[o ^ 1]) { HIPCHK(hipEventSynchronize(h->ev_copied[o ^ 1])); h->copy_pending[o ^ 1] = false; }
-						(void)hipHostUnregister(h->reg_ptr[o ^ 1]); h->reg_ptr[o ^ 1] = nullptr; }
-					if (hipHostRegister((void *)hits, want, hipHostRegisterDefault) == hipSuccess) { h->reg_ptr[o] = (void *)hits; h->reg_bytes[o] = want; reg_ok = true; }
-					else (void)hipGetLastError();
-				}
-				tq3 = tq();
-				if (reg_ok) {
-					HIPCHK(hipEventRecord(h->ev_sorted, h->stream));
-					HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_sorted, 0));
-					HIPCHK(hipMemcpyAsync(hits, sorted.p, bytes, hipMemcpyDeviceToHost, h->copy_stream));
-					HIPCHK(hipEventRecord(h->ev_copied[o], h->copy_stream));
-					h->copy_pending[o] = true;
-					queued = true;
-				}
-			}
-			if (hits && !queued) HIPCHK(hipMemcpyAsync(hits, sorted.p, bytes, hipMemcpyDeviceToHost, h->stream));
-			h->last_n_out = n_deliver; h->last_out = o;
-		}
-		tq4 = tq();
-		HIPCHK(hipEventRecord(h->ev[9], h->stream));
-		HIPCHK(hipStreamSynchronize(h->stream));
-		if (dbg_t) fprintf(stderr, "[bhip] delivery host ms: reserve+memset %.3f, sort launches %.3f, pointer check %.3f, copy enqueue %.3f, sync %.3f\n", tq1, tq2 - tq1, tq3 - tq2, tq4 - tq3, tq() - tq4);
-		S.ms_h2d = h->cur->st_ms_h2d; S.ms_stage_copy = h->cur->st_ms_copy; S.ms_stage_route = h->cur->st_ms_route; S.ms_d2h = ev_ms(h->ev[8], h->ev[9]) + (sorted_ahead ? ev_ms(h->ev[4], h->ev[5]) : 0.0f); S.ms_total = ev_ms(h->ev[0], h->ev[9]);
-		slot->state = 2;
-		h->res_valid = false;
-		return BHIP_OK;
 	}
-	return fail(BHIP_E_INTERNAL, "buffers kept overflowing");
+	HIPCHK(hipcub::DeviceScan::ExclusiveSum(h->sort_tmp.p, tmp_bytes, cnt, off, (int)(n_q + 1), st));
+	hipLaunchKernelGGL(k_hit_scatter, dim3(g), dim3(256), 0, st, h->out.as<BhipHit>(), n_host, n_dev, off, rank, sorted.as<BhipHit>(), qmap);
+	hipLaunchKernelGGL(k_hit_fix, dim3(std::min<uint32_t>((n_q + 255) / 256, (uint32_t)h->n_cu * 8)), dim3(256), 0, st, sorted.as<BhipHit>(), off, cnt, n_q, h->sort_scratch.as<BhipHit>(), (uint32_t)(h->sort_scratch.cap / sizeof(BhipHit)));
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+// The records are grouped right behind the re-scorer, with the record count read on the device: no host round trip between the two
+// (counts and ranks were taken by the re-scoring kernels as they wrote the records).  Void when a lane needs the wide-band re-scorer
+// afterwards: more records are on their way then, and deliver() groups them all.
+static int enqueue_grouping_ahead(Handle *h, BatchCall &b) {
+	int rc;
+	b.o_ahead = (h->opt_async_d2h && b.hits) ? (h->out_idx ^ 1) : 0;
+	DBuf &sorted = b.o_ahead ? h->out_sorted2 : h->out_sorted;
+	if ((rc = h->sort_idx.reserve((size_t)h->out_cap * 4)) || (rc = h->sort_keys.reserve((size_t)(b.n_q + 1) * 4)) || (rc = h->sort_keys2.reserve((size_t)(b.n_q + 1) * 4)) ||
+	    (rc = sorted.reserve((size_t)h->out_cap * sizeof(BhipHit))) || (rc = h->sort_scratch.reserve((size_t)h->out_cap * sizeof(BhipHit)))) return rc;
+	if ((rc = plan_scan(h, b, h->post_stream))) return rc;
+	if (h->copy_pending[b.o_ahead]) HIPCHK(hipStreamWaitEvent(h->post_stream, h->ev_copied[b.o_ahead], 0));      // the copy that last read this buffer
+	HIPCHK(hipEventRecord(h->ev[EV_GROUP_START], h->post_stream));
+	if ((rc = enqueue_grouping(h, b, h->post_stream, (uint32_t)h->out_cap, &h->shared_ctr.as<SharedCtr>()->n_out, sorted))) return rc;
+	HIPCHK(hipEventRecord(h->ev[EV_GROUP_DONE], h->post_stream));
+	b.sorted_ahead = true;
+	return BHIP_OK;
+}
+
+// Enqueue a whole chain, nothing waited for: the resets of the batch-wide buffers, every lane, the grouping ahead, the read-back of the shared
+// counters; then the seed lookups of the next staged batch and -- first attempt only -- the caller's hook.
+static int enqueue_chain(Handle *h, BatchCall &b, int attempt) {
+	int rc;
+	const uint32_t n_q = b.n_q;
+	b.sorted_ahead = false;
+	if ((rc = h->best.reserve((size_t)(b.n_shared + 1) * 4)) || (rc = h->out.reserve(h->out_cap * sizeof(BhipHit))) || (rc = h->shared_ctr.reserve(sizeof(SharedCtr)))) return rc;
+	HIPCHK(hipEventRecord(h->ev[EV_BEGIN], h->stream));
+	HIPCHK(hipMemsetAsync(h->best.p, 0xFF, (size_t)b.n_shared * 4, h->stream));
+	HIPCHK(hipMemsetAsync(h->shared_ctr.p, 0, 2 * sizeof(uint32_t), h->stream));
+	// the counting sort's counters (zeroed here, off the critical path) and ranks, for the re-scoring kernels
+	if ((rc = h->sort_idx.reserve((size_t)h->out_cap * 4)) || (rc = h->sort_keys.reserve((size_t)(n_q + 1) * 4))) return rc;
+	HIPCHK(hipMemsetAsync(h->sort_keys.p, 0, (size_t)(n_q + 1) * 4, h->stream));
+	if (b.sel_best) HIPCHK(hipMemsetAsync(h->best_key.p, 0xFF, (size_t)(n_q + 1) * 8, h->stream));
+	hipLaunchKernelGGL(k_set_rank_ptrs, dim3(1), dim3(1), 0, h->stream, h->shared_ctr.as<SharedCtr>(), h->sort_keys.as<uint32_t>(), h->sort_idx.as<uint32_t>());
+	HIPCHK(hipEventRecord(h->ev[EV_RESET_DONE], h->stream));
+	HIPCHK(hipStreamWaitEvent(h->sweep_stream, h->ev[EV_RESET_DONE], 0));
+	// (the prefilter stream does not wait for these fills: nothing it runs touches `best` or the shared counters -- the sweeps and the
+	// re-scorer do, on the stream the fills are on -- and the previous batch has been waited for by the host: the prefilter starts
+	// ~75 us earlier)
+	HIPCHK(hipStreamWaitEvent(h->post_stream, h->ev[EV_RESET_DONE], 0));
+	for (uint32_t l = 0; l < b.nl; ++l) if (h->lanes[l]->n_entries) if ((rc = enqueue_lane(h, h->lanes[l], b))) return rc;
+	HIPCHK(hipEventRecord(h->ev[EV_PF_DONE], h->pf_stream));          // this batch's share of the prefilter stream ends here
+	if ((rc = enqueue_grouping_ahead(h, b))) return rc;
+	if (!h->hsc_pinned) HIPCHK(hipHostMalloc((void **)&h->hsc_pinned, sizeof(SharedCtr), hipHostMallocDefault));
+	HIPCHK(hipMemcpyAsync(h->hsc_pinned, h->shared_ctr.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->post_stream));
+	HIPCHK(hipEventRecord(h->ev[EV_CHAIN_DONE], h->post_stream));
+	seed_next_batch(h, b.slot, h->ev[EV_CHAIN_DONE]);
+	if (h->enqueued_hook && attempt == 0) h->enqueued_hook(h->enqueued_ctx);      // the caller's host work for later batches, while the device is busy with this one
+	return BHIP_OK;
+}
+static int wait_chain(Handle *h, const BatchCall &b) {
+	HIPCHK(hipEventSynchronize(h->ev[EV_PF_DONE]));
+	HIPCHK(hipStreamSynchronize(h->sweep_stream));
+	HIPCHK(hipStreamSynchronize(h->post_stream));
+	for (uint32_t l = 0; l < b.nl; ++l) if (h->lanes[l]->n_entries) h->lanes[l]->hc = *h->lanes[l]->hc_pinned;
+	return BHIP_OK;
+}
+// a lane whose records mostly survive the counting filter does better with the exact table
+static void adapt_prefilter_algo(Handle *h, const BatchCall &b) {
+	for (uint32_t l = 0; l < b.nl; ++l) {
+		Lane *L = h->lanes[l];
+		// (with the minimum-only semantics the counting-filter kernel also splits off the lanes that cannot hold a minimum --
+		// the second sweep -- which the exact-table kernel does not: it only takes over when most records survive)
+		// Round 6: measured again with k_prefilter_cq on a database with strain-level redundancy (57 % of the records survive its filter: a read
+		// of a 500-strain family meets the family's clumps in every one of its lists): the exact-table kernel took 61.5 ms per 2 M reads where
+		// k_prefilter_cq takes 8.5 (gpurun_out/r06a, r06b) -- with the minimum-only semantics the switch is off while that kernel is in use
+		const bool cq_min_only = !b.all_hits && h->opt_pf_cw == 2 && L->pf_algo_used == 3;
+		if (L->n_entries && L->pf_algo == 0 && !cq_min_only && L->hc.ent_read > 100000 && (double)L->hc.surv_sum > (b.all_hits ? 0.20 : 0.50) * (double)L->hc.ent_read) L->pf_algo = 1;
+	}
+}
+static void print_chain_counters(const Handle *h, const BatchCall &b) {      // BHIP_DEBUG
+	for (uint32_t l = 0; l < b.nl; ++l) {
+		const Lane *L = h->lanes[l];
+		if (!L->n_entries) continue;
+		fprintf(stderr, "[bhip] lane %u: %llu list records, %llu survived the counting filter, next prefilter algorithm %d\n", l, (unsigned long long)L->hc.ent_read, (unsigned long long)L->hc.surv_sum, L->pf_algo);
+		for (int cls = 0; cls < kNumClasses; ++cls) if (L->npf[cls] + L->nex[cls])
+			fprintf(stderr, "[bhip] lane %u class NW=%d: prefiltered %u exhaustive %u maxE %u maxwords %u | tasks %u + deferred %u (kept %u) clump pairs %u windows %u + %u | fallback queries(last class) %u raw %u\n",
+				l, kClasses[cls], L->npf[cls], L->nex[cls], L->maxE[cls], L->maxwords[cls], L->hc.n_tasks_cls[cls], L->hc.n_tasks2_cls[cls], L->hc.n_tasks2k_cls[cls], L->hc.n_cand_cls[cls], L->hc.n_wins_cls[cls], L->hc.n_wins2_cls[cls], L->hc.n_fb, L->hc.n_raw);
+		if (L->hc.n_fb) fprintf(stderr, "[bhip] lane %u: %u queries overflowed the first prefilter pass, %u the second (dense fallback)\n", l, L->hc.n_fb, L->hc.n_fb2);
+	}
+}
+// capacity checks of the lanes' buffers (first call of a workload: grow and redo)
+static int grow_lane_capacities(Handle *h, const BatchCall &b) {
+	bool redo = false;
+	for (uint32_t l = 0; l < b.nl; ++l) {
+		Lane *L = h->lanes[l];
+		if (!L->n_entries) continue;
+		const Counters &c = L->hc;
+		for (int cls = 0; cls < kNumClasses; ++cls) {
+			redo |= grow_cap(L->cand_cap, c.n_cand_cls[cls], true, (int)l, "cand");
+			redo |= grow_cap(L->task_cap, c.n_tasks_cls[cls], true, (int)l, "tasks");
+			redo |= grow_cap(L->task_cap, c.n_tasks2_cls[cls], true, (int)l, "tasks");
+			redo |= grow_cap(L->win_cap, c.n_wins2_cls[cls], true, (int)l, "wins");
+			redo |= grow_cap(L->win_cap, c.n_wins_cls[cls], true, (int)l, "wins");
+		}
+		redo |= grow_cap(L->raw_cap, c.n_raw, true, (int)l, "raw");
+	}
+	return redo ? STEP_REDO : BHIP_OK;
+}
+// Rare: bands wider than the LDS plan (repeats inside one shear) go through the global-scratch variant of the re-scorer, lane by lane, each
+// waited for.  Then the shared counters as they stand behind the last re-scorer.  Redo: the scratch was too small for a lane's bands.
+static int rescore_wide_bands(Handle *h, BatchCall &b) {
+	bool redo = false;
+	const RefArgs R = ref_args(h);
+	SharedCtr *sc = h->shared_ctr.as<SharedCtr>();
+	for (uint32_t l = 0; l < b.nl; ++l) {
+		Lane *L = h->lanes[l];
+		if (!L->n_entries || !L->hc.n_wide) continue;
+		b.sorted_ahead = false;                  // more records are on their way
+		if (getenv("BHIP_DEBUG")) fprintf(stderr, "[bhip] lane %u: n_wide %u hits through the global-scratch re-scorer\n", l, L->hc.n_wide);
+		Counters *dc = L->counters.as<Counters>();
+		hipLaunchKernelGGL(k_rescore<true>, dim3(std::min<uint32_t>((L->hc.n_wide + 63) / 64, (uint32_t)h->n_cu * 16)), dim3(64), 256, h->post_stream,
+			L->raw.as<BhipRawHit>(), &dc->n_raw, (uint32_t)L->raw_cap, L->wide.as<uint32_t>(), &dc->n_wide, h->best.as<uint32_t>(), b.all_hits,
+			h->cur->qcodes.as<uint8_t>(), h->cur->qoff.as<uint64_t>(), six_or_null(h), rc_or_null(h),
+			R.bytes(), R.off, R.len, h->lut.as<uint8_t>(), h->out.as<BhipHit>(),
+			&sc->n_out, (uint32_t)h->out_cap, (uint32_t *)nullptr, (uint32_t *)nullptr, L->scratch.as<uint32_t>(), &dc->scratch_used,
+			(unsigned long long)L->scratch_cap, &sc->err, (const uint32_t *)nullptr, 0u, 0u, 0u);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(&L->hc, dc, sizeof(Counters), hipMemcpyDeviceToHost, h->post_stream));
+		HIPCHK(hipStreamSynchronize(h->post_stream));
+		redo |= grow_cap(L->scratch_cap, L->hc.scratch_used, false, (int)l, "scratch");
+	}
+	if (b.sorted_ahead) b.hsc = *h->hsc_pinned;      // (nothing ran after the chain: the copy behind it is current)
+	else HIPCHK(hipMemcpy(&b.hsc, h->shared_ctr.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return redo || (b.hsc.err & 2u) ? STEP_REDO : BHIP_OK;
+}
+// the shared error bits and the record buffer; then the number of records is known
+static int check_shared_counters(Handle *h, BatchCall &b) {
+	if (b.hsc.err & 1u) return fail(BHIP_E_RESCORE, "re-scoring could not reproduce a hit found by the edit-distance kernel (a query starting with a symbol outside the alphabet? the reference stops here as well: CRITICAL ERROR: Truncation within known good path, burst.c:812-816)");
+	if (grow_cap(h->out_cap, b.hsc.n_out, true, -1, "out")) return STEP_REDO;
+	b.n_deliver = b.sel_best ? (b.sorted_ahead ? *h->nsel_pinned : std::min<uint32_t>(b.hsc.n_out, b.n_q)) : b.hsc.n_out;      // (not grouped yet: an upper bound; deliver()'s grouping gives the number)
+	*b.n_hits = b.n_deliver;
+	h->last_n_out = 0;
+	return BHIP_OK;
+}
+// statistics of a chain that went through, and the note that its records are resident
+static void collect_stats(Handle *h, const BatchCall &b) {
+	BhipStats &S = h->stats;
+	S.n_queries = b.n_q; S.n_hits = b.n_deliver;
+	uint64_t qlen_sum = 0;
+	for (uint32_t l = 0; l < b.nl; ++l) {
+		Lane *L = h->lanes[l];
+		if (!L->n_entries) continue;
+		const Counters &c = L->hc;
+		S.n_pairs += L->n_pairs_ex + c.unit_sum; S.n_columns += c.col_sum; S.n_task_columns += c.tcol_sum; S.n_raw_hits += c.n_raw; S.acx_entries_read += c.ent_read;
+		S.myers_launches += L->launches; S.prefilter_launches += L->pf_launches; if (L->pf_launches) S.prefilter_algo = (uint32_t)L->pf_algo_used; S.n_window_columns += c.wcol_sum; qlen_sum += c.qlen_sum;
+		if (L->prefix_words) S.prefix_words = L->prefix_words;
+		for (int cls = 0; cls < kNumClasses; ++cls) {
+			S.n_pairs += c.n_cand_cls[cls]; S.n_windows += c.n_wins_cls[cls] + c.n_wins2_cls[cls]; S.n_lane_tasks += c.n_tasks_cls[cls] + c.n_tasks2k_cls[cls];
+			if (!(L->npf[cls] + L->nex[cls])) continue;
+			hipEvent_t *ce = L->ev_cls[cls];
+			S.ms_peq += L->peq_ahead[cls] ? ev_ms(L->ev_peq_cur[SPAN_START], L->ev_peq_cur[SPAN_DONE]) : ev_ms(ce[CE_START], ce[CE_PEQ_DONE]);
+			if (L->npf[cls]) S.ms_prefilter += ev_ms(ce[CE_PF_START], ce[CE_PF_DONE]);
+			if (L->npf[cls] && L->pf_masked[cls]) {
+				hipEvent_t *es = L->ev_seed[h->cur->seq & 1][cls];
+				S.ms_seed += ev_ms(es[SPAN_START], es[SPAN_DONE]); S.ms_prefilter_hash += ev_ms(L->ev_pf[cls][PF_HASH_START], L->ev_pf[cls][PF_HASH_DONE]); S.n_seed_words += L->seed_words[cls];
+			}
+			float sweep = ev_ms(ce[CE_SWEEP_START], ce[CE_SWEEP_EX_DONE]), win = ev_ms(ce[CE_SWEEP_EX_DONE], ce[CE_WIN_DONE]);
+			if (L->pruned[cls]) { const float second = ev_ms(L->ev_ph[cls][PH_WIN_DONE], L->ev_ph[cls][PH_SWEEP2_DONE]); sweep += second; win -= second; }   // filter + second task sweep sit between the two window launches
+			S.ms_myers += sweep + win;
+			if (L->prefix_words) { S.ms_myers_prefix += sweep; S.ms_myers_window += win; }
+		}
+		S.ms_rescore += ev_ms(L->ev_rs[RS_START], L->ev_rs[RS_DONE]);
+	}
+	S.bytes_algorithmic = 8ull * S.n_columns + qlen_sum / 2 + 192ull * S.n_pairs;
+	h->res_valid = true; h->res_seq = b.slot->seq; h->res_all_hits = b.mode; h->res_n = b.n_deliver; h->res_n_raw = b.hsc.n_out; h->res_stats = h->stats;
+}
+// one attempt at the chain: enqueue, wait, check
+static int run_chain(Handle *h, BatchCall &b, int attempt) {
+	int rc;
+	if ((rc = enqueue_chain(h, b, attempt)) || (rc = wait_chain(h, b))) return rc;
+	adapt_prefilter_algo(h, b);
+	if (getenv("BHIP_DEBUG")) print_chain_counters(h, b);
+	if ((rc = grow_lane_capacities(h, b)) || (rc = rescore_wide_bands(h, b)) || (rc = check_shared_counters(h, b))) return rc;
+	collect_stats(h, b);
+	return BHIP_OK;
+}
+
+// The records were not grouped behind the re-scorer (or into the other buffer): count, scan, group on the main stream.  With sel_best the
+// number of selected records is only known afterwards (rare path: records that stayed resident, wide bands).
+static int group_late(Handle *h, BatchCall &b, int o, DBuf &sorted) {
+	int rc;
+	const uint32_t n = b.hsc.n_out, n_q = b.n_q;
+	if (h->copy_pending[o]) { HIPCHK(hipEventSynchronize(h->ev_copied[o])); h->copy_pending[o] = false; }    // the copy that last read this buffer
+	if ((rc = sorted.reserve((size_t)n * sizeof(BhipHit))) || (rc = h->sort_scratch.reserve((size_t)n * sizeof(BhipHit)))) return rc;
+	uint32_t *cnt = h->sort_keys.as<uint32_t>(), *rank = h->sort_idx.as<uint32_t>();
+	HIPCHK(hipMemsetAsync(cnt, 0, (size_t)(n_q + 1) * 4, h->stream));
+	if (b.sel_best) HIPCHK(hipMemsetAsync(h->best_key.p, 0xFF, (size_t)(n_q + 1) * 8, h->stream));
+	b.mark(0);
+	hipLaunchKernelGGL(k_hit_count, dim3(std::min<uint32_t>((n + 255) / 256, (uint32_t)h->n_cu * 8)), dim3(256), 0, h->stream, h->out.as<BhipHit>(), n, (const uint32_t *)nullptr, cnt, rank);
+	if ((rc = plan_scan(h, b, h->stream)) || (rc = enqueue_grouping(h, b, h->stream, n, (const uint32_t *)nullptr, sorted))) return rc;
+	if (b.sel_best) {
+		HIPCHK(hipStreamSynchronize(h->stream));
+		b.n_deliver = *h->nsel_pinned; *b.n_hits = b.n_deliver; h->stats.n_hits = b.n_deliver; h->res_n = b.n_deliver;
+		if (b.hits && b.n_deliver > b.cap) return fail(BHIP_E_CAPACITY, "hit buffer holds %llu records, %u needed", (unsigned long long)b.cap, b.n_deliver);
+	}
+	return BHIP_OK;
+}
+// Page-lock the caller's buffer for the asynchronous copy out of slot o (kept registered: callers alternate between two buffers).
+// ok: the buffer is page-locked -- by this or an earlier call, or by the caller (bhip_alloc_host / bhip_host_register).
+static int lock_caller_buffer(Handle *h, BhipHit *hits, size_t want, size_t bytes, int o, bool &ok) {
+	if (!h->copy_stream) { HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&h->ev_sorted, hipEventDisableTiming));
+		for (auto &e : h->ev_copied) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+	ok = h->reg_ptr[o] == (void *)hits && h->reg_bytes[o] >= bytes;
+	if (!ok) {
+		hipPointerAttribute_t at;
+		memset(&at, 0, sizeof at);
+		if (hipPointerGetAttributes(&at, (const void *)hits) == hipSuccess && at.type == hipMemoryTypeHost) ok = true;
+		else (void)hipGetLastError();
+	}
+	if (!ok) {
+		if (h->reg_ptr[o]) { (void)hipHostUnregister(h->reg_ptr[o]); h->reg_ptr[o] = nullptr; }
+		if (h->reg_ptr[o ^ 1] == (void *)hits) { if (h->copy_pending[o ^ 1]) { HIPCHK(hipEventSynchronize(h->ev_copied[o ^ 1])); h->copy_pending[o ^ 1] = false; }
+			(void)hipHostUnregister(h->reg_ptr[o ^ 1]); h->reg_ptr[o ^ 1] = nullptr; }
+		if (hipHostRegister((void *)hits, want, hipHostRegisterDefault) == hipSuccess) { h->reg_ptr[o] = (void *)hits; h->reg_bytes[o] = want; ok = true; }
+		else (void)hipGetLastError();
+	}
+	return BHIP_OK;
+}
+// Hand the records over: grouped late where they were not grouped ahead, then copied into the caller's buffer -- on the copy stream behind
+// the call (option async_d2h, page-locked buffer) or on the main stream, which is waited for.
+static int deliver(Handle *h, BatchCall &b) {
+	int rc;
+	BhipStats &S = h->stats;
+	if (b.hits && b.n_deliver > b.cap) return fail(BHIP_E_CAPACITY, "hit buffer holds %llu records, %u needed", (unsigned long long)b.cap, b.n_deliver);
+	HIPCHK(hipEventRecord(h->ev[EV_DELIVER_START], h->stream));
+	b.t0 = std::chrono::steady_clock::now();
+	if (b.hsc.n_out) {
+		if ((rc = h->sort_idx.reserve(std::max<size_t>((size_t)b.hsc.n_out, b.sel_best ? (size_t)b.n_q + 1 : 0) * 4)) || (rc = h->sort_keys.reserve((size_t)(b.n_q + 1) * 4)) ||
+		    (rc = h->sort_keys2.reserve((size_t)(b.n_q + 1) * 4))) return rc;
+		const bool async = h->opt_async_d2h && b.hits;
+		const int o = async ? (h->out_idx ^= 1) : 0;
+		DBuf &sorted = o ? h->out_sorted2 : h->out_sorted;
+		if (b.sorted_ahead && o == b.o_ahead) b.mark(0);          // grouped already, behind the re-scorer
+		else if ((rc = group_late(h, b, o, sorted))) return rc;
+		b.mark(1);
+		const size_t bytes = (size_t)b.n_deliver * sizeof(BhipHit);
+		bool queued = false;
+		if (async) {
+			if ((rc = lock_caller_buffer(h, b.hits, (size_t)b.cap * sizeof(BhipHit), bytes, o, queued))) return rc;
+			b.mark(2);
+			if (queued) {
+				HIPCHK(hipEventRecord(h->ev_sorted, h->stream));
+				HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_sorted, 0));
+				HIPCHK(hipMemcpyAsync(b.hits, sorted.p, bytes, hipMemcpyDeviceToHost, h->copy_stream));
+				HIPCHK(hipEventRecord(h->ev_copied[o], h->copy_stream));
+				h->copy_pending[o] = true;
+			}
+		}
+		if (b.hits && !queued) HIPCHK(hipMemcpyAsync(b.hits, sorted.p, bytes, hipMemcpyDeviceToHost, h->stream));
+		h->last_n_out = b.n_deliver; h->last_out = o;
+	}
+	b.mark(3);
+	HIPCHK(hipEventRecord(h->ev[EV_DELIVER_DONE], h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
+	if (getenv("BHIP_DEBUG_TIMES")) {
+		const double *t = b.t_host, t_sync = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b.t0).count() - t[3];
+		fprintf(stderr, "[bhip] delivery host ms: reserve+memset %.3f, sort launches %.3f, pointer check %.3f, copy enqueue %.3f, sync %.3f\n", t[0], t[1] - t[0], t[2] - t[1], t[3] - t[2], t_sync);
+	}
+	S.ms_h2d = h->cur->st_ms_h2d; S.ms_stage_copy = h->cur->st_ms_copy; S.ms_stage_route = h->cur->st_ms_route;
+	S.ms_d2h = ev_ms(h->ev[EV_DELIVER_START], h->ev[EV_DELIVER_DONE]) + (b.sorted_ahead ? ev_ms(h->ev[EV_GROUP_START], h->ev[EV_GROUP_DONE]) : 0.0f); S.ms_total = ev_ms(h->ev[EV_BEGIN], h->ev[EV_DELIVER_DONE]);
+	b.slot->state = 2;
+	h->res_valid = false;
+	return BHIP_OK;
+}
+
+extern "C" int bhip_align_staged(void *handle, int all_hits_arg, BhipHit *hits, uint64_t cap, uint64_t *n_hits) {
+	Handle *h = (Handle *)handle;
+	if (!h || !n_hits) return fail(BHIP_E_ARG, "null argument");
+	*n_hits = 0;
+	if (all_hits_arg < 0 || all_hits_arg > BHIP_HITS_BEST) return fail(BHIP_E_ARG, "all_hits must be 0, 1 or 2 (BHIP_HITS_BEST)");
+	BatchCall b;
+	b.mode = all_hits_arg; b.all_hits = all_hits_arg == BHIP_HITS_ALL ? 1 : 0; b.sel_best = all_hits_arg == BHIP_HITS_BEST;
+	b.hits = hits; b.cap = cap; b.n_hits = n_hits;
+	if (b.sel_best && !h->n_order) return fail(BHIP_E_ARG, "BHIP_HITS_BEST needs the reference order table (bhip_set_ref_order)");
+	memset(&h->stats, 0, sizeof h->stats);
+	HIPCHK(hipSetDevice(h->device));
+	int rc;
+	if ((rc = pick_batch(h, b))) return rc;
+	if (!b.n_q) { b.slot->state = 2; return BHIP_OK; }
+	if ((rc = plan_batch(h, b))) return rc;
+	if (records_resident(h, b)) take_resident(h, b);
+	else {
+		h->res_valid = false;
+		rc = STEP_REDO;
+		for (int attempt = 0; attempt < 24 && rc == STEP_REDO; ++attempt) rc = run_chain(h, b, attempt);
+		if (rc == STEP_REDO) return fail(BHIP_E_INTERNAL, "buffers kept overflowing");
+		if (rc) return rc;
+	}
+	return deliver(h, b);
 }
 
 extern "C" int bhip_align_batch(void *handle, const uint8_t *q_codes, const uint64_t *q_off, const uint16_t *q_emac,
@@ -1110,18 +1246,18 @@ extern "C" int bhip_align_pairs(void *handle, const uint8_t *q_codes, const uint
 	hipLaunchKernelGGL(k_build_peq, dim3((uint32_t)std::min<uint64_t>(((uint64_t)n_q + qb - 1) / qb, (uint64_t)h->n_cu * 16)), dim3(256), 0, st,
 		h->cur->qcodes.as<uint8_t>(), h->cur->qoff.as<uint64_t>(), (const uint32_t *)nullptr, n_q, NW, 0, h->mm, L->peq.as<uint32_t>(), (const uint32_t *)nullptr, 0u, h->peq_rows);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(h->ev[0], st));
+	HIPCHK(hipEventRecord(h->ev[EV_BEGIN], st));
 	launch_myers(h, L, st, NW, (uint32_t)std::min<uint64_t>((n_pairs + 15) / 16, (uint64_t)h->n_cu * 8), h->pairs.as<uint2>(), nullptr, n_pairs, 0, nullptr,
 		nullptr, nullptr, 0, nullptr, h->mins.as<uint8_t>(), dc);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(h->ev[1], st));
+	HIPCHK(hipEventRecord(h->ev[EV_KERNEL_DONE], st));
 	HIPCHK(hipMemcpyAsync(mins, h->mins.p, n_pairs * 16, hipMemcpyDeviceToHost, st));
 	Counters hc;
 	HIPCHK(hipMemcpyAsync(&hc, dc, sizeof hc, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
 	h->stats.n_queries = n_q; h->stats.n_pairs = n_pairs; h->stats.n_columns = hc.col_sum; h->stats.myers_launches = 1;
 	h->stats.bytes_algorithmic = 8ull * hc.col_sum + hc.qlen_sum / 2 + 192ull * n_pairs;
-	h->stats.ms_myers = ev_ms(h->ev[0], h->ev[1]); h->stats.ms_total = h->stats.ms_myers;
+	h->stats.ms_myers = ev_ms(h->ev[EV_BEGIN], h->ev[EV_KERNEL_DONE]); h->stats.ms_total = h->stats.ms_myers;
 	return BHIP_OK;
 }
 
@@ -1143,31 +1279,30 @@ extern "C" int bhip_prefilter(void *handle, const uint8_t *q_codes, const uint64
 		{
 			std::vector<uint32_t> plan(n_q, 1u);
 			for (uint32_t i = 0; i < n_q; ++i) plan[i] = make_seed_plan(q_codes + q_off[i], (uint32_t)(q_off[i + 1] - q_off[i]), q_emac[i], (uint32_t)h->K, h->opt_prefilter_stride, h->alt);
-			if ((rc = upload_plan(h, q_codes, q_off, q_emac, n_q, plan))) return rc;
-	{	// 4-bit packed copy of the queries at a fixed stride (layout used by the seed, profile and re-scoring kernels)
-		const uint32_t qw_g = (h->cur->st_maxlen + 7) / 8;
-		if ((rc = h->cur->qpack.reserve((size_t)n_q * qw_g * 4 + 16))) return rc;
-		const uint64_t total = (uint64_t)n_q * qw_g;
-		if (total) hipLaunchKernelGGL(k_pack_queries, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, (uint64_t)h->n_cu * 16)), dim3(256), 0, h->stream,
-			h->cur->qcodes.as<uint8_t>(), h->cur->qoff.as<uint64_t>(), n_q, qw_g, h->cur->qpack.as<uint32_t>());
-		HIPCHK(hipGetLastError());
-	}
+			if ((rc = upload_plan(h, n_q, plan))) return rc;
+			// 4-bit packed copy of the queries at a fixed stride (layout used by the seed, profile and re-scoring kernels)
+			const uint32_t qw_g = (h->cur->st_maxlen + 7) / 8;
+			if ((rc = h->cur->qpack.reserve((size_t)n_q * qw_g * 4 + 16))) return rc;
+			const uint64_t total = (uint64_t)n_q * qw_g;
+			if (total) hipLaunchKernelGGL(k_pack_queries, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, (uint64_t)h->n_cu * 16)), dim3(256), 0, h->stream,
+				h->cur->qcodes.as<uint8_t>(), h->cur->qoff.as<uint64_t>(), n_q, qw_g, h->cur->qpack.as<uint32_t>());
+			HIPCHK(hipGetLastError());
 		}
 		if ((rc = L->cand.reserve(L->cand_cap * sizeof(uint2)))) return rc;
 		if ((rc = L->candcnt.reserve(L->cand_cap * sizeof(uint32_t)))) return rc;
 		HIPCHK(hipStreamSynchronize(h->stream));
 		HIPCHK(hipMemsetAsync(L->counters.p, 0, sizeof(Counters), L->stream));
 		Counters *dc = L->counters.as<Counters>();
-		HIPCHK(hipEventRecord(h->ev[0], L->stream));
+		HIPCHK(hipEventRecord(h->ev[EV_BEGIN], L->stream));
 		if ((rc = launch_prefilter(h, L, L->stream, nullptr, n_q, L->cand.as<uint2>(), L->candcnt.as<uint32_t>(), (uint32_t)L->cand_cap, false, &dc->n_cand, dc))) return rc;
-		HIPCHK(hipEventRecord(h->ev[1], L->stream));
+		HIPCHK(hipEventRecord(h->ev[EV_KERNEL_DONE], L->stream));
 		Counters hc;
 		HIPCHK(hipMemcpyAsync(&hc, dc, sizeof hc, hipMemcpyDeviceToHost, L->stream));
 		HIPCHK(hipStreamSynchronize(L->stream));
 		if (hc.n_cand > L->cand_cap) { L->cand_cap = (uint64_t)hc.n_cand + 1024; continue; }
 		*n_out = hc.n_cand;
 		memset(&h->stats, 0, sizeof h->stats);
-		h->stats.n_queries = n_q; h->stats.n_pairs = hc.n_cand; h->stats.acx_entries_read = hc.ent_read; h->stats.ms_prefilter = ev_ms(h->ev[0], h->ev[1]);
+		h->stats.n_queries = n_q; h->stats.n_pairs = hc.n_cand; h->stats.acx_entries_read = hc.ent_read; h->stats.ms_prefilter = ev_ms(h->ev[EV_BEGIN], h->ev[EV_KERNEL_DONE]);
 		if (hc.n_cand > cap) return fail(BHIP_E_CAPACITY, "candidate buffer holds %llu, %u needed", (unsigned long long)cap, hc.n_cand);
 		std::vector<uint2> c(hc.n_cand); std::vector<uint32_t> cc(hc.n_cand);
 		if (hc.n_cand) {

@@ -295,16 +295,30 @@ struct StageSlot {
 	}
 };
 
+// Indices of the timing events.  A class's chain (Lane::ev_cls), in the order the device meets them:
+//   CE_START (sweep stream) .. CE_PEQ_DONE: match profiles;  CE_PF_START .. CE_PF_DONE (prefilter stream): prefilter;
+//   CE_SWEEP_START .. CE_SWEEP_PF_DONE: sweep of the prefiltered queries, .. CE_SWEEP_EX_DONE: of the exhaustive ones (sweep stream);
+//   .. CE_WIN_DONE (post stream): window stage, with the second sweep of a pruned class inside
+enum ClassEvent { CE_START, CE_PEQ_DONE, CE_PF_DONE, CE_SWEEP_PF_DONE, CE_SWEEP_EX_DONE, CE_WIN_DONE, CE_SWEEP_START, CE_PF_START, CE_COUNT };
+enum { RS_START, RS_DONE };                            // Lane::ev_rs: the lane's re-scoring (RS_START is also recorded behind every class: the class's window stage is done)
+enum { PH_WIN_DONE, PH_SWEEP2_DONE };                  // Lane::ev_ph: first window stage done, second task sweep done
+enum { PF_SEED_START, PF_HASH_START, PF_HASH_DONE };   // Lane::ev_pf: seed lookup start, hash kernel start, hash kernel done
+enum { SPAN_START, SPAN_DONE };                        // Lane::ev_seed, ev_peq_alt, ev_peq_cur: start and end of one piece of work
+// Handle::ev.  A batch call: EV_BEGIN, EV_RESET_DONE (batch-wide buffers reset), EV_PF_DONE (the call's share of the prefilter stream),
+// EV_CHAIN_DONE (shared counters read back), EV_GROUP_START .. EV_GROUP_DONE (grouping behind the re-scorer), EV_DELIVER_START ..
+// EV_DELIVER_DONE.  The one-kernel entry points (bhip_align_pairs, bhip_prefilter): EV_BEGIN .. EV_KERNEL_DONE.
+enum { EV_BEGIN = 0, EV_RESET_DONE = 1, EV_KERNEL_DONE = 1, EV_PF_DONE = 2, EV_CHAIN_DONE = 3, EV_GROUP_START = 4, EV_GROUP_DONE = 5, EV_DELIVER_START = 8, EV_DELIVER_DONE = 9, EV_COUNT = 10 };
+
 // One independent sub-pipeline of a staged batch: its own stream and scratch, a contiguous range of shared slots
 // (so a forward entry and its reverse-complement twin are always in the same lane and `best[six]` is final when the
 // lane's re-scorer runs).  Lanes overlap each other's latency-bound kernels (prefilter, window, re-scorer) with the
 // VALU-bound column sweep, which itself is serialised on one dedicated stream (Handle::sweep_stream).
 struct Lane {
 	hipStream_t stream = nullptr;
-	hipEvent_t ev_cls[kNumClasses][8];   // per class: 0 start, 1 peq done (sweep stream), 7 prefilter start, 2 prefilter done, 6 sweep start, 3 sweep(pf) done, 4 sweep(ex) done, 5 window done
-	hipEvent_t ev_rs[2];
-	hipEvent_t ev_ph[kNumClasses][2];    // per class: first window sweep done, second task sweep done
-	hipEvent_t ev_pf[kNumClasses][3];    // per class: seed lookup start, hash kernel start, hash kernel done
+	hipEvent_t ev_cls[kNumClasses][CE_COUNT];   // per class: ClassEvent
+	hipEvent_t ev_rs[2];                 // RS_START, RS_DONE
+	hipEvent_t ev_ph[kNumClasses][2];    // per class: PH_WIN_DONE, PH_SWEEP2_DONE
+	hipEvent_t ev_pf[kNumClasses][3];    // per class: PF_SEED_START, PF_HASH_START, PF_HASH_DONE
 	uint64_t seed_words[kNumClasses] = {0};
 	uint32_t pf_launches = 0;
 	bool fb_dirty = false;                 // the clump-level prefilter of an earlier class of this call left its overflow count in the shared counter
@@ -324,7 +338,7 @@ struct Lane {
 	uint64_t seeded_seq[kNumClasses] = {0};
 	uint32_t seeded_n[kNumClasses] = {0}, seeded_W16[kNumClasses] = {0};
 	hipEvent_t ev_seed[2][kNumClasses][2];   // [batch parity][class]: seed lookup start, done
-	// match profiles built ahead for the next staged batch (when it has a single class in this lane): swapped in by enqueue_lane
+	// match profiles built ahead for the next staged batch (when it has a single class in this lane): swapped in by enqueue_class
 	DBuf peq_alt, peqp_alt;
 	bool alt_ok = false; uint64_t alt_seq = 0; int alt_cls = 0, alt_nwp = 0; uint32_t alt_n = 0;
 	hipEvent_t ev_peq_alt[2], ev_peq_cur[2];  // profile build start, done: of the buffers built ahead / of the ones in use
@@ -354,7 +368,7 @@ struct Handle {
 	hipStream_t pf_stream = nullptr;      // peq + prefilter of every lane, in lane order
 	hipStream_t sweep_stream = nullptr;   // every k_myers_prefix / k_myers launch, in lane order
 	hipStream_t post_stream = nullptr;    // window stage + re-scorer + counter read-back, in lane order
-	hipEvent_t ev[10];
+	hipEvent_t ev[EV_COUNT];
 	// database
 	uint32_t n_clumps = 0, tot_refs = 0, max_clump_len = 0;
 	DBuf ref_lane, ref_off, clump_len, lut;           // ref_lane: [clump][lane][32-column chunk][16 B], each lane contiguous inside its clump's area
@@ -384,7 +398,7 @@ struct Handle {
 	// BEST on the device (bhip_align_staged with all_hits = BHIP_HITS_BEST): RefIxSrt per reference, the per-entry minimum key of a batch
 	DBuf ref_order, best_key; uint32_t n_order = 0;
 	uint32_t *nsel_pinned = nullptr;      // read-back of the number of selected records
-	bool res_sel = false; uint32_t res_n_raw = 0;      // the resident records of a batch that did not fit the caller's buffer: selected? how many before the selection?
+	uint32_t res_n_raw = 0;               // ... how many before the selection of one per entry (BHIP_HITS_BEST)
 	SharedCtr *hsc_pinned = nullptr;      // read-back of shared_ctr behind the chain (pinned: no blocking copy on the way out of a batch)
 	const uint8_t *s_codes() const { return cur->st_has_junk ? cur->qcodes_s.as<uint8_t>() : cur->qcodes.as<uint8_t>(); }
 	const uint64_t *s_off() const { return cur->st_has_junk ? cur->qoff_s.as<uint64_t>() : cur->qoff.as<uint64_t>(); }

@@ -844,3 +844,145 @@ def test_first_symbol_outside_the_alphabet_stops_like_the_reference():
         dev.align_batch(q, all_hits=False)
     assert e.value.code == capi.BHIP_E_RESCORE
     dev.close()
+
+
+# ---- the redo paths of a batch call (bhip_align_staged): a chain that outgrows its buffers is run again, bands beyond the LDS plan go
+# through the global-scratch re-scorer.  The library says so under BHIP_DEBUG ("[bhip] redo: ...", "... n_wide N hits ...") ----
+def staged_call(dev, mode, buf):
+    """ONE bhip_align_staged call on the staged batch, no retry on the caller's side: (return code, record count)"""
+    from burst_amd import capi
+    n = capi.C.c_uint64()
+    rc = capi.lib().bhip_align_staged(dev._h, mode, capi._ptr(buf), len(buf), capi.C.byref(n))
+    return rc, int(n.value)
+
+
+def with_debug_lines(capfd, monkeypatch, fn):
+    """fn() under BHIP_DEBUG: (its result, the library's debug lines)"""
+    monkeypatch.setenv("BHIP_DEBUG", "1")
+    capfd.readouterr()
+    try:
+        res = fn()
+    finally:
+        err = capfd.readouterr().err
+        monkeypatch.delenv("BHIP_DEBUG")
+    return res, [ln for ln in err.splitlines() if ln.startswith("[bhip]")]
+
+
+def redo_inputs(n_reads=17000):
+    """64 references within one substitution of one 300-symbol sequence (4 clumps), reads of 100 symbols cut from it with 0 - 1 edits and
+    a budget of 3: every reference is a hit for every read -- 64 x 17 000 = 1 088 000 raw hits and records"""
+    rng = np.random.default_rng(4101)
+    base = rng.integers(1, 5, size=300, dtype=np.uint8)
+    seqs = []
+    for i in range(64):
+        v = base.copy()
+        if i:
+            p = int(rng.integers(0, len(v)))
+            v[p] = v[p] % 4 + 1
+        seqs.append(v)
+    reads, _ = synth.make_reads([base], n_reads, 100, [0, 1], 4102)
+    return seqs, reads
+
+
+def wide_band_inputs(rep=150):
+    """A read of "AC" x rep with ONE substitution in the middle (without it every alignment to a repeat is an exact match, and exact matches
+    leave in k_rescore_classify: nothing would be re-scored), the plain repeat beside it, and ordinary 100-symbol reads; 24 references of
+    600 symbols, every third one "AC" x 300, the others random.  The substituted read meets a repeat with one edit at every second end
+    column over hundreds of columns: a band of > 48 (BHIP_RESCORE_WMAX) diagonals."""
+    rng = np.random.default_rng(4201)
+    ac = np.tile(np.array([1, 2], np.uint8), 300)
+    seqs = [ac.copy() if i % 3 == 0 else rng.integers(1, 5, size=600, dtype=np.uint8) for i in range(24)]
+    plain = np.tile(np.array([1, 2], np.uint8), rep)
+    edited = plain.copy()
+    edited[rep] = 3
+    ordinary, _ = synth.make_reads([s for i, s in enumerate(seqs) if i % 3], 14, 100, [0, 1, 2, 3], 4202)
+    return seqs, ordinary[:7] + [edited, plain] + ordinary[7:]
+
+
+def test_chain_redone_for_size_gives_the_same_records(capfd, monkeypatch):
+    """Exhaustive route, all hits: 1 088 000 raw hits against Lane::raw_cap = 2^18 and as many records against Handle::out_cap = 2^20, so
+    the first call runs the chain three times (raw grows, then out).  The redo changes nothing: the second call on the same handle redoes
+    nothing and returns the same bytes, so does a fresh handle that gets the reads in eight batches below every limit, and the first
+    100 reads' records are the oracle's.  A caller's buffer one record too small gets BHIP_E_CAPACITY and the count; the next call
+    delivers the resident records without running the chain."""
+    from burst_amd import capi
+    seqs, reads = redo_inputs()
+    n_r = len(reads)
+    packed, clump_len, tot = dbutil.pack_clumps(seqs)
+    lut = ol.score_lut(1)
+    E = [budget(0.97, 100)] * n_r
+    assert E[0] == 3
+    q = capi.Queries(reads, E, list(range(n_r)), [0] * n_r)
+    dev = capi.Device(packed, clump_len, tot, lut)
+    dev.stage(q)
+    buf = np.zeros(64 * n_r + 16, dtype=capi.HIT_DTYPE)
+    (rc, n), lines = with_debug_lines(capfd, monkeypatch, lambda: staged_call(dev, 1, buf))
+    redo = [ln for ln in lines if "redo:" in ln]
+    print("first call: rc", rc, "records", n, redo)
+    assert rc == capi.BHIP_OK and n > 2 ** 20
+    assert any(" raw " in ln for ln in redo) and any(" out " in ln for ln in redo), lines
+    first = buf[:n].copy()
+    # the same batch again: every buffer is large enough now
+    buf[:] = 0
+    (rc, n2), lines = with_debug_lines(capfd, monkeypatch, lambda: staged_call(dev, 1, buf))
+    assert rc == capi.BHIP_OK and n2 == n and not [ln for ln in lines if "redo:" in ln], lines
+    assert any("list records" in ln for ln in lines)                     # (the chain did run)
+    assert buf[:n].tobytes() == first.tobytes()
+    # a caller's buffer one record too small, then one that is large enough: the resident records, no chain
+    small = np.zeros(n - 1, dtype=capi.HIT_DTYPE)
+    rc, n3 = staged_call(dev, 1, small)
+    assert rc == capi.BHIP_E_CAPACITY and n3 == n
+    buf[:] = 0
+    (rc, n4), lines = with_debug_lines(capfd, monkeypatch, lambda: staged_call(dev, 1, buf))
+    assert rc == capi.BHIP_OK and n4 == n and not [ln for ln in lines if "redo:" in ln or "list records" in ln], lines
+    assert buf[:n].tobytes() == first.tobytes()
+    dev.close()
+    # the first 100 reads against the oracle
+    q100 = capi.Queries(reads[:100], E[:100], list(range(100)), [0] * 100)
+    exp = oracle_hits(packed, clump_len, tot, q100, lut, True)
+    assert len(exp) == 6400
+    assert_hits_equal(first[first["q"] < 100], exp)
+    # a fresh handle, eight batches none of which reaches a limit
+    dev = capi.Device(packed, clump_len, tot, lut)
+    parts = []
+    step = n_r // 8
+    assert step * 8 == n_r
+
+    def eight():
+        for k in range(8):
+            qk = capi.Queries(reads[k * step:(k + 1) * step], E[:step], list(range(step)), [0] * step)
+            got = dev.align_batch(qk, all_hits=True, cap=64 * step + 16)
+            got["q"] += k * step
+            parts.append(got)
+    _, lines = with_debug_lines(capfd, monkeypatch, eight)
+    assert not [ln for ln in lines if "redo:" in ln], lines
+    assert np.concatenate(parts).tobytes() == first.tobytes()
+    dev.close()
+
+
+@pytest.mark.parametrize("all_hits", [False, True])
+def test_bands_beyond_the_lds_plan_are_rescored_through_global_scratch(all_hits, capfd, monkeypatch):
+    """k_rescore<true>: the hits of wide_band_inputs() (repeat length used: "AC" x 150, with one substitution) have bands of hundreds of
+    diagonals and leave the LDS plan of at most BHIP_RESCORE_WMAX = 48; ordinary reads run their narrow bands in the same batch.  Records
+    against the oracle, the path taken from the library's debug line."""
+    from burst_amd import capi
+    seqs, reads = wide_band_inputs()
+    packed, clump_len, tot = dbutil.pack_clumps(seqs)
+    lut = ol.score_lut(1)
+    q = capi.Queries(reads, [budget(0.97, len(r)) for r in reads], list(range(len(reads))), [0] * len(reads))
+    exp = oracle_hits(packed, clump_len, tot, q, lut, all_hits)
+    assert (exp["q"] == 7).sum() == 8 and (exp["ed"][exp["q"] == 7] == 1).all()       # the edited repeat: one edit against each of the 8 repeats
+    assert (exp["q"] == 8).sum() == 8 and len(set(exp["q"].tolist())) > 10
+    dev = capi.Device(packed, clump_len, tot, lut)
+    dev.stage(q)
+    buf = np.zeros(1 << 12, dtype=capi.HIT_DTYPE)
+    (rc, n), lines = with_debug_lines(capfd, monkeypatch, lambda: staged_call(dev, int(all_hits), buf))
+    wide = [int(ln.split("n_wide ")[1].split()[0]) for ln in lines if "n_wide " in ln]
+    print("n_wide", wide, [ln for ln in lines if "redo:" in ln])
+    assert rc == capi.BHIP_OK and wide and wide[0] > 0, lines
+    assert_hits_equal(buf[:n].copy(), exp)
+    buf[:] = 0
+    (rc, n2), lines = with_debug_lines(capfd, monkeypatch, lambda: staged_call(dev, int(all_hits), buf))
+    assert rc == capi.BHIP_OK and not [ln for ln in lines if "redo:" in ln], lines
+    assert_hits_equal(buf[:n2].copy(), exp)
+    dev.close()
