@@ -46,7 +46,12 @@ class BhipQuerySpan(C.Structure):
 EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_batch", "bhip_align_pairs", "bhip_prefilter", "bhip_set_option", "bhip_get_stats",
            "bhip_device_info", "bhip_destroy", "bhip_last_error", "bhip_abi_version", "bhip_set_ref_order", "bhip_copy_hits_device", "bhip_sync_hits",
            "bhip_comm_create", "bhip_comm_unique_id", "bhip_comm_create_rank", "bhip_comm_allreduce_min", "bhip_comm_fetch_gathered", "bhip_comm_gather_hits", "bhip_comm_stage_device", "bhip_comm_gather_staged", "bhip_comm_stage_reset", "bhip_comm_destroy", "bhip_acx_export", "bhip_reserve", "bhip_reserve_symbols", "bhip_sort_queries", "bhip_stage_spans", "bhip_alloc_host", "bhip_free_host", "bhip_host_register", "bhip_host_unregister", "bhip_set_enqueued_hook", "bhip_acx_export_entries",
-           "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks"]
+           "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
+           "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents"]
+
+# BhipCovLine, 16 bytes: header, .b6 columns 9 and 10, weight (bits 0..30) | unique << 31
+COV_LINE_DTYPE = np.dtype([("ref", "<u4"), ("st", "<u4"), ("ed", "<u4"), ("w", "<u4")])
+assert COV_LINE_DTYPE.itemsize == 16
 
 
 class BurstHipError(RuntimeError):
@@ -133,6 +138,15 @@ def _load():
     lib.bhip_team_destroy.restype = None
     lib.bhip_device_copy.argtypes = [vp, vp, u64, i32]
     lib.bhip_device_copy.restype = i32
+    lib.bhip_cov_begin.argtypes = [vp, u32, vp, u32]
+    lib.bhip_cov_add.argtypes = [vp, u32, vp, u64]
+    lib.bhip_cov_sample_stats.argtypes = [vp, u32, vp, vp]
+    lib.bhip_cov_dataset_stats.argtypes = [vp, vp, vp]
+    lib.bhip_cov_info.argtypes = [vp, vp]
+    lib.bhip_cov_end.argtypes = [vp]
+    lib.bhip_lane_extents.argtypes = [vp, vp]
+    for f in (lib.bhip_cov_begin, lib.bhip_cov_add, lib.bhip_cov_sample_stats, lib.bhip_cov_dataset_stats, lib.bhip_cov_info, lib.bhip_cov_end, lib.bhip_lane_extents):
+        f.restype = i32
     return lib
 
 
@@ -318,6 +332,40 @@ class Device:
         n = C.c_uint64()
         _chk(lib().bhip_copy_hits_device(self._h, C.c_void_p(int(dst_ptr)), int(cap_records), C.byref(n)))
         return int(n.value)
+
+    def lane_extents(self):
+        """index after the last non-pad symbol of every lane of the resident database, [16 * clump + lane] (bhip_lane_extents)"""
+        ext = np.zeros(16 * self.n_clumps, np.uint32)
+        _chk(lib().bhip_lane_extents(self._h, _ptr(ext)))
+        return ext
+
+    def cov_begin(self, lengths, pad=0):
+        """coverage over len(lengths) reference headers (bhip_cov_begin); cov_add() one whole sample at a time"""
+        lengths = _arr(lengths, np.uint32)
+        self._cov_n = len(lengths)
+        _chk(lib().bhip_cov_begin(self._h, len(lengths), _ptr(lengths), int(pad)))
+
+    def cov_add(self, sample, lines):
+        """lines: COV_LINE_DTYPE array (ref, st, ed, w = weight | unique << 31)"""
+        lines = np.ascontiguousarray(lines, dtype=COV_LINE_DTYPE)
+        _chk(lib().bhip_cov_add(self._h, int(sample), _ptr(lines), len(lines)))
+
+    def cov_stats(self, sample=None):
+        """(shared, unique), each uint64 [headers][4] = tot, cov, sq, lines; sample=None: the Dataset column"""
+        sh, un = np.zeros((self._cov_n, 4), np.uint64), np.zeros((self._cov_n, 4), np.uint64)
+        if sample is None:
+            _chk(lib().bhip_cov_dataset_stats(self._h, _ptr(sh), _ptr(un)))
+        else:
+            _chk(lib().bhip_cov_sample_stats(self._h, int(sample), _ptr(sh), _ptr(un)))
+        return sh, un
+
+    def cov_info(self):
+        info = np.zeros(8, np.uint64)
+        _chk(lib().bhip_cov_info(self._h, _ptr(info)))
+        return dict(zip(("events", "peak_bytes", "compactions", "cap_bytes", "us_last", "events_per_block", "us_total", "samples"), (int(x) for x in info)))
+
+    def cov_end(self):
+        _chk(lib().bhip_cov_end(self._h))
 
     def align_pairs(self, q, pair_q, pair_clump):
         pair_q = _arr(pair_q, np.uint32)

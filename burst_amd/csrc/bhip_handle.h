@@ -444,6 +444,8 @@ struct Handle {
 	int opt_seed_min_need = -1;   // the longest lists of a query's sampled words are left out while its guaranteed count stays >= this (0 = keep every list, -1 = 3 when the rule of seed_min_need_for says it pays)
 	int opt_seed_drop_len = 8;    // ... lists shorter than this are always kept (leaving them out saves nothing and costs selectivity)
 	double acx_wmean = 0.0;       // occurrence-weighted mean .acx list length
+	void *cov = nullptr;          // coverage state between bhip_cov_begin and bhip_cov_end (bhip_cov.hip)
+	long long opt_cov_event_cap = 0;   // bytes the coverage event sets may take before they are compacted (0 = a fifth of the memory free at the first bhip_cov_add)
 };
 
 static inline float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; (void)hipEventElapsedTime(&ms, a, b); return ms; }
@@ -457,4 +459,5 @@ void apply_slot(Handle *h, StageSlot *S);
 void lane_capacity_floor(Handle *h, Lane *L, uint64_t n);
 int  bhip_load_accelerator(Handle *h, const uint32_t *acx_lens, const void *acx_lists, int acx_fmt, int K, const uint32_t *badlist, uint32_t n_bad);   // bhip_acx.hip
 int  bhip_build_accelerator(Handle *h, int K, int z);
+void bhip_cov_release(Handle *h);                                            // bhip_cov.hip
 #endif

@@ -70,6 +70,7 @@ extern "C" void bhip_destroy(void *handle) {
 	if (h->post_stream) (void)hipStreamSynchronize(h->post_stream);
 	if (h->stage_stream) (void)hipStreamSynchronize(h->stage_stream);
 	for (StageSlot &S : h->slots) S.release_all();
+	bhip_cov_release(h);
 	if (h->hsc_pinned) (void)hipHostFree(h->hsc_pinned);
 	if (h->nsel_pinned) (void)hipHostFree(h->nsel_pinned);
 	for (Lane *L : h->lanes) lane_destroy(L);
@@ -241,6 +242,7 @@ extern "C" int bhip_set_option(void *handle, const char *name, long long value) 
 	if (!strcmp(name, "prefilter_cw")) { if (value < 0 || value > 2) return fail(BHIP_E_ARG, "prefilter_cw must be 0, 1 or 2"); h->opt_pf_cw = (int)value; return BHIP_OK; }
 	if (!strcmp(name, "prefilter_bytes")) { h->opt_pf_bytes = value != 0; return BHIP_OK; }
 	if (!strcmp(name, "prefilter_rb")) { if (value != 0 && (value < 2 || value > 4)) return fail(BHIP_E_ARG, "prefilter_rb must be 0, 2, 3 or 4"); h->opt_pf_rb = (int)value; return BHIP_OK; }
+	if (!strcmp(name, "cov_event_cap")) { if (value < 0) return fail(BHIP_E_ARG, "cov_event_cap must be >= 0 bytes (0 = a fifth of the free memory)"); h->opt_cov_event_cap = value; return BHIP_OK; }
 	if (!strcmp(name, "lanes")) {
 		if (value < 1 || value > BHIP_MAX_LANES) return fail(BHIP_E_ARG, "lanes must be 1 .. %d", BHIP_MAX_LANES);
 		h->opt_lanes = (int)value; for (StageSlot &S : h->slots) { S.state = 0; S.st_valid = false; } return BHIP_OK;

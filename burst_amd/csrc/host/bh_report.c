@@ -135,6 +135,41 @@ int bh_report_tax(FILE *out, const BhDb *db, const BhQueries *Q, const BhipHit *
  * walks the runs. */
 int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx,
                    uint64_t *nLines) {
+	return bh_report_view_sink(out, db, Q, view, mode, flags, tx, nLines, NULL);
+}
+/* one placement into a chunk's sink buffer (0 = no memory) */
+static inline int pl_push(BhPlaceSink *b, uint32_t ref, uint32_t st, uint32_t ed, uint32_t w) {
+	if (b->n == b->cap) {
+		const uint64_t nc = b->cap ? b->cap * 2 : 1024;
+		BhipCovLine *np = realloc(b->lines, nc * sizeof(*np));
+		if (!np) return 0;
+		b->lines = np; b->cap = nc;
+	}
+	const BhipCovLine l = {ref, st, ed, w};
+	b->lines[b->n++] = l;
+	return 1;
+}
+/* a rendered chunk's placements behind those of the chunks before it; the chunk's buffer is released */
+static int pl_append(BhPlaceSink *sink, BhPlaceSink *b) {
+	int ok = 1;
+	if (b->n) {
+		if (sink->n + b->n > sink->cap) {
+			uint64_t nc = sink->cap ? sink->cap * 2 : 4096;
+			while (nc < sink->n + b->n) nc *= 2;
+			BhipCovLine *np = realloc(sink->lines, nc * sizeof(*np));
+			if (np) { sink->lines = np; sink->cap = nc; } else ok = 0;
+		}
+		if (ok) { memcpy(sink->lines + sink->n, b->lines, b->n * sizeof(*b->lines)); sink->n += b->n; }
+	}
+	free(b->lines); b->lines = NULL; b->n = b->cap = 0;
+	return ok;
+}
+/* The same with an optional placement sink: for every line printed, (header of column 2, column 9, column 10, unique flag), the lines a
+ * unique query's reads print for one placement folded into one entry whose weight is the number of those reads.  The chunks are
+ * rendered by a team: every chunk fills a buffer of its own and the buffers are concatenated in chunk order, as the text is.
+ * sink == NULL is bh_report_view. */
+int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx,
+                        uint64_t *nLines, BhPlaceSink *sink) {
 	const BhipHit *hits = view->base;
 	const uint64_t nU = Q->numUniq, nE = Q->numEntries;
 	FILE *const real_out = out;
@@ -245,7 +280,11 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 	const double t_pre = omp_get_wtime();
 	const uint64_t CH = chunkQ, nChunks = (nU + CH - 1) / CH, chunkGroup = (uint64_t)nThreads * 8;
 	LineBuf *cbuf = calloc(nChunks + 1, sizeof(*cbuf)); uint64_t *coff = calloc(nChunks + 2, sizeof(*coff));
-	if (!cbuf || !coff) { free(cbuf); free(coff); free(start); free(count); free(RefCounts); return bh_set_error(BH_E_OOM, "OOM:report"); }
+	BhPlaceSink *pbuf = sink ? calloc(nChunks + 1, sizeof(*pbuf)) : NULL;
+	if (!cbuf || !coff || (sink && !pbuf)) { free(cbuf); free(coff); free(pbuf); free(start); free(count); free(RefCounts); return bh_set_error(BH_E_OOM, "OOM:report"); }
+	if (sink) sink->n = 0;
+	/* header of a placement: the unique-header number of the .edx (RefMap), which direct-FASTA runs keep as well */
+	#define SINK(rix, st, ed, reads, uniq) do { if (sink && (reads) && !pl_push(&pbuf[ch], db->refMap ? db->refMap[rix] : (rix), st, ed, (uint32_t)(reads) | ((uniq) ? 0x80000000u : 0u))) out->oom = 1; } while (0)
 	/* the rendered chunks of a group are written side by side at their offsets (pwrite) when the output is a seekable file: one
 	 * thread copying gigabytes into the page cache was the other half of the report's time */
 	fflush(real_out);
@@ -320,6 +359,7 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 				const uint64_t i = bi[k]; const uint32_t qlen = Q->len[i];
 				uint32_t st, ed; coords(db, bb[k], brix[k], qlen, &st, &ed);
 				for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[brix[k]], bb[k], qlen, st, ed, i, 0, NULL); ++lines; }
+				SINK(brix[k], st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 			}
 		}
 	} else
@@ -350,6 +390,7 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 				} else FinalTaxon = tt;
 			}
 			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[rix], best, qlen, st, ed, i, wt, FinalTaxon); ++lines; }
+			SINK(rix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 		} else if (mode == BH_ANY) {                                         /* any valid hit; column 12 = duplicate flag (burst.c:4268-4272) */
 			/* The reference prints the first hit within budget a thread meets and marks the query spent (burst.c:4239-4275, 4457-4475).
 			 * Exhaustive path, one thread: clumps ascending, the entries of a clump in sorted order, lanes ascending -- the LAST
@@ -360,6 +401,7 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 			const uint32_t rix = db->refIxSrt[rp->refIx];
 			uint32_t st, ed; coords(db, rp, rix, qlen, &st, &ed);
 			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line(out, Q->heads[j], db->refHead[rix], rp, qlen, st, ed, j > Q->offset[i]); ++lines; }
+			SINK(rix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 		} else if (mode == BH_ALLPATHS || mode == BH_FORAGE) {               /* burst.c:4582-4640, 4642-4692 */
 			uint32_t b = 0;
 			if (mode == BH_ALLPATHS) {
@@ -379,6 +421,10 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 				const BhipHit *rp = RPcache[zz]; const uint32_t rix = RIXcache[zz];
 				uint32_t st, ed; coords(db, rp, rix, qlen, &st, &ed);
 				print_line_tax(out, Q->heads[j], db->refHead[rix], rp, qlen, st, ed, i, wt, wt ? bh_tax_lookup(T, db->refHead[rix], ncbi) : NULL); ++lines;   /* burst.c:4631-4633, 4685-4687 */
+			}
+			if (sink) for (uint64_t zz = 0; zz < rix_ix; ++zz) {      /* a read with one placement only is on one line of the file */
+				uint32_t st, ed; coords(db, RPcache[zz], RIXcache[zz], qlen, &st, &ed);
+				SINK(RIXcache[zz], st, ed, Q->offset[i + 1] - Q->offset[i], rix_ix == 1);
 			}
 		} else {                                                             /* CAPITALIST pass B (burst.c:4746-4779, 4831-4843) */
 			uint32_t b = 0;
@@ -447,6 +493,7 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 			}
 			uint32_t st, ed; coords(db, best, bestrix, qlen, &st, &ed);
 			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[bestrix], best, qlen, st, ed, i, wt, Final); ++lines; }
+			SINK(bestrix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 		}
 	}
 	if (out->oom) {
@@ -463,6 +510,10 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 			for (uint64_t ch = cg0; ch < cg1; ++ch) {
 				if (!oom && cbuf[ch].len && fwrite(cbuf[ch].p, 1, cbuf[ch].len, real_out) != cbuf[ch].len) wr = 1;
 				free(cbuf[ch].p); cbuf[ch].p = NULL;
+				if (sink && !pl_append(sink, &pbuf[ch])) {
+					#pragma omp atomic write
+					oom = 1;
+				}
 			}
 			t_write += omp_get_wtime() - tg0;
 		}
@@ -473,6 +524,10 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 		t_render += omp_get_wtime() - tg0;
 		coff[cg0] = 0;
 		for (uint64_t ch = cg0; ch < cg1; ++ch) coff[ch + 1] = coff[ch] + cbuf[ch].len;      /* chunks in query order */
+		if (sink) for (uint64_t ch = cg0; ch < cg1; ++ch) if (!pl_append(sink, &pbuf[ch])) {
+			#pragma omp atomic write
+			oom = 1;
+		}
 	}
 	if (use_pwrite == 2) {      /* the group's range of the file mapped: the threads copy their chunks into the page cache side by side */
 		#pragma omp single
@@ -519,7 +574,8 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 	if (dbg) fprintf(stderr, "[bh_report] %lu lines: tables %.3f s, rendering %.3f s, writing %.3f s (%d threads, %s)\n", (unsigned long)lines, t_pre - t_begin, t_render, t_write - t_render, nThreads, use_pwrite == 2 ? "shared mapping" : use_pwrite ? "pwrite" : "fwrite");
 	if (map_fd >= 0) close(map_fd);
 	if (use_pwrite && lseek(out_fd, file_pos, SEEK_SET) == (off_t)-1) wr = 1;      /* the stream continues behind what was written */
-	free(cbuf); free(coff);
+	#undef SINK
+	free(cbuf); free(coff); free(pbuf);
 	free(start); free(count); free(RefCounts);
 	if (oom) return bh_set_error(BH_E_OOM, "OOM:report");
 	if (wr) return bh_set_error(BH_E_IO, "short write on the output file");

@@ -34,6 +34,8 @@ struct BhSession {
 	BhRun block, all;
 	SessIngest *cur, *ahead; pthread_t th; char *pending;
 	FILE *out; char *out_path;
+	char *cov_name;                 /* with a coverage: the output the loaded sample was given (names its column, also when the sample fails) */
+	BhPlaceSink sink;               /* the report's placements of the current sample (buffer kept across samples) */
 	int dead, dbg, threads_ok;
 	int alive;                      /* query tables alive (the current sample's and the prefetched one's) */
 	pthread_mutex_t mu;             /* `alive` and its debug line */
@@ -101,6 +103,7 @@ int bh_session_open(const BhDb *db, BhMultiRank *ranks, int n_local, int n_ranks
 
 int bh_session_ended(const BhSession *s) { return s ? s->dead : 0; }
 void bh_session_set_node(BhSession *s, BhNode *node) { if (s) s->node = node; }
+void bh_session_set_coverage(BhSession *s, BhCov *cov) { if (s) s->o.cov = cov; }
 const BhQueries *bh_session_sample(const BhSession *s) { return s && s->cur ? &s->cur->Q : NULL; }
 
 int bh_session_prefetch(BhSession *s, const char *queries) {
@@ -125,6 +128,11 @@ static int sample_fail_ex(BhSession *s, BhSampleResult *res, int rc, const char 
 	/* usage and I/O errors are the sample's own; anything else (memory, device, internal) ends the session: nothing more is
 	 * started on a device after a device error */
 	if (fatal || (rc != BH_E_USAGE && rc != BH_E_IO)) s->dead = rc;
+	if (s->o.cov && s->i0 >= 0) {      /* a sample that fails alone is an all-zero column; a run that ends here writes no tables */
+		if (s->dead) bh_cov_abort(s->o.cov);
+		else if (s->cov_name) (void)bh_cov_sample_failed(s->o.cov, s->cov_name);
+	}
+	free(s->cov_name); s->cov_name = NULL;
 	return bh_set_error(rc, "%s", res->err);
 }
 static int sample_fail(BhSession *s, BhSampleResult *res, int rc, const char *msg) { return sample_fail_ex(s, res, rc, msg, 0); }
@@ -137,6 +145,8 @@ int bh_session_load(BhSession *s, const char *queries, const char *out_path, BhS
 	if (s->dead) { res->rc = s->dead; snprintf(res->err, sizeof res->err, "the session was ended by an earlier error (code %d)", s->dead); return bh_set_error(s->dead, "%s", res->err); }
 	if (s->cur) return bh_set_error(BH_E_USAGE, "bh_session_load: the previous sample has not been finished or dropped");
 	s->tLoad = wall();
+	free(s->cov_name); s->cov_name = NULL;
+	if (s->o.cov && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
 	SessIngest *g = NULL;
 	/* the outstanding ingest is this sample's: take it.  If it is another one's (prefetched before this sample was named) it stays
 	 * outstanding and this sample is read here */
@@ -174,10 +184,17 @@ int bh_session_load(BhSession *s, const char *queries, const char *out_path, BhS
 	return BH_OK;
 }
 
-int bh_session_drop(BhSession *s) {
-	if (!s) return BH_OK;
+static void drop_sample(BhSession *s) {
 	close_output(s, 0);
 	if (s->cur) { ingest_free(s->cur); s->cur = NULL; }
+	free(s->cov_name); s->cov_name = NULL;
+}
+int bh_session_drop(BhSession *s) {
+	if (!s) return BH_OK;
+	/* a loaded sample that is given up (another rank could not have it) is a failed sample to the coverage: an all-zero column under
+	 * its name, so that the later samples keep their columns */
+	if (s->o.cov && s->cur && s->cov_name && !s->dead) (void)bh_cov_sample_failed(s->o.cov, s->cov_name);
+	drop_sample(s);
 	return BH_OK;
 }
 
@@ -282,7 +299,7 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		const double tr = wall();
 		uint64_t lines = 0;
 		setvbuf(s->out, NULL, _IOFBF, 1 << 22);
-		rc = bh_report_view(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines);
+		rc = bh_report_view_sink(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov ? &s->sink : NULL);
 		if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
 		FILE *f = s->out; s->out = NULL;
 		if (fclose(f)) { char msg[512]; snprintf(msg, sizeof msg, "ERROR: write failed: %s", s->out_path); return sample_fail(s, res, BH_E_IO, msg); }      /* (a full disk must not end in success) */
@@ -290,6 +307,13 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		res->nLines = lines; res->secReport = wall() - tr;
 		if (o->verbose) printf("Wrote %lu alignments\n", (unsigned long)lines);
 		PHASE("consolidation, output");
+		if (o->cov) {      /* the sample's column: its placements to rank 0's device (no collective: the lines exist only here) */
+			rc = S > 1 ? bh_cov_lengths_host(o->cov) : BH_OK;      /* (database-sharded: rank 0's handle holds a slice, the default lengths come from host memory) */
+			if (!rc) rc = bh_cov_sample(o->cov, R[s->i0].hh, s->cov_name, s->sink.lines, s->sink.n);
+			free(s->cov_name); s->cov_name = NULL;      /* (the column exists: a failure below must not add another) */
+			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
+			PHASE("coverage of the sample");
+		}
 	}
 	#undef PHASE
 	ingest_free(s->cur); s->cur = NULL;      /* the sample's tables and page-lockings; the record buffers stay */
@@ -304,11 +328,12 @@ int bh_session_run(BhSession *s, const char *queries, const char *out_path, BhSa
 void bh_session_close(BhSession *s) {
 	if (!s) return;
 	if (s->ahead) { pthread_join(s->th, NULL); ingest_free(s->ahead); s->ahead = NULL; }
-	bh_session_drop(s);
+	drop_sample(s);      /* (not bh_session_drop: the coverage object may be gone by now) */
 	free(s->pending);
 	/* the ranks' runs belong to the caller (BhMultiRank.run); slices of the session's block must not outlive it */
 	for (int i = 0; i < s->n_local; ++i) if (s->block.hits && s->ranks[i].run.hitsPinned == 2 && s->ranks[i].run.hits >= s->block.hits && s->ranks[i].run.hits < s->block.hits + s->block.capHits) memset(&s->ranks[i].run, 0, sizeof s->ranks[i].run);
 	bh_run_free(&s->block); bh_run_free(&s->all);
+	free(s->sink.lines); free(s->cov_name);
 	pthread_mutex_destroy(&s->mu);
 	free(s);
 }

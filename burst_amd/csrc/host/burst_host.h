@@ -263,6 +263,48 @@ int  bh_report_tax(FILE *out, const BhDb *db, const BhQueries *q, const BhipHit 
 /* the same over records that lie in several runs (the records of an entry inside one run, contiguous) */
 int  bh_report_view(FILE *out, const BhDb *db, const BhQueries *q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx, uint64_t *nLines);
 
+/* the same with a placement sink (bh_report.c): sink->lines (malloc'd, the caller's to free; may be handed in again) holds, in the order
+ * of the file, one entry per (unique query, placement): header number (RefMap of the reference of column 2), columns 9 and 10, and
+ * w = the number of lines the entry stands for (the reads of the unique query) | unique << 31 -- unique: each of those reads is on this one
+ * line of the file only.  sink = NULL: bh_report_view. */
+typedef struct BhPlaceSink { BhipCovLine *lines; uint64_t n, cap; } BhPlaceSink;
+int  bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx, uint64_t *nLines, BhPlaceSink *sink);
+
+/* ---- coverage and count tables per reference header and sample (bh_cov.c; burst_hip --coverage) ----
+ * What embalmlets/bcov.c and embalmulate.c compute from the .b6 text, from the report's own placements: PREFIXshared.txt, PREFIXunique.txt,
+ * PREFIXshared_binary.txt, PREFIXunique_binary.txt (bcov's names and format) and PREFIXcounts.txt.  The statistics are the device's
+ * (bhip_cov_*, exact 64-bit integers); the tables are written from them in double, to temporary names first and renamed together, so
+ * that a failed run leaves no partial tables.
+ *   bh_cov_open     lengths_file: bcov's table `name<TAB>length` per line (BH_E_USAGE naming the first header of the database it lacks),
+ *                   or NULL: the database's own extent of every header (bh_cov_lengths_from_extents over bhip_lane_extents)
+ *   bh_cov_sample   the next sample (column): its placements go to the device behind `hip_handle` (the same handle every time)
+ *   bh_cov_sample_failed  the next column stays all zero (a sample that failed alone); named on standard output
+ *   bh_cov_stats    columns x headers x {tot, cov, sq, lines}, column 0 = Dataset; either pointer may be NULL
+ *   bh_cov_write    fetches the statistics and writes the five tables
+ * Any device error is final: later calls return it and nothing is written. */
+typedef struct BhCov BhCov;
+typedef int (*bh_cov_tap_fn)(void *ctx, uint32_t sample, const BhipCovLine *lines, uint64_t n);
+int  bh_cov_open(const BhDb *db, const char *prefix, const char *lengths_file, uint32_t pad, BhCov **cov);
+/* test / diagnostic hook: called with every sample's placements before they go to the device; a return of 1 keeps them from it */
+void bh_cov_set_tap(BhCov *cov, bh_cov_tap_fn fn, void *ctx);
+int  bh_cov_sample(BhCov *cov, void *hip_handle, const char *out_path, const BhipCovLine *lines, uint64_t n);
+int  bh_cov_sample_failed(BhCov *cov, const char *out_path);
+void bh_cov_abort(BhCov *cov);                  /* the run ends on an error: nothing will be written */
+void bh_cov_dims(const BhCov *cov, uint32_t *n_columns, uint32_t *n_headers);
+const uint32_t *bh_cov_lengths(const BhCov *cov);      /* [n_headers]; NULL before the first sample of a run without a lengths file */
+int  bh_cov_stats(BhCov *cov, uint64_t *shared, uint64_t *unique);
+int  bh_cov_write(BhCov *cov);
+void bh_cov_print_info(BhCov *cov);             /* one line on standard output: device time of the columns, peak of the event buffer, compactions */
+void bh_cov_close(BhCov *cov);
+/* extents[16 * clump + lane] -> length of every header: the largest refStart + extent of the lane over the header's fragments */
+int  bh_cov_lengths_from_extents(const BhDb *db, const uint32_t *extents, uint32_t *lengths);
+/* the lane extents from the packed references in host memory (where no one device holds the whole database) */
+void bh_cov_extents_host(const BhDb *db, uint32_t *extents);
+int  bh_cov_lengths_host(BhCov *cov);           /* no lengths table: take them from bh_cov_extents_host now */
+/* the writer alone: stats = [n_columns][n_headers][4] (tot, cov, sq, lines), column 0 = Dataset, col_names[1 .. n_columns) the samples */
+int  bh_cov_write_tables(const char *prefix, uint32_t n_headers, const char *const *headers, const uint32_t *lengths, uint32_t n_columns,
+                         const char *const *col_names, const uint64_t *shared, const uint64_t *unique);
+
 /* ---- a session: the database stays on the devices, a list of query files runs through it (bh_session.c) ---- */
 typedef struct BhSession BhSession;
 typedef struct BhSessionOpts {            /* fixed for the whole session */
@@ -272,6 +314,7 @@ typedef struct BhSessionOpts {            /* fixed for the whole session */
 	const BhTaxOpts *tax;                 /* NULL = no taxonomy column (copied; the BhTax it points to must outlive the session) */
 	int ingest_ahead;                     /* 1 = bh_session_prefetch parses a sample on a thread while the current one is searched and reported */
 	int verbose;                          /* 1 = the command line's per-sample lines on standard output */
+	BhCov *cov;                           /* NULL, or the coverage every reported sample feeds (rank 0's process; the caller opens it, writes the tables and closes it) */
 } BhSessionOpts;
 typedef struct BhSampleResult {
 	int rc; char err[512];
@@ -301,6 +344,7 @@ int  bh_session_drop(BhSession *s);
 int  bh_session_run(BhSession *s, const char *queries, const char *out_path, BhSampleResult *res);
 const BhQueries *bh_session_sample(const BhSession *s);
 void bh_session_set_node(BhSession *s, BhNode *node);
+void bh_session_set_coverage(BhSession *s, BhCov *cov);      /* BhSessionOpts.cov for a session opened before its database was read */
 int  bh_session_ended(const BhSession *s);      /* 0, or the code of the error that ended the session */
 void bh_session_close(BhSession *s);
 

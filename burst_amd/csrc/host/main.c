@@ -4,6 +4,7 @@
  *   burst_hip -r refs.fa -q reads.fa -o out.b6 [-s [len]]            direct FASTA (exhaustive, no accelerator)
  *   burst_hip -r refs.fa -d [QUICK|DNA|RNA] [qLen] -o DB.edx [-a DB.acx] [-s [len]] [-dp N] -i 0.97      database construction
  *   burst_hip -r DB.edx (-a DB.acx | -ad) --samples LIST -m ... -i ...    a list of `queries<TAB>output` against the one resident database (bh_session.c)
+ *   ... -q / -o or --samples ... --coverage PREFIX [--coverage-lengths FILE] [--coverage-pad N]      coverage and count tables per reference and sample (bh_cov.c)
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
  * reference's exit code 1.  Extra flags: --device N, --batch N (unique queries per device call), -k {12|15}.
@@ -114,6 +115,7 @@ typedef struct {
 	const char *ref_FN, *xcel_FN, *tax_FN, *list_FN;
 	BhMode mode; float thres; int z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device;
 	int n_gpus, n_gpus_given, n_dev_list, *dev_list, shard_db, n_shards; uint64_t batch; BhTaxOpts *txo;
+	const char *cov_prefix, *cov_lengths; uint32_t cov_pad;
 } SamplesArgs;
 typedef struct { char *q, *o; int line; } Sample;
 
@@ -201,6 +203,11 @@ static int samples_main(SamplesArgs *a) {
 		printf(" --> [Accel] K=%d, %s format, %u ambiguous clumps\n", K, db.acxFmt ? "LARGE" : "SMALL", db.badSz);
 	}
 	PHASE("database read");
+	BhCov *cov = NULL;
+	if (a->cov_prefix) {      /* (the lengths table is checked against the database's headers before a device is touched) */
+		if ((rc = bh_cov_open(&db, a->cov_prefix, a->cov_lengths, a->cov_pad, &cov))) DIES(rc);
+		bh_session_set_coverage(ses, cov);
+	}
 	if (shard_db && (uint32_t)n_shards > db.numRclumps) { bh_session_close(ses); puts("ERROR: more database shards than clumps"); return 1; }
 	{ const int e = open_devices(&db, n_gpus, dev_list, shard_db, n_shards, a->accel_dev, K, a->z, hhs, ranks, slices); if (e) { bh_session_close(ses); return e; } }
 	for (int r = 0; r < n_gpus; ++r) ranks[r].hh = hhs[r];
@@ -219,12 +226,18 @@ static int samples_main(SamplesArgs *a) {
 		} else ++n_done;
 		fflush(stdout);
 	}
+	if (cov && !bh_session_ended(ses)) {
+		tp = wall();
+		if ((rc = bh_cov_write(cov))) { fprintf(stderr, "%s\n", bh_last_error()); if (!first_fail) first_fail = code_to_exit(rc); }
+		else { printf("Coverage tables written: %sshared.txt, %sunique.txt, %sshared_binary.txt, %sunique_binary.txt, %scounts.txt\n", a->cov_prefix, a->cov_prefix, a->cov_prefix, a->cov_prefix, a->cov_prefix); PHASE("coverage tables"); bh_cov_print_info(cov); }
+	} else if (cov) puts("No coverage tables are written: the run ended on an error");
 	printf("\nSamples: %d done, %d failed. Alignment time: %f seconds\n", n_done, n_failed, wall() - start);
 	fflush(NULL);
 	#undef PHASE
 	#undef DIES
 	if (!getenv("BURST_HOST_TEARDOWN")) _exit(first_fail);      /* (as the single-sample path: the operating system releases a finished process's memory faster) */
 	bh_session_close(ses);
+	bh_cov_close(cov);
 	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); bh_run_free(&ranks[r].run); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
 	bh_db_free(&db); bh_tax_free(&taxonomy);
 	for (int i = 0; i < nS; ++i) { free(S[i].q); free(S[i].o); }
@@ -252,6 +265,9 @@ static void usage(void) {
 	puts("--accelerator-device (-ad): no .acx file, the device builds the accelerator from the .edx (word length -k, default 12)");
 	puts("--samples <list>: align a list of query files against the one resident database, each to its own output; one sample per line,");
 	puts("                  'queries<TAB>output' (in place of -q / -o; needs -r DB.edx; the database is read, uploaded and indexed once)");
+	puts("--coverage <prefix> [--coverage-lengths <file>] [--coverage-pad <int>]: with -q / -o or --samples, leave coverage and count tables per");
+	puts("                  reference and sample next to the .b6 files: <prefix>shared.txt, unique.txt, shared_binary.txt, unique_binary.txt,");
+	puts("                  counts.txt; lengths from a 'name<TAB>length' table, else the database's own extent of every reference");
 	puts("--host-acx: build accelerators (-d ... -a, --make-acx) with the host builder instead of the device");
 }
 
@@ -265,7 +281,8 @@ int main(int argc, char **argv) {
 	uint32_t latency = 16;                          /* burst.c:83 */
 	int n_gpus = 1, n_gpus_given = 0, gather_host = 1, n_dev_list = 0, dev_list[BH_MAX_GPUS], accel_dev = 0, host_acx = 0, shard_db = 0, n_shards = 0;
 	uint64_t batch = 1u << 21;      /* unique queries per device batch: the fixed cost of a batch (launches, synchronisation) is about 1 ms of device time */
-	const char *ref_FN = 0, *query_FN = 0, *output_FN = 0, *xcel_FN = 0, *mkacx_FN = 0, *tax_FN = 0, *samples_FN = 0;
+	const char *ref_FN = 0, *query_FN = 0, *output_FN = 0, *xcel_FN = 0, *mkacx_FN = 0, *tax_FN = 0, *samples_FN = 0, *cov_prefix = 0, *cov_lengths = 0;
+	uint32_t cov_pad = 0;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
 	BhTaxOpts txo; memset(&txo, 0, sizeof txo); txo.taxacut = 10;   /* burst.c:92 */
 	setenv("GPU_MAX_HW_QUEUES", "8", 0);      /* HIP runtime: hardware queues for the library's four streams (read when the runtime starts) */
@@ -316,6 +333,9 @@ int main(int argc, char **argv) {
 		else if (!strcmp(a, "--no-dupe-hunt")) rep_flags |= BH_REP_NO_DUPE_HUNT;   /* diagnostics: print every (hit, reference) expansion */
 		else if (!strcmp(a, "--samples")) { NEEDARG("--samples"); samples_FN = argv[i]; }
 		else if (!strcmp(a, "--make-acx")) { NEEDARG("--make-acx"); mkacx_FN = argv[i]; }
+		else if (!strcmp(a, "--coverage")) { NEEDARG("--coverage"); cov_prefix = argv[i]; }
+		else if (!strcmp(a, "--coverage-lengths")) { NEEDARG("--coverage-lengths"); cov_lengths = argv[i]; }
+		else if (!strcmp(a, "--coverage-pad")) { NEEDARG("--coverage-pad"); cov_pad = (uint32_t)strtoul(argv[i], 0, 10); }
 		else if (!strcmp(a, "--device")) { NEEDARG("--device"); device = atoi(argv[i]); }
 		else if (!strcmp(a, "--gpus")) { NEEDARG("--gpus"); n_gpus = atoi(argv[i]); n_gpus_given = 1; if (n_gpus < 1) { puts("ERROR: --gpus must be >= 1"); return 1; } }
 		else if (!strcmp(a, "--devices")) {      /* explicit device of every rank, e.g. 0,1,2,3 (the same device twice only with --gather host) */
@@ -378,6 +398,8 @@ int main(int argc, char **argv) {
 	}
 	if (n_dev_list && !n_gpus_given) { n_gpus = n_dev_list; n_gpus_given = 1; }
 	if (n_dev_list && n_dev_list != n_gpus) { puts("ERROR: --devices must name one device per --gpus rank"); return 1; }
+	if ((cov_lengths || cov_pad) && !cov_prefix) { puts("ERROR: --coverage-lengths and --coverage-pad go with --coverage <prefix>"); return 1; }
+	if (cov_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --coverage works from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
 	if (samples_FN) {
 		/* per sample what a separate invocation writes; everything checked here is checked before a device is touched.  Out of scope:
 		 * per-sample identity / mode, FASTA references, -x, serial shards and the RCCL gather (refused below and in samples_main) */
@@ -387,7 +409,7 @@ int main(int argc, char **argv) {
 		if (!gather_host) { puts("ERROR: --samples takes the host gather only (drop --gather rccl)"); return 1; }
 		if (accel_dev && xcel_FN) { puts("ERROR: -ad builds the accelerator on the device; drop -a"); return 1; }
 		SamplesArgs sa = {ref_FN, xcel_FN, tax_FN, samples_FN, mode, thres, z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device,
-		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo};
+		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo, cov_prefix, cov_lengths, cov_pad};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
@@ -516,6 +538,9 @@ int main(int argc, char **argv) {
 	const int use_rccl = n_gpus_given && !gather_host;
 	if (shard_db && !n_shards) n_shards = n_gpus;
 	if (!shard_db || n_shards < 2) { shard_db = 0; n_shards = 1; }
+	if (cov_prefix && shard_db && n_gpus == 1 && n_shards > 1) { JOIN_INGEST(); puts("ERROR: --coverage needs a resident device handle: it does not go with the serial-shards path (--gpus 1 --shards S)"); return 1; }
+	BhCov *cov = NULL;
+	if (cov_prefix && (rc = bh_cov_open(&db, cov_prefix, cov_lengths, cov_pad, &cov))) DIEJ(rc);      /* (before a device is touched) */
 	if (shard_db && n_gpus == 1 && n_shards > 1 && !use_rccl) {
 		/* more shards than devices: the shards take turns on the one device (bh_search_serial_shards) -- a database larger than the
 		 * device's memory, at the price of one upload per shard */
@@ -640,16 +665,24 @@ int main(int argc, char **argv) {
 	PHASE("search (all batches)");
 	uint64_t lines = 0;
 	setvbuf(output, NULL, _IOFBF, 1 << 22);
-	if ((rc = bh_report_view(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines))) DIE(rc);
+	BhPlaceSink sink; memset(&sink, 0, sizeof sink);
+	if ((rc = bh_report_view_sink(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov ? &sink : NULL))) DIE(rc);
 	if (fclose(output)) { fprintf(stderr, "ERROR: write failed: %s\n", output_FN); return 2; }      /* (the last buffer of the report: a full disk must not end in exit code 0) */
 	printf("Wrote %lu alignments\n", (unsigned long)lines);
 	PHASE("consolidation, output");
+	if (cov) {      /* a study of one sample: the Dataset column and the sample's (rank 0's handle; the lines exist only here) */
+		if ((shard_db && (rc = bh_cov_lengths_host(cov))) || (rc = bh_cov_sample(cov, hhs[0], output_FN, sink.lines, sink.n)) || (rc = bh_cov_write(cov))) DIE(rc);
+		printf("Coverage tables written: %sshared.txt, %sunique.txt, %sshared_binary.txt, %sunique_binary.txt, %scounts.txt\n", cov_prefix, cov_prefix, cov_prefix, cov_prefix, cov_prefix);
+		PHASE("coverage");
+		bh_cov_print_info(cov);
+	}
 	printf("\nAlignment time: %f seconds\n", wall() - start);
 	fflush(NULL);
 	/* The job is done and its output is on disk.  Unpinning and unmapping tens of gigabytes one table after the other took about a
 	 * second for a 32 M-read job; the operating system releases a finished process's memory (host and device) far faster.
 	 * BURST_HOST_TEARDOWN=1 walks through the orderly release instead (leak checks). */
 	if (!getenv("BURST_HOST_TEARDOWN")) _exit(0);
+	bh_cov_close(cov); free(sink.lines);
 	if (comm) bhip_comm_destroy(comm);
 	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
 	for (int r = 0; r < n_gpus; ++r) bh_run_free(&ranks[r].run);

@@ -86,7 +86,10 @@ class BhTaxOpts(C.Structure):
 class BhSessionOpts(C.Structure):
     _fields_ = [("mode", C.c_int), ("thres", C.c_float), ("do_rc", C.c_int), ("incl_ws", C.c_int), ("z", C.c_int), ("do_accel", C.c_int), ("K", C.c_int),
                 ("skip_ambig", C.c_int), ("rep_flags", C.c_int), ("batch", C.c_uint64), ("shard_db", C.c_int), ("tax", C.POINTER(BhTaxOpts)),
-                ("ingest_ahead", C.c_int), ("verbose", C.c_int)]
+                ("ingest_ahead", C.c_int), ("verbose", C.c_int), ("cov", C.c_void_p)]
+
+
+COV_TAP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64)
 
 
 class BhSampleResult(C.Structure):
@@ -176,6 +179,23 @@ def lib():
         L.bh_session_ended.argtypes = [C.c_void_p]
         L.bh_session_close.argtypes = [C.c_void_p]
         L.bh_session_close.restype = None
+        L.bh_cov_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.bh_cov_set_tap.argtypes = [C.c_void_p, COV_TAP_FN, C.c_void_p]
+        L.bh_cov_set_tap.restype = None
+        L.bh_cov_abort.argtypes = [C.c_void_p]
+        L.bh_cov_abort.restype = None
+        L.bh_cov_dims.argtypes = [C.c_void_p, u32p, u32p]
+        L.bh_cov_dims.restype = None
+        L.bh_cov_lengths.argtypes = [C.c_void_p]
+        L.bh_cov_lengths.restype = u32p
+        L.bh_cov_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_cov_write.argtypes = [C.c_void_p]
+        L.bh_cov_close.argtypes = [C.c_void_p]
+        L.bh_cov_close.restype = None
+        L.bh_cov_lengths_from_extents.argtypes = [C.POINTER(BhDb), C.c_void_p, C.c_void_p]
+        L.bh_cov_extents_host.argtypes = [C.POINTER(BhDb), C.c_void_p]
+        L.bh_cov_extents_host.restype = None
+        L.bh_cov_write_tables.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -517,8 +537,14 @@ class Session:
 
     def __init__(self, db, devs=None, mode="CAPITALIST", thres=0.97, rc=False, whitespace=False, z=1, accel=None, K=0, batch=1 << 21, shard_db=0,
                  taxonomy=None, taxacut=10, tax_ncbi=False, tax_suppress=False, tax_strict=False, rep_flags=0, ingest_ahead=True,
-                 align=None, reduce_min=None, rank=0, world=None, c0=0, node=None, comm=None, verbose=False):
+                 align=None, reduce_min=None, rank=0, world=None, c0=0, node=None, comm=None, verbose=False,
+                 coverage=None, coverage_lengths=None, coverage_pad=0, coverage_tap=None):
+        """coverage = prefix: every reported sample feeds the coverage (bh_cov.c) on rank 0's device handle; close() writes the five tables
+        prefix{shared,unique,shared_binary,unique_binary,counts}.txt unless the session ended on an error; coverage() returns the integer
+        statistics.  coverage_lengths: a `name<TAB>length` table (default: the database's own extents); coverage_tap(sample, lines):
+        called with every sample's placements (capi.COV_LINE_DTYPE) before they go to the device, a true return keeps them from it."""
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
+        self.cov = C.c_void_p()
         devs = list(devs) if isinstance(devs, (list, tuple)) else [devs]
         n_local = len(devs)
         world = world or n_local
@@ -543,6 +569,21 @@ class Session:
             self.taxo.tax, self.taxo.suppress, self.taxo.strict, self.taxo.taxacut, self.taxo.ncbi = C.pointer(self.tax), int(tax_suppress), int(tax_strict), taxacut, int(tax_ncbi)
             o.tax = C.pointer(self.taxo)
         self.ended = False
+        self.cov_aborted = False
+        if coverage is not None and (rank == 0 or len(devs) > 1):      # (in a job of processes the lines exist only where rank 0 reports)
+            _chk(lib().bh_cov_open(C.byref(db.c), coverage.encode(), coverage_lengths.encode() if coverage_lengths else None, int(coverage_pad), C.byref(self.cov)))
+            if coverage_tap is not None:
+                def _tap(ctx, sample, lines, n):
+                    try:
+                        a = np.frombuffer((C.c_uint8 * (int(n) * 16)).from_address(lines), dtype=capi.COV_LINE_DTYPE).copy() if n else np.zeros(0, capi.COV_LINE_DTYPE)
+                        return 1 if coverage_tap(int(sample), a) else 0
+                    except Exception:      # (an exception must not cross the C frame)
+                        import traceback
+                        traceback.print_exc()
+                        return 0
+                self._cb.append(COV_TAP_FN(_tap))
+                lib().bh_cov_set_tap(self.cov, self._cb[-1], None)
+            o.cov = self.cov
         _chk(lib().bh_session_open(C.byref(db.c), self.ranks, n_local, world, comm, node.h if node is not None else None, C.byref(o), C.byref(self.h)))
 
     def _align_cb(self, align):
@@ -608,14 +649,44 @@ class Session:
         self.node = node
         lib().bh_session_set_node(self.h, node.h if node is not None else None)
 
+    def coverage(self):
+        """the integer statistics so far: (shared, unique), each uint64 [columns][headers][4] = tot, cov, sq, lines; column 0 = Dataset"""
+        if not self.cov:
+            raise HostError("the session has no coverage")
+        nc, nh = C.c_uint32(), C.c_uint32()
+        lib().bh_cov_dims(self.cov, C.byref(nc), C.byref(nh))
+        sh, un = np.zeros((nc.value, nh.value, 4), np.uint64), np.zeros((nc.value, nh.value, 4), np.uint64)
+        _chk(lib().bh_cov_stats(self.cov, sh.ctypes.data, un.ctypes.data))
+        return sh, un
+
+    def coverage_abort(self):
+        """the walk ends on an error that the session itself has not seen (another rank's): close() writes no tables"""
+        if self.cov:
+            lib().bh_cov_abort(self.cov)
+            self.cov_aborted = True
+
+    def coverage_lengths(self):
+        nh = C.c_uint32()
+        lib().bh_cov_dims(self.cov, None, C.byref(nh))
+        p = lib().bh_cov_lengths(self.cov)
+        return _view(p, nh.value, np.uint32).copy() if p else None
+
     def close(self):
         if self.h:
+            err = None
+            if self.cov:      # (before the handles go: the coverage lives on rank 0's)
+                if not lib().bh_session_ended(self.h) and not self.cov_aborted and lib().bh_cov_write(self.cov):
+                    err = lib().bh_last_error().decode("utf-8", "replace")
+                lib().bh_cov_close(self.cov)
+                self.cov = C.c_void_p()
             lib().bh_session_close(self.h)
             self.h = C.c_void_p()
             for i in range(len(self.ranks)):
                 lib().bh_run_free(C.byref(self.ranks[i].run))
             if self.tax.n or self.tax.blob:
                 lib().bh_tax_free(C.byref(self.tax))
+            if err:
+                raise HostError("coverage tables not written: " + err)
 
     def __enter__(self):
         return self

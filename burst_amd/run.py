@@ -119,7 +119,8 @@ def run_samples(args, samples, db, K, accel, z, rank, local_rank, world, one_dev
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         a[:] = t.cpu().numpy()
     ses = host.Session(db, dev, mode=args.mode, thres=args.id, rc=args.forwardreverse, z=z, accel=accel, K=K, batch=args.batch, shard_db=world if shard_db else 0,
-                       reduce_min=reduce_min if shard_db else None, rank=rank, world=world, c0=c0)
+                       reduce_min=reduce_min if shard_db else None, rank=rank, world=world, c0=c0,
+                       coverage=args.coverage, coverage_lengths=args.coverage_lengths, coverage_pad=args.coverage_pad)      # (rank 0's handle: the lines exist only where it reports)
     node, cap_have, first_fail, n_done = None, 0, 0, 0
     ses.prefetch(samples[0][0])
     for i, (q, o) in enumerate(samples):
@@ -154,12 +155,13 @@ def run_samples(args, samples, db, K, accel, z, rank, local_rank, world, one_dev
             res = ses.finish()
             st = agree(res["rc"])
         elif res["rc"] == 0:
-            ses.drop()                      # (another rank could not have this sample)
+            ses.drop()                      # (another rank could not have this sample; with --coverage: an all-zero column under its name)
         if st < 0:
             if rank == 0:
                 print("Sample %d/%d FAILED (exit code %d): %s" % (i + 1, len(samples), exit_of.get(st, 4), res["err"] or "another rank failed"), flush=True)
             first_fail = first_fail or exit_of.get(st, 4)
             if st not in (host.E_USAGE, host.E_IO) or ses.ended:
+                ses.coverage_abort()        # (the error may be another rank's: no tables of a walk that ended early)
                 break                       # nothing more is started on a device after a device error
             continue
         n_done += 1
@@ -169,7 +171,14 @@ def run_samples(args, samples, db, K, accel, z, rank, local_rank, world, one_dev
         print("Samples: %d done, %d failed" % (n_done, len(samples) - n_done), flush=True)
     if world > 1:
         dist.barrier()
-    ses.close()
+    try:
+        ended = ses.ended
+        ses.close()      # (with --coverage: rank 0 writes the tables here, unless the walk ended on an error)
+        if rank == 0 and args.coverage and not ended and not ses.cov_aborted:
+            print("Coverage tables: %s{shared,unique,shared_binary,unique_binary,counts}.txt" % args.coverage, flush=True)
+    except host.HostError as e:
+        sys.stderr.write("%s\n" % e)
+        first_fail = first_fail or 4
     if node is not None:
         node.close()
     if world > 1:
@@ -196,7 +205,13 @@ def main(argv=None):
     ap.add_argument("--shard", default="queries", choices=["queries", "db"],
                     help="queries: database replicated, every rank aligns its range of queries (default); db: every rank holds a "
                          "range of the database's clumps and aligns all queries (for databases larger than one device)")
+    ap.add_argument("--coverage", metavar="PREFIX", help="coverage and count tables per reference and sample next to the outputs: "
+                    "PREFIX{shared,unique,shared_binary,unique_binary,counts}.txt (computed on rank 0's device from the lines it reports)")
+    ap.add_argument("--coverage-lengths", metavar="FILE", help="reference lengths, 'name<TAB>length' per line (default: the database's own extent of every reference)")
+    ap.add_argument("--coverage-pad", type=int, default=0, help="bases a placement's range is widened by at both ends")
     args = ap.parse_args(argv)
+    if (args.coverage_lengths or args.coverage_pad) and not args.coverage:
+        ap.error("--coverage-lengths and --coverage-pad go with --coverage PREFIX")
     samples = None
     if args.samples:
         if args.queries or args.output:
@@ -206,6 +221,8 @@ def main(argv=None):
             return code
     elif not args.queries or not args.output:
         ap.error("the following arguments are required: -q/--queries, -o/--output (or --samples)")
+    elif args.coverage:
+        samples = [(args.queries, args.output)]      # a study of one sample: the session's path
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     import torch
     one_dev = os.environ.get("BURST_RUN_DEVICE")      # test hook: every rank on this device (gloo plumbing; RCCL refuses two ranks on one device)

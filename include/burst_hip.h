@@ -298,6 +298,35 @@ BHIP_API int bhip_sort_queries(int device, const uint8_t *codes, uint64_t codes_
 BHIP_API int bhip_dna_marks(int device, const uint8_t *sym, uint64_t sym_len, const uint64_t *ref_start, const uint32_t *ref_len,
                             uint64_t n_refs, uint32_t W, uint64_t *max_chain, uint64_t *max_sh, uint8_t *flags, uint64_t *info);
 
+/* Coverage of the printed placements per reference header and sample (burst_hip --coverage; no reference counterpart on the device: what
+ * embalmlets/bcov.c and embalmulate.c compute from the .b6 text with two counters per reference POSITION).  A line covers the half-open
+ * range [max(lo - 1 - pad, 0), min(hi - 1 + pad, length)) of its header, lo / hi = the smaller / larger of st and ed; the depth of a
+ * position is the summed weight of the lines that cover it.  Per header and column the library returns four 64-bit integers:
+ * tot = sum of the depths, cov = positions with depth != 0, sq = sum of the squared depths, lines = summed weight of the lines (those with
+ * an empty range included).  Two columns each time: "shared" over all lines, "unique" over those with bit 31 of `w` set.  The device
+ * works from two sorted events per line, never from per-position arrays (csrc/bhip_cov.hip): the cost follows the lines.
+ *   bhip_cov_begin        n_headers lengths (copied) and the pad; replaces a coverage that was open on the handle
+ *   bhip_cov_add          ONE WHOLE sample: its lines (header < n_headers).  A sample index can be added once; indices need not be dense
+ *   bhip_cov_sample_stats shared / unique [n_headers][4] = tot, cov, sq, lines of that sample (either may be NULL); all zero for an index
+ *                         that was never added
+ *   bhip_cov_dataset_stats the same over the events of ALL samples added so far (the depths of the samples summed)
+ *   bhip_cov_info         [0] events resident, [1] peak bytes of the event sets, [2] compactions so far, [3] the cap in bytes, [4] device
+ *                         microseconds of the last bhip_cov_add's sorts, scans and statistics kernels (HIP events), [5] events per block of
+ *                         the statistics kernel, [6] the sum of [4] over all calls, [7] samples added
+ *   bhip_cov_end          releases everything (bhip_destroy does it too)
+ * Option "cov_event_cap" (bytes, default 0 = a fifth of the device memory free at the first bhip_cov_add): beyond it the event sets are
+ * compacted (equal keys summed, zeros dropped); BHIP_E_DEVICE only if the compacted sets still do not fit.
+ * bhip_lane_extents: extents[16 * clump + lane] = index after the lane's last symbol that is not the pad code 0 (0 for an empty lane), for
+ * all 16 * n_clumps lanes of the resident database -- the reference lengths a caller derives without walking the packed references. */
+typedef struct BhipCovLine { uint32_t ref, st, ed, w; } BhipCovLine;      /* header, .b6 columns 9 and 10, weight (bits 0..30) | unique << 31 */
+BHIP_API int bhip_cov_begin(void *handle, uint32_t n_headers, const uint32_t *lengths, uint32_t pad);
+BHIP_API int bhip_cov_add(void *handle, uint32_t sample, const BhipCovLine *lines, uint64_t n);
+BHIP_API int bhip_cov_sample_stats(void *handle, uint32_t sample, uint64_t *shared, uint64_t *unique);
+BHIP_API int bhip_cov_dataset_stats(void *handle, uint64_t *shared, uint64_t *unique);
+BHIP_API int bhip_cov_info(void *handle, uint64_t info[8]);
+BHIP_API int bhip_cov_end(void *handle);
+BHIP_API int bhip_lane_extents(void *handle, uint32_t *extents);
+
 /* Tuning knobs.  "prefilter_stride": 0 (default) = automatic sparse seeds -- per query the largest stride s <= K for
  * which an alignment within budget still keeps >= 3 of the words starting at 0, s, 2s, ... (one edit destroys at most
  * ceil(K/s) of them), fewest .acx look-ups with the same no-false-negative guarantee; s >= 1 forces every s-th word,
