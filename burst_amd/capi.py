@@ -47,7 +47,20 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_device_info", "bhip_destroy", "bhip_last_error", "bhip_abi_version", "bhip_set_ref_order", "bhip_copy_hits_device", "bhip_sync_hits",
            "bhip_comm_create", "bhip_comm_unique_id", "bhip_comm_create_rank", "bhip_comm_allreduce_min", "bhip_comm_fetch_gathered", "bhip_comm_gather_hits", "bhip_comm_stage_device", "bhip_comm_gather_staged", "bhip_comm_stage_reset", "bhip_comm_destroy", "bhip_acx_export", "bhip_reserve", "bhip_reserve_symbols", "bhip_sort_queries", "bhip_stage_spans", "bhip_alloc_host", "bhip_free_host", "bhip_host_register", "bhip_host_unregister", "bhip_set_enqueued_hook", "bhip_acx_export_entries",
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
-           "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents"]
+           "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
+           "bhip_trace_paths", "bhip_paths_info"]
+
+# BhipPathReq, 16 bytes: query entry, refIx, finalPos, ed of a record
+PATH_REQ_DTYPE = np.dtype([("q", "<u4"), ("refIx", "<u4"), ("finalPos", "<u4"), ("ed", "<u4")])
+assert PATH_REQ_DTYPE.itemsize == 16
+OP_I, OP_D, OP_EQ, OP_X = 1, 2, 7, 8
+OP_CHARS = {OP_I: "I", OP_D: "D", OP_EQ: "=", OP_X: "X"}
+
+
+def cigar_text(ops):
+    """ops of one path (words length << 4 | code) as CIGAR text in =XID"""
+    return "".join("%d%s" % (int(w) >> 4, OP_CHARS[int(w) & 15]) for w in ops)
+
 
 # BhipCovLine, 16 bytes: header, .b6 columns 9 and 10, weight (bits 0..30) | unique << 31
 COV_LINE_DTYPE = np.dtype([("ref", "<u4"), ("st", "<u4"), ("ed", "<u4"), ("w", "<u4")])
@@ -145,6 +158,10 @@ def _load():
     lib.bhip_cov_info.argtypes = [vp, vp]
     lib.bhip_cov_end.argtypes = [vp]
     lib.bhip_lane_extents.argtypes = [vp, vp]
+    lib.bhip_trace_paths.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, vp, vp, vp]
+    lib.bhip_trace_paths.restype = i32
+    lib.bhip_paths_info.argtypes = [vp, vp]
+    lib.bhip_paths_info.restype = i32
     for f in (lib.bhip_cov_begin, lib.bhip_cov_add, lib.bhip_cov_sample_stats, lib.bhip_cov_dataset_stats, lib.bhip_cov_info, lib.bhip_cov_end, lib.bhip_lane_extents):
         f.restype = i32
     return lib
@@ -338,6 +355,33 @@ class Device:
         ext = np.zeros(16 * self.n_clumps, np.uint32)
         _chk(lib().bhip_lane_extents(self._h, _ptr(ext)))
         return ext
+
+    def trace_paths(self, q, requests, cap=None):
+        """alignment paths of records (bhip_trace_paths).  q: the Queries the records' entry numbers refer to; requests: PATH_REQ_DTYPE array
+        (or rows q, refIx, finalPos, ed).  Returns (ops, op_off, ref_first, gap_r): request i owns ops[op_off[i]:op_off[i + 1]]"""
+        if not (isinstance(requests, np.ndarray) and requests.dtype == PATH_REQ_DTYPE):
+            rows = np.asarray(requests, dtype=np.uint32).reshape(-1, 4)
+            requests = np.zeros(len(rows), PATH_REQ_DTYPE)
+            for k, name in enumerate(("q", "refIx", "finalPos", "ed")):
+                requests[name] = rows[:, k]
+        requests = np.ascontiguousarray(requests)
+        n = len(requests)
+        cap = int(cap) if cap is not None else max(16, 4 * n)
+        op_off = np.zeros(n + 1, np.uint64)
+        ref_first, gap_r = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        while True:
+            ops = np.zeros(max(cap, 1), np.uint32)
+            rc = lib().bhip_trace_paths(self._h, _ptr(q.codes), _ptr(q.off), q.n, _ptr(requests), n, _ptr(ops), cap, _ptr(op_off), _ptr(ref_first), _ptr(gap_r))
+            if rc == BHIP_E_CAPACITY and int(op_off[n]) > cap:
+                cap = int(op_off[n])
+                continue
+            _chk(rc)
+            return ops[:int(op_off[n])], op_off, ref_first[:n], gap_r[:n]
+
+    def paths_info(self):
+        info = np.zeros(4, np.uint64)
+        _chk(lib().bhip_paths_info(self._h, _ptr(info)))
+        return dict(zip(("us_last", "us_total", "requests", "ops"), (int(x) for x in info)))
 
     def cov_begin(self, lengths, pad=0):
         """coverage over len(lengths) reference headers (bhip_cov_begin); cov_add() one whole sample at a time"""

@@ -445,6 +445,7 @@ struct Handle {
 	int opt_seed_drop_len = 8;    // ... lists shorter than this are always kept (leaving them out saves nothing and costs selectivity)
 	double acx_wmean = 0.0;       // occurrence-weighted mean .acx list length
 	void *cov = nullptr;          // coverage state between bhip_cov_begin and bhip_cov_end (bhip_cov.hip)
+	void *paths = nullptr;        // buffers, events and totals of bhip_trace_paths (bhip_paths.hip), made by the first call
 	long long opt_cov_event_cap = 0;   // bytes the coverage event sets may take before they are compacted (0 = a fifth of the memory free at the first bhip_cov_add)
 };
 
@@ -460,4 +461,5 @@ void lane_capacity_floor(Handle *h, Lane *L, uint64_t n);
 int  bhip_load_accelerator(Handle *h, const uint32_t *acx_lens, const void *acx_lists, int acx_fmt, int K, const uint32_t *badlist, uint32_t n_bad);   // bhip_acx.hip
 int  bhip_build_accelerator(Handle *h, int K, int z);
 void bhip_cov_release(Handle *h);                                            // bhip_cov.hip
+void bhip_paths_release(Handle *h);                                          // bhip_paths.hip
 #endif

@@ -170,6 +170,13 @@ static int pl_append(BhPlaceSink *sink, BhPlaceSink *b) {
  * sink == NULL is bh_report_view. */
 int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx,
                         uint64_t *nLines, BhPlaceSink *sink) {
+	return bh_report_view_paths(out, db, Q, view, mode, flags, tx, nLines, sink, NULL);
+}
+/* The same with the alignment paths (bh_paths.c): every chunk notes, per line it prints, the record the line shows and the offset of its
+ * reference; the thread that writes a group of chunks has the group's distinct records traced in one call and writes every line with its
+ * two further columns.  paths == NULL is bh_report_view_sink. */
+int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx,
+                         uint64_t *nLines, BhPlaceSink *sink, BhPaths *paths) {
 	const BhipHit *hits = view->base;
 	const uint64_t nU = Q->numUniq, nE = Q->numEntries;
 	FILE *const real_out = out;
@@ -281,10 +288,14 @@ int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhR
 	const uint64_t CH = chunkQ, nChunks = (nU + CH - 1) / CH, chunkGroup = (uint64_t)nThreads * 8;
 	LineBuf *cbuf = calloc(nChunks + 1, sizeof(*cbuf)); uint64_t *coff = calloc(nChunks + 2, sizeof(*coff));
 	BhPlaceSink *pbuf = sink ? calloc(nChunks + 1, sizeof(*pbuf)) : NULL;
-	if (!cbuf || !coff || (sink && !pbuf)) { free(cbuf); free(coff); free(pbuf); free(start); free(count); free(RefCounts); return bh_set_error(BH_E_OOM, "OOM:report"); }
+	BhPathBuf *lbuf = paths ? calloc(nChunks + 1, sizeof(*lbuf)) : NULL;
+	int perr = 0;
+	if (!cbuf || !coff || (sink && !pbuf) || (paths && !lbuf)) { free(cbuf); free(coff); free(pbuf); free(lbuf); free(start); free(count); free(RefCounts); return bh_set_error(BH_E_OOM, "OOM:report"); }
 	if (sink) sink->n = 0;
 	/* header of a placement: the unique-header number of the .edx (RefMap), which direct-FASTA runs keep as well */
 	#define SINK(rix, st, ed, reads, uniq) do { if (sink && (reads) && !pl_push(&pbuf[ch], db->refMap ? db->refMap[rix] : (rix), st, ed, (uint32_t)(reads) | ((uniq) ? 0x80000000u : 0u))) out->oom = 1; } while (0)
+	/* the line just printed shows record rp against reference rix */
+	#define PLINE(rp, rix) do { if (paths && !bh_paths_push(&lbuf[ch], (uint64_t)((rp) - hits), db->refStart ? db->refStart[rix] : 0)) out->oom = 1; } while (0)
 	/* the rendered chunks of a group are written side by side at their offsets (pwrite) when the output is a seekable file: one
 	 * thread copying gigabytes into the page cache was the other half of the report's time */
 	fflush(real_out);
@@ -294,7 +305,7 @@ int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhR
 	/* measured on the GPU box (32 M lines, 2.4 GB, 32 threads): one thread's fwrite 0.3-0.5 s, pwrite side by side 0.6 s (the
 	 * writers queue on the file's lock), a shared mapping 1.6 s (page faults): one writer it is, beside the next group's rendering */
 	use_pwrite = 0;
-	if (getenv("BURST_HOST_REPORT_WRITE")) { const int w_ = atoi(getenv("BURST_HOST_REPORT_WRITE")); if (w_ >= 0 && w_ <= 2 && (use_pwrite || !w_)) use_pwrite = w_; }      /* tuning / test hook */
+	if (getenv("BURST_HOST_REPORT_WRITE") && !paths) { const int w_ = atoi(getenv("BURST_HOST_REPORT_WRITE")); if (w_ >= 0 && w_ <= 2 && (use_pwrite || !w_)) use_pwrite = w_; }      /* tuning / test hook */
 	char *map_base = NULL; size_t map_len = 0, map_skew = 0;
 	int map_fd = -1;      /* a shared writable mapping needs a descriptor opened for reading and writing: the caller's stream is write-only */
 	if (use_pwrite == 2) {
@@ -358,7 +369,7 @@ int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhR
 			for (uint32_t k = 0; k < nb; ++k) {
 				const uint64_t i = bi[k]; const uint32_t qlen = Q->len[i];
 				uint32_t st, ed; coords(db, bb[k], brix[k], qlen, &st, &ed);
-				for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[brix[k]], bb[k], qlen, st, ed, i, 0, NULL); ++lines; }
+				for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[brix[k]], bb[k], qlen, st, ed, i, 0, NULL); PLINE(bb[k], brix[k]); ++lines; }
 				SINK(brix[k], st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 			}
 		}
@@ -389,7 +400,7 @@ int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhR
 					}
 				} else FinalTaxon = tt;
 			}
-			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[rix], best, qlen, st, ed, i, wt, FinalTaxon); ++lines; }
+			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[rix], best, qlen, st, ed, i, wt, FinalTaxon); PLINE(best, rix); ++lines; }
 			SINK(rix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 		} else if (mode == BH_ANY) {                                         /* any valid hit; column 12 = duplicate flag (burst.c:4268-4272) */
 			/* The reference prints the first hit within budget a thread meets and marks the query spent (burst.c:4239-4275, 4457-4475).
@@ -400,7 +411,7 @@ int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhR
 			if (!merged) for (uint32_t k = 1; k < n; ++k) if (list[k]->ed < rp->ed) rp = list[k];
 			const uint32_t rix = db->refIxSrt[rp->refIx];
 			uint32_t st, ed; coords(db, rp, rix, qlen, &st, &ed);
-			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line(out, Q->heads[j], db->refHead[rix], rp, qlen, st, ed, j > Q->offset[i]); ++lines; }
+			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line(out, Q->heads[j], db->refHead[rix], rp, qlen, st, ed, j > Q->offset[i]); PLINE(rp, rix); ++lines; }
 			SINK(rix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 		} else if (mode == BH_ALLPATHS || mode == BH_FORAGE) {               /* burst.c:4582-4640, 4642-4692 */
 			uint32_t b = 0;
@@ -420,7 +431,7 @@ int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhR
 			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) for (uint64_t zz = 0; zz < rix_ix; ++zz) {
 				const BhipHit *rp = RPcache[zz]; const uint32_t rix = RIXcache[zz];
 				uint32_t st, ed; coords(db, rp, rix, qlen, &st, &ed);
-				print_line_tax(out, Q->heads[j], db->refHead[rix], rp, qlen, st, ed, i, wt, wt ? bh_tax_lookup(T, db->refHead[rix], ncbi) : NULL); ++lines;   /* burst.c:4631-4633, 4685-4687 */
+				print_line_tax(out, Q->heads[j], db->refHead[rix], rp, qlen, st, ed, i, wt, wt ? bh_tax_lookup(T, db->refHead[rix], ncbi) : NULL); PLINE(rp, rix); ++lines;   /* burst.c:4631-4633, 4685-4687 */
 			}
 			if (sink) for (uint64_t zz = 0; zz < rix_ix; ++zz) {      /* a read with one placement only is on one line of the file */
 				uint32_t st, ed; coords(db, RPcache[zz], RIXcache[zz], qlen, &st, &ed);
@@ -492,7 +503,7 @@ int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhR
 				}
 			}
 			uint32_t st, ed; coords(db, best, bestrix, qlen, &st, &ed);
-			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[bestrix], best, qlen, st, ed, i, wt, Final); ++lines; }
+			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[bestrix], best, qlen, st, ed, i, wt, Final); PLINE(best, bestrix); ++lines; }
 			SINK(bestrix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 		}
 	}
@@ -507,8 +518,26 @@ int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhR
 		#pragma omp single nowait
 		{
 			t_render += omp_get_wtime() - tg0;
+			if (paths && !oom && !perr) {      /* the group's lines with their paths: one trace call, then the text */
+				const uint64_t ng = cg1 - cg0;
+				char **tp_ = malloc(ng * sizeof(*tp_)); size_t *tl_ = malloc(ng * sizeof(*tl_));
+				int e_ = 0;
+				if (!tp_ || !tl_) {
+					#pragma omp atomic write
+					oom = 1;
+				} else {
+					for (uint64_t ch = cg0; ch < cg1; ++ch) { tp_[ch - cg0] = cbuf[ch].p; tl_[ch - cg0] = cbuf[ch].len; }
+					e_ = bh_paths_emit(paths, real_out, Q, hits, tp_, tl_, lbuf + cg0, ng);
+				}
+				free(tp_); free(tl_);
+				if (e_) {
+					#pragma omp atomic write
+					perr = e_;
+				}
+			}
 			for (uint64_t ch = cg0; ch < cg1; ++ch) {
-				if (!oom && cbuf[ch].len && fwrite(cbuf[ch].p, 1, cbuf[ch].len, real_out) != cbuf[ch].len) wr = 1;
+				if (paths) { free(lbuf[ch].l); lbuf[ch].l = NULL; lbuf[ch].n = lbuf[ch].cap = 0; }
+				if (!paths && !oom && cbuf[ch].len && fwrite(cbuf[ch].p, 1, cbuf[ch].len, real_out) != cbuf[ch].len) wr = 1;
 				free(cbuf[ch].p); cbuf[ch].p = NULL;
 				if (sink && !pl_append(sink, &pbuf[ch])) {
 					#pragma omp atomic write
@@ -575,8 +604,11 @@ int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhR
 	if (map_fd >= 0) close(map_fd);
 	if (use_pwrite && lseek(out_fd, file_pos, SEEK_SET) == (off_t)-1) wr = 1;      /* the stream continues behind what was written */
 	#undef SINK
-	free(cbuf); free(coff); free(pbuf);
+	#undef PLINE
+	if (lbuf) for (uint64_t ch = 0; ch < nChunks; ++ch) free(lbuf[ch].l);
+	free(cbuf); free(coff); free(pbuf); free(lbuf);
 	free(start); free(count); free(RefCounts);
+	if (perr && !oom) return perr;      /* (the text is bh_paths_emit's) */
 	if (oom) return bh_set_error(BH_E_OOM, "OOM:report");
 	if (wr) return bh_set_error(BH_E_IO, "short write on the output file");
 	if (nLines) *nLines = lines;

@@ -36,6 +36,7 @@ struct BhSession {
 	FILE *out; char *out_path;
 	char *cov_name;                 /* with a coverage: the output the loaded sample was given (names its column, also when the sample fails) */
 	BhPlaceSink sink;               /* the report's placements of the current sample (buffer kept across samples) */
+	BhPaths *paths;                 /* with o.cigar: the tracer on the reporting rank's handle, opened by the first sample that reports */
 	int dead, dbg, threads_ok;
 	int alive;                      /* query tables alive (the current sample's and the prefetched one's) */
 	pthread_mutex_t mu;             /* `alive` and its debug line */
@@ -299,13 +300,15 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		const double tr = wall();
 		uint64_t lines = 0;
 		setvbuf(s->out, NULL, _IOFBF, 1 << 22);
-		rc = bh_report_view_sink(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov ? &s->sink : NULL);
+		rc = o->cigar && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
+		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov ? &s->sink : NULL, s->paths);
 		if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
 		FILE *f = s->out; s->out = NULL;
 		if (fclose(f)) { char msg[512]; snprintf(msg, sizeof msg, "ERROR: write failed: %s", s->out_path); return sample_fail(s, res, BH_E_IO, msg); }      /* (a full disk must not end in success) */
 		close_output(s, 1);
 		res->nLines = lines; res->secReport = wall() - tr;
 		if (o->verbose) printf("Wrote %lu alignments\n", (unsigned long)lines);
+		if (o->verbose && s->paths) bh_paths_print_info(s->paths, R[s->i0].hh);
 		PHASE("consolidation, output");
 		if (o->cov) {      /* the sample's column: its placements to rank 0's device (no collective: the lines exist only here) */
 			rc = S > 1 ? bh_cov_lengths_host(o->cov) : BH_OK;      /* (database-sharded: rank 0's handle holds a slice, the default lengths come from host memory) */
@@ -333,7 +336,7 @@ void bh_session_close(BhSession *s) {
 	/* the ranks' runs belong to the caller (BhMultiRank.run); slices of the session's block must not outlive it */
 	for (int i = 0; i < s->n_local; ++i) if (s->block.hits && s->ranks[i].run.hitsPinned == 2 && s->ranks[i].run.hits >= s->block.hits && s->ranks[i].run.hits < s->block.hits + s->block.capHits) memset(&s->ranks[i].run, 0, sizeof s->ranks[i].run);
 	bh_run_free(&s->block); bh_run_free(&s->all);
-	free(s->sink.lines); free(s->cov_name);
+	free(s->sink.lines); free(s->cov_name); bh_paths_close(s->paths);
 	pthread_mutex_destroy(&s->mu);
 	free(s);
 }

@@ -270,6 +270,33 @@ int  bh_report_view(FILE *out, const BhDb *db, const BhQueries *q, const BhRunVi
 typedef struct BhPlaceSink { BhipCovLine *lines; uint64_t n, cap; } BhPlaceSink;
 int  bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx, uint64_t *nLines, BhPlaceSink *sink);
 
+/* ---- alignment paths of the printed lines (bh_paths.c; burst_hip --cigar) ----
+ * Every line gets two further tab-separated columns behind everything it has (taxonomy included): the leftmost 1-based position of the
+ * path on the ORIGINAL reference (refStart of the reference of column 2 + bhip_trace_paths' ref_first) and the CIGAR text in =XID.  The
+ * path is that of the line's RECORD (query entry, refIx, finalPos, ed): a reverse-strand line carries the path of its reverse-complement
+ * entry against the forward reference, a duplicate read its unique query's, and a record is traced once per group of report chunks
+ * whatever the number of its lines.  What stands in front of the two columns is byte for byte what the report writes without them.
+ *   bh_paths_open       the tracer is bhip_trace_paths on `hip_handle` (rank 0's: the records meet there)
+ *   bh_paths_set_trace  another tracer (tests): same arguments and return codes in this file's terms, BH_E_CAPACITY = op_off[n] ops wanted
+ *   bh_paths_push       the report's note of one printed line: index of its record in the report's record array, refStart of its reference
+ *   bh_paths_emit       n_chunks rendered chunks (text[c], text_len[c]: whole lines) and their notes, in file order, to `out`
+ *   bh_cigar_text       ops (length << 4 | code) as text; returns its length, 0 = does not fit `cap` or not an op */
+typedef struct BhPaths BhPaths;
+typedef int (*bh_paths_trace_fn)(void *ctx, const BhQueries *q, const BhipPathReq *req, uint64_t n, uint32_t *ops, uint64_t ops_cap, uint64_t *op_off,
+                                 uint32_t *ref_first, uint32_t *gap_r);
+typedef struct BhPathLine { uint64_t hit; uint32_t refOff; } BhPathLine;
+typedef struct BhPathBuf { BhPathLine *l; uint64_t n, cap; } BhPathBuf;
+int  bh_paths_open(void *hip_handle, BhPaths **paths);
+void bh_paths_set_trace(BhPaths *paths, bh_paths_trace_fn fn, void *ctx);
+void bh_paths_totals(const BhPaths *paths, uint64_t *requests, uint64_t *ops, uint64_t *lines);
+void bh_paths_print_info(BhPaths *paths, void *hip_handle);      /* one `Paths:` line on standard output: requests, ops, device milliseconds since the last one */
+void bh_paths_close(BhPaths *paths);
+int  bh_paths_push(BhPathBuf *b, uint64_t hit, uint32_t ref_off);
+int  bh_paths_emit(BhPaths *paths, FILE *out, const BhQueries *q, const BhipHit *hits, char *const *text, const size_t *text_len, const BhPathBuf *bufs, uint64_t n_chunks);
+size_t bh_cigar_text(const uint32_t *ops, uint64_t n, char *out, size_t cap);
+int  bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx, uint64_t *nLines,
+                          BhPlaceSink *sink, BhPaths *paths);
+
 /* ---- coverage and count tables per reference header and sample (bh_cov.c; burst_hip --coverage) ----
  * What embalmlets/bcov.c and embalmulate.c compute from the .b6 text, from the report's own placements: PREFIXshared.txt, PREFIXunique.txt,
  * PREFIXshared_binary.txt, PREFIXunique_binary.txt (bcov's names and format) and PREFIXcounts.txt.  The statistics are the device's
@@ -315,6 +342,7 @@ typedef struct BhSessionOpts {            /* fixed for the whole session */
 	int ingest_ahead;                     /* 1 = bh_session_prefetch parses a sample on a thread while the current one is searched and reported */
 	int verbose;                          /* 1 = the command line's per-sample lines on standard output */
 	BhCov *cov;                           /* NULL, or the coverage every reported sample feeds (rank 0's process; the caller opens it, writes the tables and closes it) */
+	int cigar;                            /* 1 = every line carries its path's position and CIGAR (bh_paths.c), traced on the handle of the rank that reports */
 } BhSessionOpts;
 typedef struct BhSampleResult {
 	int rc; char err[512];

@@ -115,7 +115,7 @@ typedef struct {
 	const char *ref_FN, *xcel_FN, *tax_FN, *list_FN;
 	BhMode mode; float thres; int z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device;
 	int n_gpus, n_gpus_given, n_dev_list, *dev_list, shard_db, n_shards; uint64_t batch; BhTaxOpts *txo;
-	const char *cov_prefix, *cov_lengths; uint32_t cov_pad;
+	const char *cov_prefix, *cov_lengths; uint32_t cov_pad; int cigar;
 } SamplesArgs;
 typedef struct { char *q, *o; int line; } Sample;
 
@@ -186,7 +186,7 @@ static int samples_main(SamplesArgs *a) {
 	BhSessionOpts so; memset(&so, 0, sizeof so);
 	so.mode = a->mode; so.thres = a->thres; so.do_rc = a->do_rc; so.incl_ws = a->incl_ws; so.z = a->z; so.do_accel = a->do_accel; so.K = K;
 	so.skip_ambig = a->skip_ambig; so.rep_flags = a->rep_flags; so.batch = a->batch; so.shard_db = shard_db ? n_shards : 0; so.tax = a->tax_FN ? a->txo : NULL;
-	so.ingest_ahead = 1; so.verbose = 1;
+	so.ingest_ahead = 1; so.verbose = 1; so.cigar = a->cigar;
 	BhSession *ses = NULL;
 	if ((rc = bh_session_open(&db, ranks, n_gpus, n_gpus, NULL, NULL, &so, &ses))) DIE(rc);
 	bh_queries_sort_device(dev_list[0]);      /* large query files are sorted on the (first) search device */
@@ -265,6 +265,8 @@ static void usage(void) {
 	puts("--accelerator-device (-ad): no .acx file, the device builds the accelerator from the .edx (word length -k, default 12)");
 	puts("--samples <list>: align a list of query files against the one resident database, each to its own output; one sample per line,");
 	puts("                  'queries<TAB>output' (in place of -q / -o; needs -r DB.edx; the database is read, uploaded and indexed once)");
+	puts("--cigar: with -q / -o or --samples, two further columns per line: the leftmost 1-based reference position of the alignment path and");
+	puts("    its CIGAR in =XID (I: query symbol without a reference column, D: reference column without a query symbol)");
 	puts("--coverage <prefix> [--coverage-lengths <file>] [--coverage-pad <int>]: with -q / -o or --samples, leave coverage and count tables per");
 	puts("                  reference and sample next to the .b6 files: <prefix>shared.txt, unique.txt, shared_binary.txt, unique_binary.txt,");
 	puts("                  counts.txt; lengths from a 'name<TAB>length' table, else the database's own extent of every reference");
@@ -274,7 +276,7 @@ static void usage(void) {
 int main(int argc, char **argv) {
 	BhMode mode = BH_CAPITALIST;                    /* burst.c:81 */
 	float thres = 0.97f;                            /* burst.c:93 */
-	int xalpha = 0;
+	int xalpha = 0, cigar = 0;
 	int dna_db = 0, dpart = 0;
 	int z = 1, do_rc = 0, incl_ws = 0, makedb = 0, do_shear = 0, do_accel = 0, dedupe = 0, device = 0, K = 0, skip_ambig = 0, threads = 0, rep_flags = 0;
 	long shear_amt = 500, db_qlen = 500;            /* burst.c:94 */
@@ -334,6 +336,7 @@ int main(int argc, char **argv) {
 		else if (!strcmp(a, "--samples")) { NEEDARG("--samples"); samples_FN = argv[i]; }
 		else if (!strcmp(a, "--make-acx")) { NEEDARG("--make-acx"); mkacx_FN = argv[i]; }
 		else if (!strcmp(a, "--coverage")) { NEEDARG("--coverage"); cov_prefix = argv[i]; }
+		else if (!strcmp(a, "--cigar")) cigar = 1;
 		else if (!strcmp(a, "--coverage-lengths")) { NEEDARG("--coverage-lengths"); cov_lengths = argv[i]; }
 		else if (!strcmp(a, "--coverage-pad")) { NEEDARG("--coverage-pad"); cov_pad = (uint32_t)strtoul(argv[i], 0, 10); }
 		else if (!strcmp(a, "--device")) { NEEDARG("--device"); device = atoi(argv[i]); }
@@ -400,6 +403,10 @@ int main(int argc, char **argv) {
 	if (n_dev_list && n_dev_list != n_gpus) { puts("ERROR: --devices must name one device per --gpus rank"); return 1; }
 	if ((cov_lengths || cov_pad) && !cov_prefix) { puts("ERROR: --coverage-lengths and --coverage-pad go with --coverage <prefix>"); return 1; }
 	if (cov_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --coverage works from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	/* (refused before a device is touched: the paths are traced on ONE handle that holds the whole database in the nucleotide alphabet) */
+	if (cigar && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --cigar adds the alignment paths to the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (cigar && (shard_db || n_shards)) { puts("ERROR: --cigar traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
+	if (cigar && !gather_host) { puts("ERROR: --cigar takes the host gather only (drop --gather rccl)"); return 1; }
 	if (samples_FN) {
 		/* per sample what a separate invocation writes; everything checked here is checked before a device is touched.  Out of scope:
 		 * per-sample identity / mode, FASTA references, -x, serial shards and the RCCL gather (refused below and in samples_main) */
@@ -409,7 +416,7 @@ int main(int argc, char **argv) {
 		if (!gather_host) { puts("ERROR: --samples takes the host gather only (drop --gather rccl)"); return 1; }
 		if (accel_dev && xcel_FN) { puts("ERROR: -ad builds the accelerator on the device; drop -a"); return 1; }
 		SamplesArgs sa = {ref_FN, xcel_FN, tax_FN, samples_FN, mode, thres, z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device,
-		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo, cov_prefix, cov_lengths, cov_pad};
+		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo, cov_prefix, cov_lengths, cov_pad, cigar};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
@@ -666,9 +673,12 @@ int main(int argc, char **argv) {
 	uint64_t lines = 0;
 	setvbuf(output, NULL, _IOFBF, 1 << 22);
 	BhPlaceSink sink; memset(&sink, 0, sizeof sink);
-	if ((rc = bh_report_view_sink(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov ? &sink : NULL))) DIE(rc);
+	BhPaths *paths = NULL;
+	if (cigar && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
+	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov ? &sink : NULL, paths))) DIE(rc);
 	if (fclose(output)) { fprintf(stderr, "ERROR: write failed: %s\n", output_FN); return 2; }      /* (the last buffer of the report: a full disk must not end in exit code 0) */
 	printf("Wrote %lu alignments\n", (unsigned long)lines);
+	if (paths) bh_paths_print_info(paths, hhs[0]);
 	PHASE("consolidation, output");
 	if (cov) {      /* a study of one sample: the Dataset column and the sample's (rank 0's handle; the lines exist only here) */
 		if ((shard_db && (rc = bh_cov_lengths_host(cov))) || (rc = bh_cov_sample(cov, hhs[0], output_FN, sink.lines, sink.n)) || (rc = bh_cov_write(cov))) DIE(rc);
@@ -682,7 +692,7 @@ int main(int argc, char **argv) {
 	 * second for a 32 M-read job; the operating system releases a finished process's memory (host and device) far faster.
 	 * BURST_HOST_TEARDOWN=1 walks through the orderly release instead (leak checks). */
 	if (!getenv("BURST_HOST_TEARDOWN")) _exit(0);
-	bh_cov_close(cov); free(sink.lines);
+	bh_cov_close(cov); free(sink.lines); bh_paths_close(paths);
 	if (comm) bhip_comm_destroy(comm);
 	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
 	for (int r = 0; r < n_gpus; ++r) bh_run_free(&ranks[r].run);

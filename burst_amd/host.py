@@ -86,7 +86,7 @@ class BhTaxOpts(C.Structure):
 class BhSessionOpts(C.Structure):
     _fields_ = [("mode", C.c_int), ("thres", C.c_float), ("do_rc", C.c_int), ("incl_ws", C.c_int), ("z", C.c_int), ("do_accel", C.c_int), ("K", C.c_int),
                 ("skip_ambig", C.c_int), ("rep_flags", C.c_int), ("batch", C.c_uint64), ("shard_db", C.c_int), ("tax", C.POINTER(BhTaxOpts)),
-                ("ingest_ahead", C.c_int), ("verbose", C.c_int), ("cov", C.c_void_p)]
+                ("ingest_ahead", C.c_int), ("verbose", C.c_int), ("cov", C.c_void_p), ("cigar", C.c_int)]
 
 
 COV_TAP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64)
@@ -178,6 +178,15 @@ def lib():
         L.bh_session_set_node.restype = None
         L.bh_session_ended.argtypes = [C.c_void_p]
         L.bh_session_close.argtypes = [C.c_void_p]
+        L.bh_paths_open.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.bh_paths_close.argtypes = [C.c_void_p]
+        L.bh_paths_close.restype = None
+        L.bh_paths_totals.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.bh_paths_totals.restype = None
+        L.bh_cigar_text.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+        L.bh_cigar_text.restype = C.c_size_t
+        L.bh_report_view_paths.argtypes = [C.c_void_p, C.POINTER(BhDb), C.POINTER(BhQueries), C.POINTER(BhRunView), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64),
+                                           C.c_void_p, C.c_void_p]
         L.bh_session_close.restype = None
         L.bh_cov_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]
         L.bh_cov_set_tap.argtypes = [C.c_void_p, COV_TAP_FN, C.c_void_p]
@@ -538,8 +547,11 @@ class Session:
     def __init__(self, db, devs=None, mode="CAPITALIST", thres=0.97, rc=False, whitespace=False, z=1, accel=None, K=0, batch=1 << 21, shard_db=0,
                  taxonomy=None, taxacut=10, tax_ncbi=False, tax_suppress=False, tax_strict=False, rep_flags=0, ingest_ahead=True,
                  align=None, reduce_min=None, rank=0, world=None, c0=0, node=None, comm=None, verbose=False,
-                 coverage=None, coverage_lengths=None, coverage_pad=0, coverage_tap=None):
-        """coverage = prefix: every reported sample feeds the coverage (bh_cov.c) on rank 0's device handle; close() writes the five tables
+                 coverage=None, coverage_lengths=None, coverage_pad=0, coverage_tap=None, cigar=False):
+        """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
+        reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
+        process only).
+        coverage = prefix: every reported sample feeds the coverage (bh_cov.c) on rank 0's device handle; close() writes the five tables
         prefix{shared,unique,shared_binary,unique_binary,counts}.txt unless the session ended on an error; coverage() returns the integer
         statistics.  coverage_lengths: a `name<TAB>length` table (default: the database's own extents); coverage_tap(sample, lines):
         called with every sample's placements (capi.COV_LINE_DTYPE) before they go to the device, a true return keeps them from it."""
@@ -564,6 +576,12 @@ class Session:
         o = BhSessionOpts()
         o.mode, o.thres, o.do_rc, o.incl_ws, o.z, o.do_accel, o.K = MODES[mode], thres, int(rc), int(whitespace), z, int(accel), int(db.c.K) if db.c.hasAcx else K
         o.rep_flags, o.batch, o.shard_db, o.ingest_ahead, o.verbose = rep_flags, batch, int(shard_db), int(ingest_ahead), int(verbose)
+        if cigar:
+            if shard_db and int(shard_db) > 1:
+                raise ValueError("cigar: the paths are traced on one handle, which must hold the whole database (no shard_db)")
+            if align is not None or world != n_local:
+                raise ValueError("cigar: needs the device handles of one process (no align back end, no job of processes)")
+            o.cigar = 1
         if taxonomy:
             _chk(lib().bh_tax_load(taxonomy.encode(), C.byref(self.tax)))
             self.taxo.tax, self.taxo.suppress, self.taxo.strict, self.taxo.taxacut, self.taxo.ncbi = C.pointer(self.tax), int(tax_suppress), int(tax_strict), taxacut, int(tax_ncbi)
@@ -800,17 +818,38 @@ def clump_shard(db, world, rank):
     return int(c0.value), int(c1.value)
 
 
-def report(path, db, qs, hits, mode, flags=0):
-    """hits: HIT_DTYPE array with q = global entry index, records of one entry contiguous"""
+def cigar_text(ops):
+    """ops of one path (uint32 words length << 4 | code) as the report renders them (bh_cigar_text); raises on anything that is not an op"""
+    ops = np.ascontiguousarray(ops, np.uint32)
+    buf = C.create_string_buffer(12 * len(ops) + 2)
+    n = lib().bh_cigar_text(ops.ctypes.data, len(ops), buf, len(buf))
+    if not n:
+        raise HostError("not a path: %r" % (ops.tolist(),))
+    return buf.raw[:n].decode()
+
+
+def report(path, db, qs, hits, mode, flags=0, cigar=None):
+    """hits: HIT_DTYPE array with q = global entry index, records of one entry contiguous.  cigar: the capi.Device that holds the
+    database -- every line then carries its path's position and CIGAR (bh_paths.c; bhip_trace_paths on that handle)"""
     f = libc.fopen(path.encode(), b"wb")
     if not f:
         raise HostError("cannot open %s" % path)
     n = C.c_uint64()
     hits = np.ascontiguousarray(hits)
+    paths = C.c_void_p()
     try:
-        _chk(lib().bh_report_ex(f, C.byref(db.c), C.byref(qs.c), hits.ctypes.data_as(C.c_void_p), len(hits), MODES[mode], flags, C.byref(n)))
+        if cigar is not None:
+            _chk(lib().bh_paths_open(cigar._h, C.byref(paths)))
+            view = BhRunView()
+            view.base, view.n_runs, view.total = hits.ctypes.data, 1, len(hits)
+            view.off[0], view.n[0] = 0, len(hits)
+            _chk(lib().bh_report_view_paths(f, C.byref(db.c), C.byref(qs.c), C.byref(view), MODES[mode], flags, None, C.byref(n), None, paths))
+        else:
+            _chk(lib().bh_report_ex(f, C.byref(db.c), C.byref(qs.c), hits.ctypes.data_as(C.c_void_p), len(hits), MODES[mode], flags, C.byref(n)))
     finally:
         libc.fclose(f)
+        if paths:
+            lib().bh_paths_close(paths)
     return int(n.value)
 
 

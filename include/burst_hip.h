@@ -327,6 +327,36 @@ BHIP_API int bhip_cov_info(void *handle, uint64_t info[8]);
 BHIP_API int bhip_cov_end(void *handle);
 BHIP_API int bhip_lane_extents(void *handle, uint32_t *extents);
 
+/* The alignment PATH of placements (burst_hip --cigar; no reference counterpart: the reference reports how many mismatches and gaps a
+ * placement has, never where).  A request names a record of the search: query entry q of the caller's batch (q_codes / q_off as in
+ * bhip_align_batch), refIx, finalPos and ed as in BhipHit.  The path is the one the re-scorer's own recurrence (reScoreM_mat16,
+ * burst.c:713-886) decides: every cell of its matrix has a decision -- row 1: L if the cell's cost is 1 and the cell to its left scored 0
+ * (burst.c:722-739), else D; column 0: U; elsewhere D if the diagonal is kept (burst.c:771-779), U if it is not, L if the second comparison
+ * fails (789-795) -- and the path follows the decisions from cell (m, finalPos), which must score ed, back to row 0.  Read forwards:
+ * D with cost 0 is '=', D with cost 1 is 'X', U is 'I' (a query symbol without a reference column), L is 'D' (a reference column without
+ * a query symbol).  By construction '=' + X + I = the query's length, X + I + D = ed, D = the record's gapQ, and I = V of the FINAL cell --
+ * which is the record's gapR whenever the best (score, H) of the last row is attained in one end column only, and may differ otherwise
+ * (the reference takes gapR from the first such column and finalPos from the last, burst.c:824-885).
+ *   ops       32-bit words length << 4 | code with BAM's codes (I = 1, D = 2, '=' = 7, X = 8), runs merged, in forward order; request i
+ *             owns ops[op_off[i] .. op_off[i + 1]); op_off has n_requests + 1 entries
+ *   ref_first [i] = the first reference column the path consumes, 1-based in the sheared lane (the column after the one where row 0 is reached)
+ *   gap_r     [i] = the path's number of I
+ * BHIP_E_ARG (before any device memory is touched) when a request names a query >= n_queries, a reference >= 16 n_clumps or >= tot_refs,
+ * an end column outside 1 .. ClumpLen, a query of 0 or more than BHIP_MAX_QLEN symbols, or ed > 254; BHIP_E_CAPACITY when ops_cap is too small
+ * (op_off is complete: op_off[n_requests] is the count needed; ref_first and gap_r are valid, ops is not); BHIP_E_RESCORE when cell
+ * (m, finalPos) of a request does not score ed -- bhip_last_error names the first such request.  Query symbols are uploaded per call in
+ * chunks of bounded size; the references are the resident ones.
+ * bhip_paths_info: [0] device microseconds of the last bhip_trace_paths call (HIP events around its kernels), [1] of all calls, [2] requests
+ * and [3] ops of all calls that returned BHIP_OK or BHIP_E_CAPACITY. */
+typedef struct BhipPathReq { uint32_t q, refIx, finalPos, ed; } BhipPathReq;
+#define BHIP_OP_I  1u
+#define BHIP_OP_D  2u
+#define BHIP_OP_EQ 7u
+#define BHIP_OP_X  8u
+BHIP_API int bhip_trace_paths(void *handle, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPathReq *requests, uint64_t n_requests,
+                              uint32_t *ops, uint64_t ops_cap, uint64_t *op_off, uint32_t *ref_first, uint32_t *gap_r);
+BHIP_API int bhip_paths_info(void *handle, uint64_t info[4]);
+
 /* Tuning knobs.  "prefilter_stride": 0 (default) = automatic sparse seeds -- per query the largest stride s <= K for
  * which an alignment within budget still keeps >= 3 of the words starting at 0, s, 2s, ... (one edit destroys at most
  * ceil(K/s) of them), fewest .acx look-ups with the same no-false-negative guarantee; s >= 1 forces every s-th word,
