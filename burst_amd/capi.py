@@ -48,7 +48,15 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_comm_create", "bhip_comm_unique_id", "bhip_comm_create_rank", "bhip_comm_allreduce_min", "bhip_comm_fetch_gathered", "bhip_comm_gather_hits", "bhip_comm_stage_device", "bhip_comm_gather_staged", "bhip_comm_stage_reset", "bhip_comm_destroy", "bhip_acx_export", "bhip_reserve", "bhip_reserve_symbols", "bhip_sort_queries", "bhip_stage_spans", "bhip_alloc_host", "bhip_free_host", "bhip_host_register", "bhip_host_unregister", "bhip_set_enqueued_hook", "bhip_acx_export_entries",
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
-           "bhip_trace_paths", "bhip_paths_info"]
+           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info"]
+
+# BhipMateLine, 20 bytes: pair and header numbers, .b6 columns 9 and 10 (signed), column 11
+MATE_LINE_DTYPE = np.dtype([("pair", "<u4"), ("ref", "<u4"), ("st", "<i4"), ("ed", "<i4"), ("edits", "<u4")])
+assert MATE_LINE_DTYPE.itemsize == 20
+MATES_FR, MATES_RF, MATES_FF = 0, 1, 2
+MATES_ALL, MATES_BEST = 0, 1
+MATES_ORIENTATIONS = {"fr": MATES_FR, "rf": MATES_RF, "ff": MATES_FF}
+MATES_REPORTS = {"all": MATES_ALL, "best": MATES_BEST}
 
 # BhipPathReq, 16 bytes: query entry, refIx, finalPos, ed of a record
 PATH_REQ_DTYPE = np.dtype([("q", "<u4"), ("refIx", "<u4"), ("finalPos", "<u4"), ("ed", "<u4")])
@@ -65,6 +73,15 @@ def cigar_text(ops):
 # BhipCovLine, 16 bytes: header, .b6 columns 9 and 10, weight (bits 0..30) | unique << 31
 COV_LINE_DTYPE = np.dtype([("ref", "<u4"), ("st", "<u4"), ("ed", "<u4"), ("w", "<u4")])
 assert COV_LINE_DTYPE.itemsize == 16
+
+
+def _mate_lines(rows):
+    """rows (pair, ref, st, ed, edits) as a MATE_LINE_DTYPE array"""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 5)
+    out = np.zeros(len(rows), MATE_LINE_DTYPE)
+    for k, name in enumerate(MATE_LINE_DTYPE.names):
+        out[name] = rows[:, k]
+    return out
 
 
 class BurstHipError(RuntimeError):
@@ -162,6 +179,10 @@ def _load():
     lib.bhip_trace_paths.restype = i32
     lib.bhip_paths_info.argtypes = [vp, vp]
     lib.bhip_paths_info.restype = i32
+    lib.bhip_mates_join.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, u32, vp, vp, u64, C.POINTER(u64)]
+    lib.bhip_mates_join.restype = i32
+    lib.bhip_mates_info.argtypes = [vp, vp]
+    lib.bhip_mates_info.restype = i32
     for f in (lib.bhip_cov_begin, lib.bhip_cov_add, lib.bhip_cov_sample_stats, lib.bhip_cov_dataset_stats, lib.bhip_cov_info, lib.bhip_cov_end, lib.bhip_lane_extents):
         f.restype = i32
     return lib
@@ -382,6 +403,31 @@ class Device:
         info = np.zeros(4, np.uint64)
         _chk(lib().bhip_paths_info(self._h, _ptr(info)))
         return dict(zip(("us_last", "us_total", "requests", "ops"), (int(x) for x in info)))
+
+    def mates_join(self, a, b, orientation="fr", ins_min=0, ins_max=1000, report="all", cap=None):
+        """concordant combinations of two mates' lines (bhip_mates_join).  a, b: MATE_LINE_DTYPE arrays (or rows pair, ref, st, ed, edits);
+        orientation fr / rf / ff and report all / best by name or number.  Returns (out_a, out_b): indices into a and b, ascending (a, b).
+        cap: room offered at first (default: one combination per line of a); a capacity answer is retried once with the wanted room"""
+        a, b = (x if isinstance(x, np.ndarray) and x.dtype == MATE_LINE_DTYPE else _mate_lines(x) for x in (a, b))
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        orientation = MATES_ORIENTATIONS.get(orientation, orientation)
+        report = MATES_REPORTS.get(report, report)
+        cap = len(a) if cap is None else int(cap)
+        n = C.c_uint64(0)
+        for _ in range(2):
+            out_a, out_b = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+            rc = lib().bhip_mates_join(self._h, _ptr(a), len(a), _ptr(b), len(b), int(orientation), int(ins_min), int(ins_max), int(report),
+                                       _ptr(out_a), _ptr(out_b), cap, C.byref(n))
+            if rc != BHIP_E_CAPACITY or n.value <= cap:
+                break
+            cap = n.value
+        _chk(rc)
+        return out_a[:n.value], out_b[:n.value]
+
+    def mates_info(self):
+        info = np.zeros(4, np.uint64)
+        _chk(lib().bhip_mates_info(self._h, _ptr(info)))
+        return dict(zip(("us_last", "us_total", "lines", "combinations"), (int(x) for x in info)))
 
     def cov_begin(self, lengths, pad=0):
         """coverage over len(lengths) reference headers (bhip_cov_begin); cov_add() one whole sample at a time"""

@@ -446,6 +446,7 @@ struct Handle {
 	double acx_wmean = 0.0;       // occurrence-weighted mean .acx list length
 	void *cov = nullptr;          // coverage state between bhip_cov_begin and bhip_cov_end (bhip_cov.hip)
 	void *paths = nullptr;        // buffers, events and totals of bhip_trace_paths (bhip_paths.hip), made by the first call
+	void *mates = nullptr;        // buffers, events and totals of bhip_mates_join (bhip_mates.hip), made by the first call that launches
 	long long opt_cov_event_cap = 0;   // bytes the coverage event sets may take before they are compacted (0 = a fifth of the memory free at the first bhip_cov_add)
 };
 
@@ -462,4 +463,5 @@ int  bhip_load_accelerator(Handle *h, const uint32_t *acx_lens, const void *acx_
 int  bhip_build_accelerator(Handle *h, int K, int z);
 void bhip_cov_release(Handle *h);                                            // bhip_cov.hip
 void bhip_paths_release(Handle *h);                                          // bhip_paths.hip
+void bhip_mates_release(Handle *h);                                          // bhip_mates.hip
 #endif

@@ -72,6 +72,7 @@ extern "C" void bhip_destroy(void *handle) {
 	for (StageSlot &S : h->slots) S.release_all();
 	bhip_cov_release(h);
 	bhip_paths_release(h);
+	bhip_mates_release(h);
 	if (h->hsc_pinned) (void)hipHostFree(h->hsc_pinned);
 	if (h->nsel_pinned) (void)hipHostFree(h->nsel_pinned);
 	for (Lane *L : h->lanes) lane_destroy(L);

@@ -36,6 +36,7 @@ struct BhSession {
 	FILE *out; char *out_path;
 	char *cov_name;                 /* with a coverage: the output the loaded sample was given (names its column, also when the sample fails) */
 	BhPlaceSink sink;               /* the report's placements of the current sample (buffer kept across samples) */
+	BhMates *mates;                 /* bh_session_run_mates: the joiner, made on first use */
 	BhPaths *paths;                 /* with o.cigar: the tracer on the reporting rank's handle, opened by the first sample that reports */
 	int dead, dbg, threads_ok;
 	int alive;                      /* query tables alive (the current sample's and the prefetched one's) */
@@ -328,6 +329,76 @@ int bh_session_run(BhSession *s, const char *queries, const char *out_path, BhSa
 	return rc ? rc : bh_session_finish(s, res);
 }
 
+BhMates *bh_session_mates(BhSession *s) {
+	if (s && !s->mates && bh_mates_open(NULL, &s->mates)) return NULL;
+	return s ? s->mates : NULL;
+}
+
+static void add_result(BhSampleResult *t, const BhSampleResult *a) {
+	t->totQ += a->totQ; t->numUniq += a->numUniq; t->nHits += a->nHits; t->nBatches += a->nBatches;
+	t->secIngest += a->secIngest; t->secIngestWaited += a->secIngestWaited; t->secSearch += a->secSearch; t->secReport += a->secReport;
+	sum_stats(&t->total, &a->total);
+}
+static int mates_fail(BhSession *s, BhSampleResult *res, int rc, const char *msg) {
+	res->rc = rc;
+	snprintf(res->err, sizeof res->err, "%s", msg);
+	if (rc != BH_E_USAGE && rc != BH_E_IO) s->dead = rc;
+	return bh_set_error(rc, "%s", res->err);
+}
+
+int bh_session_run_mates(BhSession *s, const char *queries1, const char *queries2, const char *out_path, BhSampleResult *res) {
+	BhSampleResult tmp, one;
+	if (!res) res = &tmp;
+	memset(res, 0, sizeof *res);
+	if (!s || !queries1 || !queries2) return bh_set_error(BH_E_USAGE, "bh_session_run_mates: no session / no files");
+	if (s->o.mode != BH_ALLPATHS && s->o.mode != BH_FORAGE) return mates_fail(s, res, BH_E_USAGE, "ERROR: mates are joined from ALLPATHS or FORAGE placements (the other modes discard the ties the join needs)");
+	if (!s->o.do_rc) return mates_fail(s, res, BH_E_USAGE, "ERROR: mates need both strands searched (-fr)");
+	if (s->o.cov || s->o.cigar) return mates_fail(s, res, BH_E_USAGE, "ERROR: coverage and alignment paths of paired output are out of scope: mates go with neither");
+	if (s->o.mates.orientation > BHIP_MATES_FF || s->o.mates.report > BHIP_MATES_BEST || s->o.mates.ins_min > s->o.mates.ins_max)
+		return mates_fail(s, res, BH_E_USAGE, "ERROR: mates: orientation fr|rf|ff, report all|best, insert-min <= insert-max");
+	if (s->dead) { res->rc = s->dead; snprintf(res->err, sizeof res->err, "the session was ended by an earlier error (code %d)", s->dead); return bh_set_error(s->dead, "%s", res->err); }
+	const int writes = out_path && s->i0 >= 0;      /* (in a job of processes only rank 0 holds lines) */
+	char *t1 = NULL, *t2 = NULL, *to = NULL;
+	if (writes) {
+		const size_t n = strlen(out_path) + 16;
+		t1 = malloc(n); t2 = malloc(n); to = malloc(n);
+		if (!t1 || !t2 || !to) { free(t1); free(t2); free(to); return mates_fail(s, res, BH_E_OOM, "OOM:session"); }
+		snprintf(t1, n, "%s.mate1.tmp", out_path); snprintf(t2, n, "%s.mate2.tmp", out_path); snprintf(to, n, "%s.tmp", out_path);
+		if (!bh_session_mates(s)) { free(t1); free(t2); free(to); return mates_fail(s, res, BH_E_OOM, "OOM:mates"); }
+	}
+	int rc = BH_OK;
+	const char *qs[2] = {queries1, queries2};
+	for (int k = 0; k < 2 && !rc; ++k) {
+		if (!k) bh_session_prefetch(s, queries2);      /* mate 2 is parsed while mate 1 is searched */
+		if (s->o.verbose) printf("Mate %d: %s\n", k + 1, qs[k]);
+		rc = bh_session_load(s, qs[k], writes ? (k ? t2 : t1) : NULL, &one);
+		if (!rc && writes && (rc = bh_mates_names(s->mates, k, s->cur->Q.heads, s->cur->Q.totQ))) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); rc = sample_fail(s, &one, rc, msg); }
+		if (!rc) rc = bh_session_finish(s, &one);
+		add_result(res, &one);
+		if (rc) { res->rc = rc; snprintf(res->err, sizeof res->err, "%s", one.err); }
+	}
+	if (!rc && writes) {
+		const double tj = wall();
+		FILE *f = fopen(to, "wb");
+		if (!f) { char msg[512]; snprintf(msg, sizeof msg, "ERROR: Cannot open output: %s", to); rc = mates_fail(s, res, BH_E_IO, msg); }
+		else {
+			setvbuf(f, NULL, _IOFBF, 1 << 22);
+			bh_mates_set_handle(s->mates, s->ranks[s->i0].hh);
+			uint64_t lines = 0;
+			rc = bh_mates_join_files(s->mates, t1, t2, f, &s->o.mates, &lines);
+			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); fclose(f); rc = mates_fail(s, res, rc, msg); }
+			else if (fclose(f) || rename(to, out_path)) { char msg[512]; snprintf(msg, sizeof msg, "ERROR: write failed: %s", out_path); rc = mates_fail(s, res, BH_E_IO, msg); }
+			else {
+				res->nLines = lines; res->secReport += wall() - tj;
+				if (s->o.verbose) { printf("Wrote %lu lines of %lu concordant combinations\n", (unsigned long)lines, (unsigned long)(lines / 2)); bh_mates_print_info(s->mates); }
+			}
+		}
+	}
+	if (writes) { (void)unlink(t1); (void)unlink(t2); if (rc) (void)unlink(to); }
+	free(t1); free(t2); free(to);
+	return rc;
+}
+
 void bh_session_close(BhSession *s) {
 	if (!s) return;
 	if (s->ahead) { pthread_join(s->th, NULL); ingest_free(s->ahead); s->ahead = NULL; }
@@ -336,7 +407,7 @@ void bh_session_close(BhSession *s) {
 	/* the ranks' runs belong to the caller (BhMultiRank.run); slices of the session's block must not outlive it */
 	for (int i = 0; i < s->n_local; ++i) if (s->block.hits && s->ranks[i].run.hitsPinned == 2 && s->ranks[i].run.hits >= s->block.hits && s->ranks[i].run.hits < s->block.hits + s->block.capHits) memset(&s->ranks[i].run, 0, sizeof s->ranks[i].run);
 	bh_run_free(&s->block); bh_run_free(&s->all);
-	free(s->sink.lines); free(s->cov_name); bh_paths_close(s->paths);
+	free(s->sink.lines); free(s->cov_name); bh_paths_close(s->paths); bh_mates_close(s->mates);
 	pthread_mutex_destroy(&s->mu);
 	free(s);
 }

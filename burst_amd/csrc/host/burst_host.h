@@ -297,6 +297,35 @@ size_t bh_cigar_text(const uint32_t *ops, uint64_t n, char *out, size_t cap);
 int  bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx, uint64_t *nLines,
                           BhPlaceSink *sink, BhPaths *paths);
 
+/* ---- paired-end reads: two mates' printed lines joined into concordant combinations (bh_mates.c; burst_hip --mates) ----
+ * The definition is bhip_mates_join's (include/burst_hip.h) over the lines two single-end runs print; a reported combination is written as
+ * mate 1's line and mate 2's line, each followed by two tab-separated columns: the fragment's 1-based leftmost position and its length.
+ *   bh_mates_open        the joiner is bhip_mates_join on `hip_handle` (may be NULL until bh_mates_set_handle names it)
+ *   bh_mates_set_join    another joiner (tests): same arguments and return codes in this file's terms, BH_E_CAPACITY = *n_out combinations
+ *                        wanted (the call is repeated once with that room); fn = NULL: the device again
+ *   bh_mates_names       the read names of mate file `side` (0, then 1) as column 1 prints them: a new pair of files starts with side 0
+ *   bh_mates_join_files  the two single-end outputs (paths of their texts) -> the paired output on `out`; *n_lines = lines written
+ *   bh_mates_stats       the figures of the last pair of files; bh_mates_print_info: the `Mates:` line on standard output */
+typedef struct BhMates BhMates;
+typedef struct BhMatesOpts { uint32_t orientation, ins_min, ins_max, report; } BhMatesOpts;      /* BHIP_MATES_FR / RF / FF, bounds of the fragment length, BHIP_MATES_ALL / BEST */
+typedef struct BhMatesStats {
+	uint64_t reads1, reads2;              /* reads in each file */
+	uint64_t pairsNamed, pairsPlaced;     /* pair names in both files; of those, with a line on both sides */
+	uint64_t lines1, lines2;              /* lines of the two single-end outputs */
+	uint64_t examined, written;           /* combinations with equal pair and header; combinations reported (two lines each) */
+	double deviceMs;                      /* device time of the join (0 with another joiner) */
+} BhMatesStats;
+typedef int (*bh_mates_join_fn)(void *ctx, const BhipMateLine *a, uint64_t na, const BhipMateLine *b, uint64_t nb, uint32_t orientation, uint32_t ins_min,
+                                uint32_t ins_max, uint32_t report, uint32_t *out_a, uint32_t *out_b, uint64_t cap, uint64_t *n_out);
+int  bh_mates_open(void *hip_handle, BhMates **mates);
+void bh_mates_set_handle(BhMates *mates, void *hip_handle);
+void bh_mates_set_join(BhMates *mates, bh_mates_join_fn fn, void *ctx);
+int  bh_mates_names(BhMates *mates, int side, char *const *heads, uint64_t n);
+int  bh_mates_join_files(BhMates *mates, const char *lines1, const char *lines2, FILE *out, const BhMatesOpts *o, uint64_t *n_lines);
+void bh_mates_stats(const BhMates *mates, BhMatesStats *st);
+void bh_mates_print_info(const BhMates *mates);
+void bh_mates_close(BhMates *mates);
+
 /* ---- coverage and count tables per reference header and sample (bh_cov.c; burst_hip --coverage) ----
  * What embalmlets/bcov.c and embalmulate.c compute from the .b6 text, from the report's own placements: PREFIXshared.txt, PREFIXunique.txt,
  * PREFIXshared_binary.txt, PREFIXunique_binary.txt (bcov's names and format) and PREFIXcounts.txt.  The statistics are the device's
@@ -343,6 +372,7 @@ typedef struct BhSessionOpts {            /* fixed for the whole session */
 	int verbose;                          /* 1 = the command line's per-sample lines on standard output */
 	BhCov *cov;                           /* NULL, or the coverage every reported sample feeds (rank 0's process; the caller opens it, writes the tables and closes it) */
 	int cigar;                            /* 1 = every line carries its path's position and CIGAR (bh_paths.c), traced on the handle of the rank that reports */
+	BhMatesOpts mates;                    /* bh_session_run_mates: orientation, bounds of the fragment length, report (all zero: fr, [0, 0], all -- set the bounds) */
 } BhSessionOpts;
 typedef struct BhSampleResult {
 	int rc; char err[512];
@@ -370,6 +400,14 @@ int  bh_session_load(BhSession *s, const char *queries, const char *out_path, Bh
 int  bh_session_finish(BhSession *s, BhSampleResult *res);
 int  bh_session_drop(BhSession *s);
 int  bh_session_run(BhSession *s, const char *queries, const char *out_path, BhSampleResult *res);
+/* a pair of mate files: queries1 and then queries2 through the per-sample path above (queries2's ingest ahead, beside queries1's
+ * search), each into a temporary file beside out_path; the two outputs joined (bh_mates.c, on the handle of the rank that reports) into
+ * out_path, written under a temporary name and renamed.  Needs mode ALLPATHS or FORAGE, do_rc, no coverage and no cigar (BH_E_USAGE
+ * otherwise, before anything runs).  `res`: the two mates' counts and times summed, nLines = lines of the paired output.  A mate file that
+ * fails fails the pair under the rule above; no output and no temporary file stays.  bh_session_mates: the session's joiner object (made
+ * on first use: bh_mates_set_join, bh_mates_stats). */
+int  bh_session_run_mates(BhSession *s, const char *queries1, const char *queries2, const char *out_path, BhSampleResult *res);
+BhMates *bh_session_mates(BhSession *s);
 const BhQueries *bh_session_sample(const BhSession *s);
 void bh_session_set_node(BhSession *s, BhNode *node);
 void bh_session_set_coverage(BhSession *s, BhCov *cov);      /* BhSessionOpts.cov for a session opened before its database was read */

@@ -4,6 +4,8 @@
  *   burst_hip -r refs.fa -q reads.fa -o out.b6 [-s [len]]            direct FASTA (exhaustive, no accelerator)
  *   burst_hip -r refs.fa -d [QUICK|DNA|RNA] [qLen] -o DB.edx [-a DB.acx] [-s [len]] [-dp N] -i 0.97      database construction
  *   burst_hip -r DB.edx (-a DB.acx | -ad) --samples LIST -m ... -i ...    a list of `queries<TAB>output` against the one resident database (bh_session.c)
+ *   burst_hip -r DB.edx (-a DB.acx | -ad) -q R1.fq --mates R2.fq -o out.b6 -m ALLPATHS|FORAGE -i ... [--insert-min N] [--insert-max N]
+ *             [--mates-orientation fr|rf|ff] [--mates-report all|best]      paired-end reads: the concordant combinations of the two mates' placements (bh_mates.c)
  *   ... -q / -o or --samples ... --coverage PREFIX [--coverage-lengths FILE] [--coverage-pad N]      coverage and count tables per reference and sample (bh_cov.c)
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
@@ -116,10 +118,12 @@ typedef struct {
 	BhMode mode; float thres; int z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device;
 	int n_gpus, n_gpus_given, n_dev_list, *dev_list, shard_db, n_shards; uint64_t batch; BhTaxOpts *txo;
 	const char *cov_prefix, *cov_lengths; uint32_t cov_pad; int cigar;
+	const char *q1_FN, *mates_FN, *out_FN;      /* --mates: the one pair of -q / --mates / -o in place of a list (list_FN = NULL) */
+	BhMatesOpts mates; int mates_opts_given;
 } SamplesArgs;
-typedef struct { char *q, *o; int line; } Sample;
+typedef struct { char *q, *o, *m; int line; } Sample;      /* m: the mates file of a three-field line, or NULL */
 
-/* `queries<TAB>output` per line; blank lines and lines that start with '#' are skipped.  Returns 0 or the exit code. */
+/* `queries<TAB>output` or `queries<TAB>output<TAB>mates` per line; blank lines and lines that start with '#' are skipped.  Returns 0 or the exit code. */
 static int read_sample_list(const SamplesArgs *a, Sample **out, int *n_out) {
 	FILE *f = fopen(a->list_FN, "rb");
 	if (!f) { fprintf(stderr, "ERROR: Cannot open sample list: %s\n", a->list_FN); return 2; }
@@ -131,18 +135,20 @@ static int read_sample_list(const SamplesArgs *a, Sample **out, int *n_out) {
 		while (len && (buf[len - 1] == '\n' || buf[len - 1] == '\r')) buf[--len] = 0;
 		if (!len || buf[0] == '#') continue;
 		char *tab = strchr(buf, '\t');
-		if (!tab || tab == buf || !tab[1] || strchr(tab + 1, '\t')) { printf("ERROR: %s line %d: expected 'queries<TAB>output'\n", a->list_FN, line); fclose(f); return 1; }
+		char *tab2 = tab ? strchr(tab + 1, '\t') : NULL;
+		if (!tab || tab == buf || !tab[1] || tab2 == tab + 1 || (tab2 && (!tab2[1] || strchr(tab2 + 1, '\t')))) { printf("ERROR: %s line %d: expected 'queries<TAB>output' or 'queries<TAB>output<TAB>mates'\n", a->list_FN, line); fclose(f); return 1; }
 		*tab = 0;
+		if (tab2) *tab2 = 0;
 		if (n == cap) { cap = cap ? 2 * cap : 64; S = realloc(S, (size_t)cap * sizeof(*S)); if (!S) { fclose(f); fputs("OOM:samples\n", stderr); return 3; } }
-		S[n].q = strdup(buf); S[n].o = strdup(tab + 1); S[n].line = line;
-		if (!S[n].q || !S[n].o) { fclose(f); fputs("OOM:samples\n", stderr); return 3; }
+		S[n].q = strdup(buf); S[n].o = strdup(tab + 1); S[n].m = tab2 ? strdup(tab2 + 1) : NULL; S[n].line = line;
+		if (!S[n].q || !S[n].o || (tab2 && !S[n].m)) { fclose(f); fputs("OOM:samples\n", stderr); return 3; }
 		++n;
 	}
 	free(buf); fclose(f);
 	if (!n) { printf("ERROR: %s names no sample\n", a->list_FN); return 1; }
 	for (int i = 0; i < n; ++i) {
 		for (int k = 0; k < i; ++k) if (!strcmp(S[i].o, S[k].o)) { printf("ERROR: %s line %d: output '%s' is the output of line %d already\n", a->list_FN, S[i].line, S[i].o, S[k].line); return 1; }
-		for (int k = 0; k < n; ++k) if (!strcmp(S[i].o, S[k].q)) { printf("ERROR: %s line %d: output '%s' is the query file of line %d\n", a->list_FN, S[i].line, S[i].o, S[k].line); return 1; }
+		for (int k = 0; k < n; ++k) if (!strcmp(S[i].o, S[k].q) || (S[k].m && !strcmp(S[i].o, S[k].m))) { printf("ERROR: %s line %d: output '%s' is the query file of line %d\n", a->list_FN, S[i].line, S[i].o, S[k].line); return 1; }
 		if (!strcmp(S[i].o, a->ref_FN) || (a->xcel_FN && !strcmp(S[i].o, a->xcel_FN)) || !strcmp(S[i].o, a->list_FN)) {
 			printf("ERROR: %s line %d: output '%s' is the database, the accelerator or the list itself\n", a->list_FN, S[i].line, S[i].o); return 1;
 		}
@@ -153,10 +159,22 @@ static int read_sample_list(const SamplesArgs *a, Sample **out, int *n_out) {
 
 static int samples_main(SamplesArgs *a) {
 	Sample *S = NULL; int nS = 0, rc;
-	{ const int e = read_sample_list(a, &S, &nS); if (e) return e; }
+	if (a->list_FN) { const int e = read_sample_list(a, &S, &nS); if (e) return e; }
+	else {      /* --mates: a session of one pair */
+		if (!(S = calloc(1, sizeof(*S))) || !(S[0].q = strdup(a->q1_FN)) || !(S[0].o = strdup(a->out_FN)) || !(S[0].m = strdup(a->mates_FN))) { fputs("OOM:samples\n", stderr); return 3; }
+		nS = 1;
+	}
+	int any_mates = 0;
+	for (int i = 0; i < nS; ++i) any_mates |= S[i].m != NULL;
+	/* what a pair of mate files needs, checked before a device is touched */
+	if (a->mates_opts_given && !any_mates) { puts("ERROR: --insert-min, --insert-max, --mates-orientation and --mates-report go with --mates (or a --samples line with a mates file)"); return 1; }
+	if (any_mates && a->mode != BH_ALLPATHS && a->mode != BH_FORAGE) { puts("ERROR: mates are joined from the placements of -m ALLPATHS or -m FORAGE (BEST, CAPITALIST and ANY discard the ties the join needs)"); return 1; }
+	if (any_mates && !a->do_rc) { puts("ERROR: a --samples line with a mates file needs both strands searched: add -fr"); return 1; }
+	if (any_mates && (a->cigar || a->cov_prefix)) { puts("ERROR: --cigar and --coverage of paired output are out of scope: neither goes with mates"); return 1; }
 	const int usedb = bh_is_edx(a->ref_FN);
 	if (usedb < 0) DIE(usedb);
 	/* direct FASTA references: their clumps depend on the longest query (burst.c:5151) -- there is nothing to keep resident */
+	if (!usedb && !a->list_FN) { puts("ERROR: --mates needs an .edx database (FASTA references are clumped per query file: nothing would stay resident between the mates)"); return 1; }
 	if (!usedb) { puts("ERROR: --samples needs an .edx database (the clumps of FASTA references depend on the queries: nothing would stay resident)"); return 1; }
 	int K = a->K, shard_db = a->shard_db, n_shards = a->n_shards;
 	const int n_gpus = a->n_gpus;
@@ -164,6 +182,7 @@ static int samples_main(SamplesArgs *a) {
 	if (shard_db && !n_shards) n_shards = n_gpus;
 	if (!shard_db || n_shards < 2) { shard_db = 0; n_shards = 1; }
 	/* more shards than devices: one upload per shard per search -- nothing stays resident either (out of scope for --samples) */
+	if (shard_db && n_gpus == 1 && n_shards > 1 && !a->list_FN) { puts("ERROR: --mates needs a resident device handle: it does not go with the serial-shards path (--gpus 1 --shards S)"); return 1; }
 	if (shard_db && n_gpus == 1 && n_shards > 1) { puts("ERROR: --samples does not take the serial-shards path (--gpus 1 --shards S uploads every shard for every search)"); return 1; }
 	if (n_gpus % n_shards) { printf("ERROR: --shards %d does not divide --gpus %d\n", n_shards, n_gpus); return 1; }
 	if (a->threads > 0) omp_set_num_threads(a->threads);
@@ -186,7 +205,7 @@ static int samples_main(SamplesArgs *a) {
 	BhSessionOpts so; memset(&so, 0, sizeof so);
 	so.mode = a->mode; so.thres = a->thres; so.do_rc = a->do_rc; so.incl_ws = a->incl_ws; so.z = a->z; so.do_accel = a->do_accel; so.K = K;
 	so.skip_ambig = a->skip_ambig; so.rep_flags = a->rep_flags; so.batch = a->batch; so.shard_db = shard_db ? n_shards : 0; so.tax = a->tax_FN ? a->txo : NULL;
-	so.ingest_ahead = 1; so.verbose = 1; so.cigar = a->cigar;
+	so.ingest_ahead = 1; so.verbose = 1; so.cigar = a->cigar; so.mates = a->mates;
 	BhSession *ses = NULL;
 	if ((rc = bh_session_open(&db, ranks, n_gpus, n_gpus, NULL, NULL, &so, &ses))) DIE(rc);
 	bh_queries_sort_device(dev_list[0]);      /* large query files are sorted on the (first) search device */
@@ -214,10 +233,12 @@ static int samples_main(SamplesArgs *a) {
 	PHASE("device database upload");
 	int n_failed = 0, first_fail = 0, n_done = 0;
 	for (int i = 0; i < nS; ++i) {
-		printf("Sample %d/%d: %s -> %s\n", i + 1, nS, S[i].q, S[i].o);
-		if (i + 1 < nS) bh_session_prefetch(ses, S[i + 1].q);
+		if (S[i].m) printf("Sample %d/%d: %s + %s -> %s\n", i + 1, nS, S[i].q, S[i].m, S[i].o);
+		else printf("Sample %d/%d: %s -> %s\n", i + 1, nS, S[i].q, S[i].o);
+		/* (a pair prefetches its own second file; the sample after a pair is read when its turn comes) */
+		if (i + 1 < nS && !S[i].m) bh_session_prefetch(ses, S[i + 1].q);
 		BhSampleResult res;
-		rc = bh_session_run(ses, S[i].q, S[i].o, &res);
+		rc = S[i].m ? bh_session_run_mates(ses, S[i].q, S[i].m, S[i].o, &res) : bh_session_run(ses, S[i].q, S[i].o, &res);
 		if (rc) {
 			printf("Sample %d/%d FAILED (exit code %d): %s\n", i + 1, nS, code_to_exit(rc), res.err);
 			if (!n_failed++) first_fail = code_to_exit(rc);
@@ -240,7 +261,7 @@ static int samples_main(SamplesArgs *a) {
 	bh_cov_close(cov);
 	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); bh_run_free(&ranks[r].run); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
 	bh_db_free(&db); bh_tax_free(&taxonomy);
-	for (int i = 0; i < nS; ++i) { free(S[i].q); free(S[i].o); }
+	for (int i = 0; i < nS; ++i) { free(S[i].q); free(S[i].o); free(S[i].m); }
 	free(S);
 	return first_fail;
 }
@@ -265,6 +286,11 @@ static void usage(void) {
 	puts("--accelerator-device (-ad): no .acx file, the device builds the accelerator from the .edx (word length -k, default 12)");
 	puts("--samples <list>: align a list of query files against the one resident database, each to its own output; one sample per line,");
 	puts("                  'queries<TAB>output' (in place of -q / -o; needs -r DB.edx; the database is read, uploaded and indexed once)");
+	puts("--mates <name>: paired-end reads: -q holds mate 1, --mates mate 2 (paired by name, a trailing /1 or /2 ignored); -o gets every concordant");
+	puts("    combination of a line of mate 1 and a line of mate 2 on the same reference as those two lines, each followed by the fragment's leftmost");
+	puts("    position and its length.  Needs -r DB.edx and -m ALLPATHS or FORAGE; -fr is implied.  In a --samples list: a third field on the line;");
+	puts("    such a list needs -fr given (it holds for every line: the two-field lines run as the flags say)");
+	puts("--insert-min <int> (0), --insert-max <int> (1000): bounds of the fragment length; --mates-orientation fr|rf|ff (fr); --mates-report all|best (all)");
 	puts("--cigar: with -q / -o or --samples, two further columns per line: the leftmost 1-based reference position of the alignment path and");
 	puts("    its CIGAR in =XID (I: query symbol without a reference column, D: reference column without a query symbol)");
 	puts("--coverage <prefix> [--coverage-lengths <file>] [--coverage-pad <int>]: with -q / -o or --samples, leave coverage and count tables per");
@@ -285,6 +311,7 @@ int main(int argc, char **argv) {
 	uint64_t batch = 1u << 21;      /* unique queries per device batch: the fixed cost of a batch (launches, synchronisation) is about 1 ms of device time */
 	const char *ref_FN = 0, *query_FN = 0, *output_FN = 0, *xcel_FN = 0, *mkacx_FN = 0, *tax_FN = 0, *samples_FN = 0, *cov_prefix = 0, *cov_lengths = 0;
 	uint32_t cov_pad = 0;
+	const char *mates_FN = 0; BhMatesOpts mopts = {BHIP_MATES_FR, 0, 1000, BHIP_MATES_ALL}; int mates_opts_given = 0;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
 	BhTaxOpts txo; memset(&txo, 0, sizeof txo); txo.taxacut = 10;   /* burst.c:92 */
 	setenv("GPU_MAX_HW_QUEUES", "8", 0);      /* HIP runtime: hardware queues for the library's four streams (read when the runtime starts) */
@@ -337,6 +364,25 @@ int main(int argc, char **argv) {
 		else if (!strcmp(a, "--make-acx")) { NEEDARG("--make-acx"); mkacx_FN = argv[i]; }
 		else if (!strcmp(a, "--coverage")) { NEEDARG("--coverage"); cov_prefix = argv[i]; }
 		else if (!strcmp(a, "--cigar")) cigar = 1;
+		else if (!strcmp(a, "--mates")) { NEEDARG("--mates"); mates_FN = argv[i]; }
+		else if (!strcmp(a, "--insert-min") || !strcmp(a, "--insert-max")) {
+			const int is_max = !strcmp(a, "--insert-max");
+			NEEDARG(a);
+			char *end = NULL; const unsigned long long v = strtoull(argv[i], &end, 10);
+			if (!*argv[i] || *end || v > 0xFFFFFFFFull) { printf("ERROR: %s takes a length (0 .. 4294967295)\n", a); return 1; }
+			if (is_max) mopts.ins_max = (uint32_t)v; else mopts.ins_min = (uint32_t)v;
+			mates_opts_given = 1;
+		}
+		else if (!strcmp(a, "--mates-orientation")) {
+			NEEDARG("--mates-orientation"); mates_opts_given = 1;
+			if (!strcmp(argv[i], "fr")) mopts.orientation = BHIP_MATES_FR; else if (!strcmp(argv[i], "rf")) mopts.orientation = BHIP_MATES_RF;
+			else if (!strcmp(argv[i], "ff")) mopts.orientation = BHIP_MATES_FF; else { puts("ERROR: --mates-orientation fr|rf|ff"); return 1; }
+		}
+		else if (!strcmp(a, "--mates-report")) {
+			NEEDARG("--mates-report"); mates_opts_given = 1;
+			if (!strcmp(argv[i], "all")) mopts.report = BHIP_MATES_ALL; else if (!strcmp(argv[i], "best")) mopts.report = BHIP_MATES_BEST;
+			else { puts("ERROR: --mates-report all|best"); return 1; }
+		}
 		else if (!strcmp(a, "--coverage-lengths")) { NEEDARG("--coverage-lengths"); cov_lengths = argv[i]; }
 		else if (!strcmp(a, "--coverage-pad")) { NEEDARG("--coverage-pad"); cov_pad = (uint32_t)strtoul(argv[i], 0, 10); }
 		else if (!strcmp(a, "--device")) { NEEDARG("--device"); device = atoi(argv[i]); }
@@ -407,16 +453,30 @@ int main(int argc, char **argv) {
 	if (cigar && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --cigar adds the alignment paths to the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
 	if (cigar && (shard_db || n_shards)) { puts("ERROR: --cigar traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
 	if (cigar && !gather_host) { puts("ERROR: --cigar takes the host gather only (drop --gather rccl)"); return 1; }
-	if (samples_FN) {
+	if (mates_opts_given && mopts.ins_min > mopts.ins_max) { puts("ERROR: --insert-min is larger than --insert-max"); return 1; }
+	if (mates_opts_given && !mates_FN && !samples_FN) { puts("ERROR: --insert-min, --insert-max, --mates-orientation and --mates-report go with --mates"); return 1; }
+	if (mates_FN) {
+		/* a session of one pair (bh_session_run_mates), beside the single-sample path below; everything here is checked before a device is touched */
+		if (samples_FN) { puts("ERROR: --mates goes with -q / -o; in a --samples list the mates file is the third field of a line"); return 1; }
+		if (makedb || mkacx_FN) { puts("ERROR: --mates joins the lines of an alignment run: it does not go with -d or --make-acx"); return 1; }
+		if (xalpha) { puts("ERROR: --mates does not take -x (raw alphabets work against FASTA references only, and have no reverse strand)"); return 1; }
+		if (!ref_FN || !query_FN || !output_FN) { puts("ERROR: --mates needs -r DB.edx, -q (mate 1) and -o"); return 1; }
+		if (!gather_host) { puts("ERROR: --mates takes the host gather only (drop --gather rccl)"); return 1; }
+		if (accel_dev && xcel_FN) { puts("ERROR: -ad builds the accelerator on the device; drop -a"); return 1; }
+		if (!strcmp(mates_FN, query_FN) || !strcmp(output_FN, query_FN) || !strcmp(output_FN, mates_FN)) { puts("ERROR: -q, --mates and -o must be three different files"); return 1; }
+		do_rc = 1;      /* (implied: one mate of a pair lies on the reverse strand) */
+	}
+	if (samples_FN || mates_FN) {
 		/* per sample what a separate invocation writes; everything checked here is checked before a device is touched.  Out of scope:
 		 * per-sample identity / mode, FASTA references, -x, serial shards and the RCCL gather (refused below and in samples_main) */
-		if (query_FN || output_FN || makedb || mkacx_FN) { puts("ERROR: --samples names the query files and outputs itself: it does not go with -q, -o, -d or --make-acx"); return 1; }
+		if (samples_FN && (query_FN || output_FN || makedb || mkacx_FN)) { puts("ERROR: --samples names the query files and outputs itself: it does not go with -q, -o, -d or --make-acx"); return 1; }
 		if (!ref_FN) { puts("ERROR: --samples needs -r DB.edx"); return 1; }
-		if (xalpha) { puts("ERROR: --samples does not take -x (raw alphabets work against FASTA references only)"); return 1; }
+		if (samples_FN && xalpha) { puts("ERROR: --samples does not take -x (raw alphabets work against FASTA references only)"); return 1; }
 		if (!gather_host) { puts("ERROR: --samples takes the host gather only (drop --gather rccl)"); return 1; }
 		if (accel_dev && xcel_FN) { puts("ERROR: -ad builds the accelerator on the device; drop -a"); return 1; }
 		SamplesArgs sa = {ref_FN, xcel_FN, tax_FN, samples_FN, mode, thres, z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device,
-		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo, cov_prefix, cov_lengths, cov_pad, cigar};
+		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo, cov_prefix, cov_lengths, cov_pad, cigar,
+		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */

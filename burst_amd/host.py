@@ -86,7 +86,18 @@ class BhTaxOpts(C.Structure):
 class BhSessionOpts(C.Structure):
     _fields_ = [("mode", C.c_int), ("thres", C.c_float), ("do_rc", C.c_int), ("incl_ws", C.c_int), ("z", C.c_int), ("do_accel", C.c_int), ("K", C.c_int),
                 ("skip_ambig", C.c_int), ("rep_flags", C.c_int), ("batch", C.c_uint64), ("shard_db", C.c_int), ("tax", C.POINTER(BhTaxOpts)),
-                ("ingest_ahead", C.c_int), ("verbose", C.c_int), ("cov", C.c_void_p), ("cigar", C.c_int)]
+                ("ingest_ahead", C.c_int), ("verbose", C.c_int), ("cov", C.c_void_p), ("cigar", C.c_int),
+                ("mates_orientation", C.c_uint32), ("mates_ins_min", C.c_uint32), ("mates_ins_max", C.c_uint32), ("mates_report", C.c_uint32)]
+
+
+class BhMatesStats(C.Structure):
+    _fields_ = [("reads1", C.c_uint64), ("reads2", C.c_uint64), ("pairsNamed", C.c_uint64), ("pairsPlaced", C.c_uint64), ("lines1", C.c_uint64),
+                ("lines2", C.c_uint64), ("examined", C.c_uint64), ("written", C.c_uint64), ("deviceMs", C.c_double)]
+
+
+MATES_JOIN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                            C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64))
+E_CAPACITY = -6
 
 
 COV_TAP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64)
@@ -172,6 +183,13 @@ def lib():
         L.bh_session_finish.argtypes = [C.c_void_p, C.POINTER(BhSampleResult)]
         L.bh_session_run.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(BhSampleResult)]
         L.bh_session_drop.argtypes = [C.c_void_p]
+        L.bh_session_run_mates.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(BhSampleResult)]
+        L.bh_session_mates.argtypes = [C.c_void_p]
+        L.bh_session_mates.restype = C.c_void_p
+        L.bh_mates_set_join.argtypes = [C.c_void_p, MATES_JOIN_FN, C.c_void_p]
+        L.bh_mates_set_join.restype = None
+        L.bh_mates_stats.argtypes = [C.c_void_p, C.POINTER(BhMatesStats)]
+        L.bh_mates_stats.restype = None
         L.bh_session_sample.argtypes = [C.c_void_p]
         L.bh_session_sample.restype = C.POINTER(BhQueries)
         L.bh_session_set_node.argtypes = [C.c_void_p, C.c_void_p]
@@ -547,7 +565,8 @@ class Session:
     def __init__(self, db, devs=None, mode="CAPITALIST", thres=0.97, rc=False, whitespace=False, z=1, accel=None, K=0, batch=1 << 21, shard_db=0,
                  taxonomy=None, taxacut=10, tax_ncbi=False, tax_suppress=False, tax_strict=False, rep_flags=0, ingest_ahead=True,
                  align=None, reduce_min=None, rank=0, world=None, c0=0, node=None, comm=None, verbose=False,
-                 coverage=None, coverage_lengths=None, coverage_pad=0, coverage_tap=None, cigar=False):
+                 coverage=None, coverage_lengths=None, coverage_pad=0, coverage_tap=None, cigar=False,
+                 mates_orientation="fr", insert_min=0, insert_max=1000, mates_report="all", mates_join=None):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
         reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
         process only).
@@ -556,6 +575,7 @@ class Session:
         statistics.  coverage_lengths: a `name<TAB>length` table (default: the database's own extents); coverage_tap(sample, lines):
         called with every sample's placements (capi.COV_LINE_DTYPE) before they go to the device, a true return keeps them from it."""
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
+        self._mates_join = mates_join
         self.cov = C.c_void_p()
         devs = list(devs) if isinstance(devs, (list, tuple)) else [devs]
         n_local = len(devs)
@@ -576,6 +596,10 @@ class Session:
         o = BhSessionOpts()
         o.mode, o.thres, o.do_rc, o.incl_ws, o.z, o.do_accel, o.K = MODES[mode], thres, int(rc), int(whitespace), z, int(accel), int(db.c.K) if db.c.hasAcx else K
         o.rep_flags, o.batch, o.shard_db, o.ingest_ahead, o.verbose = rep_flags, batch, int(shard_db), int(ingest_ahead), int(verbose)
+        if mates_orientation not in capi.MATES_ORIENTATIONS or mates_report not in capi.MATES_REPORTS or not 0 <= int(insert_min) <= int(insert_max) < 1 << 32:
+            raise ValueError("mates: orientation fr|rf|ff, report all|best, 0 <= insert_min <= insert_max")
+        o.mates_orientation, o.mates_report = capi.MATES_ORIENTATIONS[mates_orientation], capi.MATES_REPORTS[mates_report]
+        o.mates_ins_min, o.mates_ins_max = int(insert_min), int(insert_max)
         if cigar:
             if shard_db and int(shard_db) > 1:
                 raise ValueError("cigar: the paths are traced on one handle, which must hold the whole database (no shard_db)")
@@ -642,8 +666,47 @@ class Session:
     def prefetch(self, queries):
         _chk(lib().bh_session_prefetch(self.h, queries.encode()))
 
-    def run(self, queries, out):
+    def _mates_cb(self, join):
+        def _join(ctx, a, na, b, nb, orientation, ins_min, ins_max, report, out_a, out_b, cap, n_out):
+            try:
+                la = np.frombuffer((C.c_uint8 * (int(na) * 20)).from_address(a), dtype=capi.MATE_LINE_DTYPE) if na else np.zeros(0, capi.MATE_LINE_DTYPE)
+                lb = np.frombuffer((C.c_uint8 * (int(nb) * 20)).from_address(b), dtype=capi.MATE_LINE_DTYPE) if nb else np.zeros(0, capi.MATE_LINE_DTYPE)
+                r = join(la, lb, int(orientation), int(ins_min), int(ins_max), int(report), int(cap))
+                if isinstance(r, int):      # (the joiner asks for room)
+                    n_out[0] = r
+                    return E_CAPACITY
+                ia, ib = (np.ascontiguousarray(x, dtype=np.uint32) for x in r)
+                n_out[0] = len(ia)
+                if len(ia) > cap:
+                    return E_CAPACITY
+                C.memmove(out_a, ia.ctypes.data, 4 * len(ia))
+                C.memmove(out_b, ib.ctypes.data, 4 * len(ib))
+                return 0
+            except Exception:      # (an exception must not cross the C frame)
+                import traceback
+                traceback.print_exc()
+                return E_INTERNAL
+        self._cb.append(MATES_JOIN_FN(_join))
+        return self._cb[-1]
+
+    def run(self, queries, out, mates=None):
+        """mates: the second mate file -- `queries` and `mates` are searched one after the other and `out` gets their concordant combinations
+        (bh_session_run_mates; the session's mates_orientation, insert_min, insert_max, mates_report; needs mode ALLPATHS or FORAGE and
+        rc=True).  The result then has "mates": reads1, reads2, pairsNamed, pairsPlaced, lines1, lines2, examined, written, deviceMs.
+        mates_join(a, b, orientation, ins_min, ins_max, report, cap) -> (out_a, out_b), or an int = room wanted: a joiner in place of the
+        device's (the CPU tests put the definition's brute force here)"""
         res = BhSampleResult()
+        if mates is not None:
+            m = lib().bh_session_mates(self.h)
+            if m and self._mates_join is not None:
+                lib().bh_mates_set_join(m, self._mates_cb(self._mates_join), None)
+                self._mates_join = None
+            d = self._done(lib().bh_session_run_mates(self.h, queries.encode(), mates.encode(), out.encode() if out else None, C.byref(res)), res)
+            if m and not d["rc"]:
+                st = BhMatesStats()
+                lib().bh_mates_stats(m, C.byref(st))
+                d["mates"] = {k: getattr(st, k) for k, _ in BhMatesStats._fields_}
+            return d
         return self._done(lib().bh_session_run(self.h, queries.encode(), out.encode() if out else None, C.byref(res)), res)
 
     def load(self, queries, out):

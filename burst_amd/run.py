@@ -209,8 +209,11 @@ def main(argv=None):
                     "PREFIX{shared,unique,shared_binary,unique_binary,counts}.txt (computed on rank 0's device from the lines it reports)")
     ap.add_argument("--coverage-lengths", metavar="FILE", help="reference lengths, 'name<TAB>length' per line (default: the database's own extent of every reference)")
     ap.add_argument("--coverage-pad", type=int, default=0, help="bases a placement's range is widened by at both ends")
+    ap.add_argument("--mates", help="not available here: paired-end reads are joined by burst_hip --mates (one process, the host gather)")
     ap.add_argument("--cigar", action="store_true", help="not available here: the alignment paths are traced by burst_hip --cigar (one process, the host gather)")
     args = ap.parse_args(argv)
+    if args.mates:
+        ap.error("--mates is not available in python -m burst_amd.run: use burst_hip --mates (one process, --gpus N with the host gather)")
     if args.cigar:
         ap.error("--cigar is not available in python -m burst_amd.run: use burst_hip --cigar (one process, --gpus N with the host gather)")
     if (args.coverage_lengths or args.coverage_pad) and not args.coverage:

@@ -357,6 +357,33 @@ BHIP_API int bhip_trace_paths(void *handle, const uint8_t *q_codes, const uint64
                               uint32_t *ops, uint64_t ops_cap, uint64_t *op_off, uint32_t *ref_first, uint32_t *gap_r);
 BHIP_API int bhip_paths_info(void *handle, uint64_t info[4]);
 
+/* Paired-end reads: the join of two mates' printed placements into concordant combinations (burst_hip --mates; no reference counterpart:
+ * the reference lists paired-end alignment as planned and names the recipe -- both mates in ALLPATHS mode, then the references both map to
+ * with acceptable orientation and distance).  A line is one placement as the .b6 prints it: `pair` = the pair its read belongs to and `ref` =
+ * its header, both DENSE numbers the caller assigns (equal numbers = equal names / byte-equal headers), st / ed = columns 9 and 10 as signed
+ * numbers, edits = column 11.  A line is reverse when st > ed; lo / hi = the smaller / larger of st and ed.  A combination is a line of `a`
+ * (mate 1) and a line of `b` (mate 2) with equal pair and ref; with U the upstream and D the downstream line --
+ *   BHIP_MATES_FR  exactly one of the two is reverse, U = the forward one;   BHIP_MATES_RF  the same with U = the reverse one;
+ *   BHIP_MATES_FF  both forward (U = the line of a) or both reverse (U = the line of b)
+ * -- it is concordant when U.lo <= D.lo, U.hi <= D.hi and ins_min <= D.hi - U.lo + 1 <= ins_max.  BHIP_MATES_ALL reports every concordant
+ * combination, BHIP_MATES_BEST one per pair: the smallest edits sum (saturating at 2^32 - 1), then the smallest index in a, then in b.
+ * out_a[i], out_b[i] index the caller's arrays, in ascending (a, b) order; *n_out = their number.  BHIP_E_CAPACITY when cap is too small:
+ * *n_out is the number wanted, nothing is written, the handle stays usable.  BHIP_E_ARG, before any device memory is touched, for an
+ * orientation or report outside the values above, ins_min > ins_max, na or nb >= 2^32, and (BHIP_MATES_BEST, which keeps a table indexed
+ * by pair) a pair number of `a` beyond 4 (na + nb) + 2^20.  na == 0 or nb == 0: no combinations, no launch.  Device side: csrc/bhip_mates.hip.
+ * bhip_mates_info: [0] device microseconds of the last bhip_mates_join call that launched (HIP events around its kernels, sort and scan),
+ * [1] of all calls, [2] lines taken in and [3] combinations returned by all calls that returned BHIP_OK. */
+typedef struct BhipMateLine { uint32_t pair, ref; int32_t st, ed; uint32_t edits; } BhipMateLine;
+#define BHIP_MATES_FR   0u
+#define BHIP_MATES_RF   1u
+#define BHIP_MATES_FF   2u
+#define BHIP_MATES_ALL  0u
+#define BHIP_MATES_BEST 1u
+BHIP_API int bhip_mates_join(void *handle, const BhipMateLine *a, uint64_t na, const BhipMateLine *b, uint64_t nb,
+                             uint32_t orientation, uint32_t ins_min, uint32_t ins_max, uint32_t report,
+                             uint32_t *out_a, uint32_t *out_b, uint64_t cap, uint64_t *n_out);
+BHIP_API int bhip_mates_info(void *handle, uint64_t info[4]);
+
 /* Tuning knobs.  "prefilter_stride": 0 (default) = automatic sparse seeds -- per query the largest stride s <= K for
  * which an alignment within budget still keeps >= 3 of the words starting at 0, s, 2s, ... (one edit destroys at most
  * ceil(K/s) of them), fewest .acx look-ups with the same no-false-negative guarantee; s >= 1 forces every s-th word,
