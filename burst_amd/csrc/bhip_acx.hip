@@ -9,6 +9,7 @@
 //   bhip_acx_export         back to the host as Lens[4^K] + clump ids (+ masks, BadList), e.g. to write the .acx.
 #include "bhip_handle.h"
 #include "bhip_acx_words.h"
+#include "bhip_acx_plan.h"
 
 // ------------------------------------------------------------------------------------------------
 // .acx offsets: Lens[4^K] (burst.c:3558) -> exclusive prefix inside each block of 256 words (`delta`) and the block sums
@@ -153,6 +154,14 @@ __global__ void k_attach_masks(BhipAcxView acx, uint64_t n_words,
 // ------------------------------------------------------------------------------------------------
 struct DTmp : DBuf { ~DTmp() { release(); } };
 #define ARC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+// A library call that reports its scratch size when it is given no scratch: call(scratch, bytes) asked for the size, `tmp` grown to it, and
+// called again with the same arguments.  (call returns 0 or what fail() gave it)
+template <class Call> static int with_scratch(DBuf &tmp, Call call) {
+	size_t tb = 0;
+	ARC(call((void *)nullptr, tb));
+	ARC(tmp.reserve(tb));
+	return call(tmp.p, tb);
+}
 
 // Offset lines, total and statistics from the list lengths on the device (Lens[4^K], burst.c:3558): sums of 14 -> 64-bit bases
 // (hipCUB scan) -> lines; occurrence-weighted mean list length (sizes the prefilter's per-query tables) and the longest list.
@@ -248,19 +257,13 @@ static int build_lane_masks(Handle *h) {
 		hipLaunchKernelGGL(k_extract_kmers, dim3(std::min<uint32_t>(((c1 - c0) * 16 + 255) / 256, (uint32_t)h->n_cu * 16)), dim3(256), 0, h->stream, h->ref_lane.as<uint4>(),
 			h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), d_koff.as<uint64_t>(), c0, c1, h->K, k0.as<unsigned long long>(), v0.as<uint16_t>(), amb.as<uint32_t>());
 		HIPCHK(hipGetLastError());
-		size_t tb = 0;
 		hipcub::DoubleBuffer<unsigned long long> dk(k0.as<unsigned long long>(), k1.as<unsigned long long>());
 		hipcub::DoubleBuffer<uint16_t> dv(v0.as<uint16_t>(), v1.as<uint16_t>());
-		HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, (int)n_items, 0, end_bit, h->stream));
-		ARC(tmp.reserve(tb));
-		HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, dk, dv, (int)n_items, 0, end_bit, h->stream));
+		ARC(with_scratch(tmp, [&](void *t, size_t &tb) { HIPCHK(hipcub::DeviceRadixSort::SortPairs(t, tb, dk, dv, (int)n_items, 0, end_bit, h->stream)); return 0; }));
 		// invalid slots carry key ~0, which after masking to end_bit sorts last (all ones) -- their run is simply never looked up
 		unsigned long long *skeys = dk.Current(); uint16_t *svals = dv.Current();
 		unsigned long long *ukeys = dk.Alternate(); uint16_t *umasks = dv.Alternate();
-		size_t tb2 = 0;
-		HIPCHK(hipcub::DeviceReduce::ReduceByKey(nullptr, tb2, skeys, ukeys, svals, umasks, nruns.as<uint32_t>(), BitOrU16(), (int)n_items, h->stream));
-		ARC(tmp.reserve(tb2));
-		HIPCHK(hipcub::DeviceReduce::ReduceByKey(tmp.p, tb2, skeys, ukeys, svals, umasks, nruns.as<uint32_t>(), BitOrU16(), (int)n_items, h->stream));
+		ARC(with_scratch(tmp, [&](void *t, size_t &tb) { HIPCHK(hipcub::DeviceReduce::ReduceByKey(t, tb, skeys, ukeys, svals, umasks, nruns.as<uint32_t>(), BitOrU16(), (int)n_items, h->stream)); return 0; }));
 		uint32_t n_unique = 0;
 		HIPCHK(hipMemcpyAsync(&n_unique, nruns.p, 4, hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));
@@ -544,8 +547,7 @@ __global__ __launch_bounds__(256) void k_acx_whist(const uint4 *__restrict__ ref
 	__syncthreads();
 	for (uint32_t i = threadIdx.x; i < n_buckets; i += 256) if (s_h[i]) atomicAdd(&hist[i], (unsigned long long)s_h[i]);
 }
-// tuples per (slice, clump): counts[s * n_clumps + c]; a block = 16 clumps at a time
-#define BHIP_ACX_MAX_SLICES 256u
+// tuples per (slice, clump): counts[s * n_clumps + c]; a block = 16 clumps at a time (BHIP_ACX_MAX_SLICES: bhip_acx_plan.h)
 __global__ __launch_bounds__(256) void k_acx_wcount(const uint4 *__restrict__ ref, const uint64_t *__restrict__ ref_off, const uint32_t *__restrict__ clump_len,
 		const uint8_t *__restrict__ is_bad, uint32_t n_clumps, uint32_t tot_refs, int K, int z, uint32_t shift, uint32_t n_buckets, const uint8_t *__restrict__ b2s, uint32_t n_slices,
 		uint32_t *__restrict__ counts) {
@@ -647,187 +649,17 @@ static int acx_move_up(Handle *h, char *base, size_t bytes, size_t shift) {
 	HIPCHK(hipStreamSynchronize(h->stream));
 	return 0;
 }
-static int build_accelerator_by_words(Handle *h, int K, int z, int part = 0, int n_parts = 1, bhip_share_fn share = nullptr, void *share_ctx = nullptr) {
-	const bool coop = n_parts > 1;
-	const uint32_t nC = h->n_clumps;
-	const uint64_t nw = 1ull << (2 * K);
-	const bool dbg = getenv("BHIP_DEBUG") != nullptr;
-	const auto t_begin = std::chrono::steady_clock::now();
-	auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); };
-	uint32_t cbits = 1; while ((1ull << cbits) < nC) ++cbits;
-	const uint32_t bb = (uint32_t)std::min(12, 2 * K), shift = (uint32_t)(2 * K) - bb, n_buckets = 1u << bb;
-	const uint32_t g = (uint32_t)h->n_cu * 16;
-	const uint64_t n_lines = (nw + BHIP_ACX_LINE_WORDS - 1) / BHIP_ACX_LINE_WORDS;
-	const uint32_t all_lanes = getenv("BHIP_NO_LANE_MASKS") ? 1u : 0u;
-	std::vector<uint32_t> badlist;
-	std::vector<uint32_t> rb((size_t)n_parts + 1, 0);      // bucket boundaries of the ranks' runs
-	DTmp d_lens, lines_scratch;
-	uint64_t rec_n = 0, total = 0, cap_items = 0;
-	uint32_t n_slices = 0;
-	double t_hist = 0, t_count = 0, t_sort = 0;
-	// everything a rank does on its own: 0 = its lists are built (records [0, rec_n) of the record area, their lengths in d_lens),
-	// 1 = cannot run here, < 0 = error
-	auto local_part = [&]() -> int {
-	if (cbits > 24) return 1;
-	if (coop) if (const char *ev = getenv("BHIP_TEST_COOP_FAIL_RANK")) if (atoi(ev) == part) return 1;      // (test hook: this rank cannot -> all ranks build alone)
-	// 1. expansion estimate per clump -> BadList (as the clump-sliced builder)
-	std::vector<unsigned long long> tsum(nC), nexp(nC);
-	std::vector<uint8_t> is_bad(nC, 0);
-	DTmp d_bad;
-	{
-		DTmp d_ts, d_nx;
-		ARC(d_ts.reserve((size_t)nC * 8)); ARC(d_nx.reserve((size_t)nC * 8));
-		HIPCHK(hipMemsetAsync(d_ts.p, 0, (size_t)nC * 8, h->stream)); HIPCHK(hipMemsetAsync(d_nx.p, 0, (size_t)nC * 8, h->stream));
-		hipLaunchKernelGGL(k_acx_budget, dim3(std::min<uint32_t>((nC * 16u + 255u) / 256u, (uint32_t)h->n_cu * 16)), dim3(256), 0, h->stream, h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(),
-			h->clump_len.as<uint32_t>(), nC, h->tot_refs, K, z ? 1 : 0, d_ts.as<unsigned long long>(), d_nx.as<unsigned long long>());
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(tsum.data(), d_ts.p, (size_t)nC * 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipMemcpyAsync(nexp.data(), d_nx.p, (size_t)nC * 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipStreamSynchronize(h->stream));
-	}
-	const unsigned long long full_size = K > 14 ? 0x7FFFFFFFull : (1ull << 24);      // burst.c:3322
-	for (uint32_t c = 0; c < nC; ++c) {
-		if (tsum[c] >= full_size) { is_bad[c] = 1; badlist.push_back(c); continue; }
-		if (16ull * h->h_clump_len[c] + nexp[c] >= (1ull << 31)) return 1;
-	}
-	ARC(d_bad.reserve((size_t)nC + 16));
-	HIPCHK(hipMemcpyAsync(d_bad.p, is_bad.data(), nC, hipMemcpyHostToDevice, h->stream));
-	// 2. tuples per bucket of words -> the ranks' runs of buckets (equal numbers of tuples), and inside this rank's run the slices: runs of
-	// buckets with at most `target` tuples and at most 2^24 words (three sort passes)
-	std::vector<unsigned long long> hist(n_buckets);
-	{
-		DTmp d_hist;
-		ARC(d_hist.reserve((size_t)n_buckets * 8));
-		HIPCHK(hipMemsetAsync(d_hist.p, 0, (size_t)n_buckets * 8, h->stream));
-		hipLaunchKernelGGL(k_acx_whist, dim3(g), dim3(256), 0, h->stream, h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), d_bad.as<uint8_t>(),
-			nC, h->tot_refs, K, z ? 1 : 0, shift, n_buckets, d_hist.as<unsigned long long>());
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(hist.data(), d_hist.p, (size_t)n_buckets * 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipStreamSynchronize(h->stream));
-	}
-	t_hist = since();
-	uint64_t biggest = 0;
-	total = 0;
-	for (uint32_t b = 0; b < n_buckets; ++b) total += hist[b];
-	if (!total) return 1;
-	{
-		uint64_t run = 0; int r = 1;
-		for (uint32_t b = 0; b < n_buckets && r < n_parts; ++b) {
-			while (r < n_parts && run >= (uint64_t)((double)total * r / n_parts)) rb[r++] = b;      // (run = tuples of the buckets before b)
-			run += hist[b];
-		}
-		for (; r < n_parts; ++r) rb[r] = n_buckets;
-		rb[n_parts] = n_buckets;
-	}
-	const uint32_t own0 = rb[part], own1 = rb[part + 1];
-	uint64_t total_own = 0;
-	for (uint32_t b = own0; b < own1; ++b) { total_own += hist[b]; biggest = std::max<uint64_t>(biggest, hist[b]); }
-	size_t free_b = 0, total_b = 0;
-	HIPCHK(hipMemGetInfo(&free_b, &total_b));
-	long long forced_slice = 0;
-	if (const char *ev = getenv("BHIP_MASK_SLICE")) forced_slice = atoll(ev);
-	// The record area is ONE address range (DBuf::reserve_growable) and the sort works inside it: the records fill it from the bottom, the
-	// slice at hand is sorted and folded at its TOP -- two 8-byte tuple arrays and the folded lane masks, 18 bytes per tuple -- in the part
-	// the records have not reached yet.  So a slice may have as many tuples as fit between the records so far and the top,
-	// 4 (before + n) + 18 n <= range: the early slices take what one sort call takes (2^31 tuples), the last ones what is left beside
-	// 216 GB of records -- 28 slices at the metric's size, where "one record per tuple, and the sort buffers beside them" gave 64.  Every
-	// slice costs one scan of the references, so fewer, larger slices are what makes this builder cheap.  Nothing is unmapped before the
-	// build is over (first version: sort buffers of their own, mapped and unmapped slice by slice -- ranks building side by side read each
-	// other's regions back as zeros once in three runs; with ordinary allocations of a fixed size: never in 48).
-	// A slice spans at most 2^26 words (four sort passes).
-	std::vector<uint32_t> cuts;        // bucket boundaries of the slices
-	std::vector<uint64_t> slice_items;
-	const uint32_t max_b = 26 > shift ? 1u << (26 - shift) : 1u;
-	auto buf_bytes = [](uint64_t n) -> size_t { return 2 * ((size_t)(n * 8 + 16 + 255) & ~(size_t)255) + ((size_t)(n * 2 + 16 + 255) & ~(size_t)255); };
-	// the range: the final size (a record per tuple of the whole database at most) and room for the largest slice's sort on top of the own
-	// records, as far as the device has it
-	// (round 6: 24 GB instead of 3 left alone beyond the tables.  What the sort's part of the range gives back at the end of the build is not
-	// allocatable at once -- nor is all of what a process that held the device a moment ago gave back, whatever hipMemGetInfo says: behind a
-	// parent that had opened and closed the same database, `burst_hip` at the metric's size could allocate 2.5 GB with 16 GB reported free -- and
-	// the caller's batch buffers, 7.4 GB for 2 M-entry batches, are reserved right behind the build.  The price: the last slices sort in less room.)
-	const double other = (double)nw * 4.0 + (double)(n_lines + 1) * 64.0 + (double)acx_lines_scratch_bytes(nw) + (double)nC * 8.0 + 40.0 * nC * 4.0 + (double)(24ull << 30);
-	const double avail = (double)free_b - other;
-	const uint64_t biggest_sort = std::min<uint64_t>(total_own, 2147483000ull);
-	double want_va = std::max((double)total * BHIP_REC_BYTES + 16.0, (double)total_own * BHIP_REC_BYTES + (double)buf_bytes(biggest_sort)) + 4096.0;
-	if (want_va > avail) want_va = avail;
-	if (want_va < (double)total * BHIP_REC_BYTES + 16.0 + 4096.0) return 1;      // (not even the records fit)
-	// (reserve_growable rounds up to whole chunks and adds one: planned with the two chunks taken off)
-	const size_t va_plan = (size_t)want_va > 2 * DBuf::kChunk + ((size_t)total * BHIP_REC_BYTES + 16) ? (size_t)want_va - 2 * DBuf::kChunk : (size_t)total * BHIP_REC_BYTES + 16;
-	if (h->acx_rec.reserve_growable(va_plan, h->device)) return 1;
-	const size_t va_size = h->acx_rec.va_size;
-	if (getenv("BHIP_DEBUG")) fprintf(stderr, "[bhip] word-sliced build: %.2f GB free at its start, %.2f GB set aside for the rest, range of %.2f GB for %.2f GB of records at most\n", free_b / 1e9, other / 1e9, va_size / 1e9, (double)total * BHIP_REC_BYTES / 1e9);
-	auto plan = [&](uint64_t target) -> uint32_t {      // (BHIP_MASK_SLICE: slices of a given size)
-		cuts.assign(1, own0); slice_items.clear(); cap_items = 0;
-		uint64_t before = 0;
-		for (uint32_t b0 = own0; b0 < own1;) {
-			uint32_t b1 = b0 + 1; uint64_t n = hist[b0];
-			while (b1 < own1 && b1 - b0 < max_b && n + hist[b1] <= target) n += hist[b1++];
-			if ((before + n) * BHIP_REC_BYTES + 16 + buf_bytes(n) > va_size) return 0;
-			cuts.push_back(b1); slice_items.push_back(n); cap_items = std::max(cap_items, n); before += n; b0 = b1;
-		}
-		return (uint32_t)cuts.size() - 1;
-	};
-	auto plan_by_room = [&]() -> uint32_t {
-		cuts.assign(1, own0); slice_items.clear(); cap_items = 0;
-		uint64_t before = 0;
-		for (uint32_t b0 = own0; b0 < own1;) {
-			const double room = (double)va_size - (double)before * BHIP_REC_BYTES - 4096.0;
-			const uint64_t target = room > 0 ? (uint64_t)std::min(2147483000.0, room / 22.0) : 0;
-			if (hist[b0] > target) return 0;
-			uint32_t b1 = b0 + 1; uint64_t n = hist[b0];
-			while (b1 < own1 && b1 - b0 < max_b && n + hist[b1] <= target) n += hist[b1++];
-			cuts.push_back(b1); slice_items.push_back(n); cap_items = std::max(cap_items, n); before += n; b0 = b1;
-		}
-		return (uint32_t)cuts.size() - 1;
-	};
-	const uint32_t max_slices = BHIP_ACX_MAX_SLICES - 1u;      // (slice number 0xFF marks "not this build's bucket" in the one-byte bucket -> slice table, in every mode)
-	if (own1 > own0 && total_own) {
-		n_slices = forced_slice > 0 ? plan(std::max<uint64_t>((uint64_t)forced_slice, biggest)) : plan_by_room();
-		if (!n_slices || n_slices > max_slices || cap_items >= 2147483000ull) return 1;
-	}
-	if (const char *ev = getenv("BHIP_TEST_ENTRY_BIAS")) h->acx_bias = strtoull(ev, nullptr, 0);
-	h->K = K;
-	ARC(d_lens.reserve(nw * 4 + 16));
-	HIPCHK(hipMemsetAsync(d_lens.p, 0, nw * 4, h->stream));
-	ARC(h->acx_lines.reserve_exact((n_lines + 1) * 64));      // (now, while the device has room: an allocation next to 216 GB of mapped records takes half a second)
-	ARC(lines_scratch.reserve(acx_lines_scratch_bytes(nw)));
-	if (!n_slices) { HIPCHK(hipStreamSynchronize(h->stream)); return 0; }      // (a rank whose run of buckets is empty: it only receives)
-	// 3. tuples per (slice, clump) in one scan
-	std::vector<uint8_t> b2s(n_buckets, 0xFF);
-	for (uint32_t s = 0; s < n_slices; ++s) for (uint32_t b = cuts[s]; b < cuts[s + 1]; ++b) b2s[b] = (uint8_t)s;
-	DTmp d_b2s, d_counts, d_off, nruns, tmp;
-	ARC(d_b2s.reserve(n_buckets)); ARC(d_counts.reserve_exact((size_t)n_slices * nC * 4 + 16)); ARC(d_off.reserve((size_t)nC * 4 + 16));
-	HIPCHK(hipMemcpyAsync(d_b2s.p, b2s.data(), n_buckets, hipMemcpyHostToDevice, h->stream));
-	hipLaunchKernelGGL(k_acx_wcount, dim3(g), dim3(256), 0, h->stream, h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), d_bad.as<uint8_t>(),
-		nC, h->tot_refs, K, z ? 1 : 0, shift, n_buckets, d_b2s.as<uint8_t>(), n_slices, d_counts.as<uint32_t>());
-	HIPCHK(hipGetLastError());
-	ARC(nruns.reserve(16));
-	{	// the library calls' own scratch for the largest slice, once
-		size_t tb = 0, tb1 = 0;
-		hipcub::DoubleBuffer<unsigned long long> dk((unsigned long long *)nullptr, (unsigned long long *)nullptr);
-		HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb1, dk, (int)cap_items, (int)cbits, (int)(cbits + 26), h->stream)); tb = std::max(tb, tb1);
-		hipcub::TransformInputIterator<unsigned long long, AcxWKeyOf, const unsigned long long *> kin((const unsigned long long *)nullptr, AcxWKeyOf());
-		hipcub::TransformInputIterator<uint16_t, AcxWLaneOf, const unsigned long long *> vin((const unsigned long long *)nullptr, AcxWLaneOf());
-		HIPCHK(hipcub::DeviceReduce::ReduceByKey(nullptr, tb1, kin, (unsigned long long *)nullptr, vin, (uint16_t *)nullptr, (uint32_t *)nullptr, BitOrU16(), (int)cap_items, h->stream)); tb = std::max(tb, tb1);
-		HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb1, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)nC, h->stream)); tb = std::max(tb, tb1);
-		ARC(tmp.reserve(tb + tb / 4 + 4096));
-	}
-	HIPCHK(hipStreamSynchronize(h->stream));
-	t_count = since();
-	// 4. slice after slice: offsets, tuples, sort over the slice's word bits, fold, records.  The range's memory is mapped by a thread of
-	// its own -- the top for the slice's sort, the bottom for the records so far plus this slice's (at most its tuples) -- while the slice
-	// before is at work: mapping 230 GB in 1 GiB chunks takes seconds, which lie beside the kernels.
-	std::atomic<int> map_failed(0), stop(0);
-	std::atomic<size_t> mapped_lo(0), mapped_top(0), want_lo(0), want_top(0);
-	std::thread mapper;
-	char map_err[400] = "";      // the mapper thread's own error text (hipMemCreate / hipMemMap ...), written before map_failed is set
-	struct JoinMapper { std::thread &t; std::atomic<int> &stop; ~JoinMapper() { stop = 1; if (t.joinable()) t.join(); } } join_mapper{mapper, stop};
-	{
-		DBuf *rec = &h->acx_rec;
-		const int dev = h->device;
-		char *const merr = map_err;
-		mapper = std::thread([rec, dev, merr, &want_lo, &want_top, &mapped_lo, &mapped_top, &map_failed, &stop]() {
-			auto give_up = [&](const char *what) { snprintf(merr, 400, "%s: %s", what, bhip_last_error()); (void)hipGetLastError(); map_failed = 1; };
+// The thread that maps the range's memory -- the top for the slice's sort, the bottom for the records so far plus this slice's (at most its
+// tuples) -- while the slice before is at work: mapping 230 GB in 1 GiB chunks takes seconds, which lie beside the kernels.  Stopped and
+// joined when it goes out of scope; nothing is unmapped here.
+struct RangeMapper {
+	std::atomic<int> failed{0}, stop{0};
+	std::atomic<size_t> mapped_lo{0}, mapped_top{0}, want_lo{0}, want_top{0};
+	char err[400] = "";      // the thread's own error text (hipMemCreate / hipMemMap ...), written before `failed` is set
+	std::thread t;
+	RangeMapper(DBuf *rec, int dev) {
+		t = std::thread([this, rec, dev]() {
+			auto give_up = [&](const char *what) { snprintf(err, sizeof err, "%s: %s", what, bhip_last_error()); (void)hipGetLastError(); failed = 1; };
 			if (hipSetDevice(dev) != hipSuccess) { give_up("hipSetDevice in the mapping thread"); return; }
 			size_t top = 0;
 			while (!stop.load()) {
@@ -839,124 +671,316 @@ static int build_accelerator_by_words(Handle *h, int K, int z, int part = 0, int
 			}
 		});
 	}
-	char *const va_end = h->acx_rec.as<char>() + va_size;
-	double t_map = 0, t_scan = 0, t_fill = 0, t_wait = 0;
-	auto lap = [&](double &acc, const std::chrono::steady_clock::time_point &from) { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - from).count(); };
-	for (uint32_t s = 0; s < n_slices; ++s) {
-		const uint64_t n_items = slice_items[s];
-		if (!n_items) continue;
-		want_top = buf_bytes(n_items);
-		want_lo = (size_t)(rec_n + n_items) * BHIP_REC_BYTES + 16;      // (the records so far are known, this slice's are at most its tuples)
-		if ((size_t)(rec_n + n_items) * BHIP_REC_BYTES + 16 + buf_bytes(n_items) > va_size) return fail(BHIP_E_INTERNAL, "accelerator build: slice %u does not fit its plan", s);
-		const auto tm0 = std::chrono::steady_clock::now();
-		while (mapped_top.load() < buf_bytes(n_items) && !map_failed.load()) std::this_thread::yield();
-		lap(t_map, tm0);
-		if (map_failed.load()) return fail(BHIP_E_DEVICE, "accelerator build: the sort's part of the record area could not be mapped (%s)", map_err);
-		unsigned long long *const k0 = (unsigned long long *)(va_end - buf_bytes(n_items));
-		unsigned long long *const k1 = (unsigned long long *)((char *)k0 + ((size_t)(n_items * 8 + 16 + 255) & ~(size_t)255));
-		uint16_t *const v0 = (uint16_t *)((char *)k1 + ((size_t)(n_items * 8 + 16 + 255) & ~(size_t)255));
-		const uint64_t w0 = (uint64_t)cuts[s] << shift, w1 = (uint64_t)cuts[s + 1] << shift;
-		uint32_t wl = 1; while ((1ull << wl) < w1 - w0) ++wl;
-		const uint32_t *cnt_s = d_counts.as<uint32_t>() + (size_t)s * nC;
-		size_t tb = tmp.cap;
-		HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, cnt_s, d_off.as<uint32_t>(), (int)nC, h->stream));
-		hipLaunchKernelGGL(k_acx_wwrite, dim3(g), dim3(256), 0, h->stream, h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), d_bad.as<uint8_t>(),
-			nC, h->tot_refs, K, z ? 1 : 0, (uint32_t)w0, (uint32_t)std::min<uint64_t>(w1, 0xFFFFFFFFull), cbits, d_off.as<uint32_t>(), k0);
+	~RangeMapper() { stop = 1; if (t.joinable()) t.join(); }
+	void want(size_t top_bytes, size_t lo_bytes) { want_top = top_bytes; want_lo = lo_bytes; }
+	// until that much is mapped; false: the thread gave up (`err` has its text)
+	bool wait_top(size_t bytes) { while (mapped_top.load() < bytes && !failed.load()) std::this_thread::yield(); return !failed.load(); }
+	bool wait_lo(size_t bytes) { while (mapped_lo.load() < bytes && !failed.load()) std::this_thread::yield(); return !failed.load(); }
+};
+
+// Step 1 of both builders: the expansion estimate per clump (k_acx_budget) -> BadList, and the clumps' "is bad" bytes on the device
+struct AcxBudget {
+	std::vector<unsigned long long> nexp;      // per clump: the words its ambiguous windows expand to
+	std::vector<uint8_t> is_bad;
+	std::vector<uint32_t> badlist;
+	DTmp d_bad;
+};
+static int acx_mark_bad_clumps(Handle *h, int K, int z, AcxBudget &bg) {
+	const uint32_t nC = h->n_clumps;
+	std::vector<unsigned long long> tsum(nC);
+	bg.nexp.assign(nC, 0); bg.is_bad.assign(nC, 0); bg.badlist.clear();
+	{
+		DTmp d_ts, d_nx;
+		ARC(d_ts.reserve((size_t)nC * 8)); ARC(d_nx.reserve((size_t)nC * 8));
+		HIPCHK(hipMemsetAsync(d_ts.p, 0, (size_t)nC * 8, h->stream)); HIPCHK(hipMemsetAsync(d_nx.p, 0, (size_t)nC * 8, h->stream));
+		hipLaunchKernelGGL(k_acx_budget, dim3(std::min<uint32_t>((nC * 16u + 255u) / 256u, (uint32_t)h->n_cu * 16)), dim3(256), 0, h->stream, h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(),
+			h->clump_len.as<uint32_t>(), nC, h->tot_refs, K, z ? 1 : 0, d_ts.as<unsigned long long>(), d_nx.as<unsigned long long>());
 		HIPCHK(hipGetLastError());
-		if (dbg) { const auto tc0 = std::chrono::steady_clock::now(); HIPCHK(hipStreamSynchronize(h->stream)); lap(t_scan, tc0); }      // (BHIP_DEBUG: the scan timed on its own)
-		const auto ts0 = std::chrono::steady_clock::now();
-		hipcub::DoubleBuffer<unsigned long long> dk(k0, k1);
-		tb = tmp.cap;
-		HIPCHK(hipcub::DeviceRadixSort::SortKeys(tmp.p, tb, dk, (int)n_items, (int)cbits, (int)(cbits + wl), h->stream));
-		unsigned long long *skeys = dk.Current(), *ukeys = dk.Alternate();
-		hipcub::TransformInputIterator<unsigned long long, AcxWKeyOf, const unsigned long long *> kin(skeys, AcxWKeyOf());
-		hipcub::TransformInputIterator<uint16_t, AcxWLaneOf, const unsigned long long *> vin(skeys, AcxWLaneOf());
-		tb = tmp.cap;
-		HIPCHK(hipcub::DeviceReduce::ReduceByKey(tmp.p, tb, kin, ukeys, vin, v0, nruns.as<uint32_t>(), BitOrU16(), (int)n_items, h->stream));
-		uint32_t n_unique = 0, last_off = 0, last_cnt = 0;
-		HIPCHK(hipMemcpyAsync(&n_unique, nruns.p, 4, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipMemcpyAsync(&last_off, d_off.as<uint32_t>() + (nC - 1), 4, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipMemcpyAsync(&last_cnt, cnt_s + (nC - 1), 4, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipMemcpyAsync(tsum.data(), d_ts.p, (size_t)nC * 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipMemcpyAsync(bg.nexp.data(), d_nx.p, (size_t)nC * 8, hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));
-		// (the tuples the counting scan attributed to this slice are the tuples the plan sized its buffers for: anything else means
-		// the write pass and the sort did not see the same data -- stop before the records are stored)
-		if ((uint64_t)last_off + last_cnt != n_items) return fail(BHIP_E_INTERNAL, "accelerator build: slice %u holds %llu tuples, its plan says %llu", s, (unsigned long long)last_off + last_cnt, (unsigned long long)n_items);
-		if (dbg) t_sort += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts0).count();
-		const auto tw0 = std::chrono::steady_clock::now();
-		while (mapped_lo.load() < (rec_n + n_unique) * BHIP_REC_BYTES + 16 && !map_failed.load()) std::this_thread::yield();
-		lap(t_wait, tw0);
-		if (map_failed.load()) return fail(BHIP_E_DEVICE, "accelerator build: the record area could not be mapped (%llu records so far; %s)", (unsigned long long)rec_n, map_err);
-		const auto tf0 = std::chrono::steady_clock::now();
-		hipLaunchKernelGGL(k_acx_wfill, dim3(g), dim3(256), 0, h->stream, ukeys, v0, n_unique, (uint32_t)w0, cbits,
-			h->acx_rec.as<uint32_t>() + rec_n, d_lens.as<uint32_t>(), all_lanes);
-		HIPCHK(hipGetLastError());
-		rec_n += n_unique;
-		HIPCHK(hipStreamSynchronize(h->stream));
-		lap(t_fill, tf0);
 	}
-	stop = 1;
-	if (mapper.joinable()) mapper.join();
-	// (nothing is unmapped here: the range is cut back to its final size when that is known -- behind the offset lines)
-	if (dbg) fprintf(stderr, "[bhip] word-sliced build, inside the slices: %.2f s scans, %.2f s sort + fold, %.2f s records, %.2f s waiting for the sort's part of the range, %.2f s for the records' part\n", t_scan, t_sort, t_fill, t_map, t_wait);
+	const unsigned long long full_size = K > 14 ? 0x7FFFFFFFull : (1ull << 24);      // burst.c:3322
+	for (uint32_t c = 0; c < nC; ++c) if (tsum[c] >= full_size) { bg.is_bad[c] = 1; bg.badlist.push_back(c); }
+	ARC(bg.d_bad.reserve((size_t)nC + 16));
+	HIPCHK(hipMemcpyAsync(bg.d_bad.p, bg.is_bad.data(), nC, hipMemcpyHostToDevice, h->stream));
 	return 0;
-	};
-	int rc = local_part();
-	std::vector<uint64_t> boff((size_t)n_parts + 1, 0);
-	if (coop) {      // the list lengths of the other ranks' words (a rank that could not build its own says so: everyone leaves)
-		for (int r = 0; r <= n_parts; ++r) boff[r] = ((uint64_t)rb[r] << shift) * 4ull;
-		const int st = share(share_ctx, d_lens.p, boff.data(), part, n_parts, rc != 0);
-		if (rc < 0) return rc;
-		if (st < 0) return fail(BHIP_E_DEVICE, "cooperative accelerator build: the exchange of the list lengths failed");
-		if (rc || st) return 1;
-	} else if (rc) return rc;
-	const double t_own = since();
-	uint64_t tot = 0; uint32_t maxlen = 0;
-	rc = acx_lines_from_lens(h, d_lens.as<uint32_t>(), nw, &tot, &maxlen, &lines_scratch);
-	const double t_lines = since() - t_own;
-	std::vector<unsigned long long> eoff((size_t)n_parts + 1, 0);      // first record of every rank's region
-	if (coop && !rc) {
-		DTmp d_sum, tmp;
-		rc = d_sum.reserve((size_t)n_parts * 8);
-		hipcub::TransformInputIterator<unsigned long long, U32To64, const uint32_t *> in(d_lens.as<uint32_t>(), U32To64());
-		for (int r = 0; r < n_parts && !rc; ++r) {
-			const uint64_t w0 = (uint64_t)rb[r] << shift, w1 = (uint64_t)rb[r + 1] << shift;
-			size_t tb = 0;
-			if (hipcub::DeviceReduce::Sum(nullptr, tb, in + w0, d_sum.as<unsigned long long>() + r, (int)(w1 - w0), h->stream) != hipSuccess || (rc = tmp.reserve(tb)) ||
-			    hipcub::DeviceReduce::Sum(tmp.p, tb, in + w0, d_sum.as<unsigned long long>() + r, (int)(w1 - w0), h->stream) != hipSuccess) { if (!rc) rc = fail(BHIP_E_DEVICE, "cooperative accelerator build: region sizes"); }
-		}
-		if (!rc && (hipMemcpyAsync(eoff.data() + 1, d_sum.p, (size_t)n_parts * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess))
-			rc = fail(BHIP_E_DEVICE, "cooperative accelerator build: region sizes");
-		for (int r = 0; r < n_parts; ++r) eoff[r + 1] += eoff[r];
-		if (!rc && (eoff[n_parts] != tot || eoff[part + 1] - eoff[part] != rec_n))
-			rc = fail(BHIP_E_INTERNAL, "cooperative accelerator build: rank %d wrote %llu records, its lists add up to %llu (all: %llu of %llu)", part, (unsigned long long)rec_n,
-				(unsigned long long)(eoff[part + 1] - eoff[part]), (unsigned long long)eoff[n_parts], (unsigned long long)tot);
-		// the whole record area, this rank's region moved to its place, the other regions from their builders
-		if (!rc) rc = h->acx_rec.grow_to(tot * BHIP_REC_BYTES + 16);
-		if (!rc) rc = acx_move_up(h, h->acx_rec.as<char>(), rec_n * BHIP_REC_BYTES, eoff[part] * BHIP_REC_BYTES);
-		if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(BHIP_E_DEVICE, "cooperative accelerator build: moving the region");
-		for (int r = 0; r <= n_parts; ++r) boff[r] = eoff[r] * BHIP_REC_BYTES;
-		const int st = share(share_ctx, h->acx_rec.p, boff.data(), part, n_parts, rc != 0);
-		if (rc < 0) { h->acx_rec.release(); h->acx_lines.release(); return rc; }
-		if (st < 0) { h->acx_rec.release(); h->acx_lines.release(); return fail(BHIP_E_DEVICE, "cooperative accelerator build: the exchange of the records failed"); }
-		if (st) return 1;
-	} else if (coop) {      // (the offset lines failed here: the others must not wait)
-		(void)share(share_ctx, h->acx_rec.p, boff.data(), part, n_parts, 1);
-		return rc;
+}
+
+// What the steps of build_accelerator_by_words hand each other.  Every step returns 0, 1 = cannot run here (nothing to report), or < 0 = error.
+struct WordBuild {
+	Handle *const h; const int K, z, part, n_parts; const bhip_share_fn share; void *const share_ctx;
+	const bool coop, dbg;
+	const uint32_t nC, shift, n_buckets, g, all_lanes;      // (buckets of 2^shift words; g: blocks of the scans)
+	uint32_t cbits = 1;                                     // bits of a clump number
+	const uint64_t nw, n_lines;
+	AcxBudget bad;                                          // 1
+	std::vector<unsigned long long> hist;                   // 2: tuples per bucket, whole database
+	uint64_t total = 0;
+	std::vector<uint32_t> rb;                               // 3: bucket boundaries of the ranks' runs
+	size_t va_size = 0;                                     // 4: the record area's range
+	BhipAcxPlan plan;                                       // 5: the slices of this rank's run
+	DTmp d_lens, lines_scratch;                             //    list lengths of all words; acx_lines_from_lens' scratch
+	DTmp d_b2s, d_counts, d_off, nruns, tmp;                // 6: tuples per (slice, clump), the slice loop's buffers and the library's scratch
+	uint64_t rec_n = 0;                                     // 7: records [0, rec_n) of the record area are this rank's lists
+	std::vector<uint64_t> boff;                             // 8, 10: byte offsets of the ranks' parts in the array that is exchanged
+	uint64_t tot = 0;                                       // 9: entries of the whole accelerator
+	std::vector<unsigned long long> eoff;                   // 10: first record of every rank's region
+	const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+	double t_hist = 0, t_count = 0, t_sort = 0, t_own = 0, t_lines = 0;
+	WordBuild(Handle *h_, int K_, int z_, int part_, int n_parts_, bhip_share_fn share_, void *ctx_) : h(h_), K(K_), z(z_), part(part_), n_parts(n_parts_), share(share_), share_ctx(ctx_),
+		coop(n_parts_ > 1), dbg(getenv("BHIP_DEBUG") != nullptr), nC(h_->n_clumps), shift((uint32_t)(2 * K_) - (uint32_t)std::min(12, 2 * K_)), n_buckets(1u << std::min(12, 2 * K_)),
+		g((uint32_t)h_->n_cu * 16), all_lanes(getenv("BHIP_NO_LANE_MASKS") ? 1u : 0u), nw(1ull << (2 * K_)), n_lines((nw + BHIP_ACX_LINE_WORDS - 1) / BHIP_ACX_LINE_WORDS),
+		rb((size_t)n_parts_ + 1, 0), boff((size_t)n_parts_ + 1, 0), eoff((size_t)n_parts_ + 1, 0) { while ((1ull << cbits) < nC) ++cbits; }
+	double since() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); }
+	uint32_t own0() const { return rb[part]; }
+	uint32_t own1() const { return rb[part + 1]; }
+	void release_own_scratch() { tmp.release(); nruns.release(); d_off.release(); d_counts.release(); d_b2s.release(); bad.d_bad.release(); }
+};
+static void lap(double &acc, const std::chrono::steady_clock::time_point &from) { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - from).count(); }
+
+// 1. expansion estimate per clump -> BadList (as the clump-sliced builder); 1 where this builder cannot run at all
+static int words_mark_bad(WordBuild &b) {
+	if (b.cbits > 24) return 1;
+	if (b.coop) if (const char *ev = getenv("BHIP_TEST_COOP_FAIL_RANK")) if (atoi(ev) == b.part) return 1;      // (test hook: this rank cannot -> all ranks build alone)
+	ARC(acx_mark_bad_clumps(b.h, b.K, b.z, b.bad));
+	for (uint32_t c = 0; c < b.nC; ++c) if (!b.bad.is_bad[c] && 16ull * b.h->h_clump_len[c] + b.bad.nexp[c] >= (1ull << 31)) return 1;
+	return 0;
+}
+// 2. tuples per bucket of words, whole database
+static int words_histogram(WordBuild &b) {
+	Handle *h = b.h;
+	b.hist.assign(b.n_buckets, 0);
+	DTmp d_hist;
+	ARC(d_hist.reserve((size_t)b.n_buckets * 8));
+	HIPCHK(hipMemsetAsync(d_hist.p, 0, (size_t)b.n_buckets * 8, h->stream));
+	hipLaunchKernelGGL(k_acx_whist, dim3(b.g), dim3(256), 0, h->stream, h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), b.bad.d_bad.as<uint8_t>(),
+		b.nC, h->tot_refs, b.K, b.z ? 1 : 0, b.shift, b.n_buckets, d_hist.as<unsigned long long>());
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(b.hist.data(), d_hist.p, (size_t)b.n_buckets * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
+	b.t_hist = b.since();
+	b.total = bhip_acx_run_tuples(b.hist, 0, b.n_buckets);
+	return b.total ? 0 : 1;
+}
+// 4. The record area is ONE address range (DBuf::reserve_growable) and the sort works inside it: the records fill it from the bottom, the
+// slice at hand is sorted and folded at its TOP -- two 8-byte tuple arrays and the folded lane masks, 18 bytes per tuple -- in the part
+// the records have not reached yet.  So a slice may have as many tuples as fit between the records so far and the top,
+// 4 (before + n) + 18 n <= range: the early slices take what one sort call takes (2^31 tuples), the last ones what is left beside
+// 216 GB of records -- 28 slices at the metric's size, where "one record per tuple, and the sort buffers beside them" gave 64.  Every
+// slice costs one scan of the references, so fewer, larger slices are what makes this builder cheap.  Nothing is unmapped before the
+// build is over (first version: sort buffers of their own, mapped and unmapped slice by slice -- ranks building side by side read each
+// other's regions back as zeros once in three runs; with ordinary allocations of a fixed size: never in 48).
+// The range's size (bhip_acx_range_bytes) comes from what the device has free beyond what is set aside for the rest:
+// (round 6: 24 GB instead of 3 left alone beyond the tables.  What the sort's part of the range gives back at the end of the build is not
+// allocatable at once -- nor is all of what a process that held the device a moment ago gave back, whatever hipMemGetInfo says: behind a
+// parent that had opened and closed the same database, `burst_hip` at the metric's size could allocate 2.5 GB with 16 GB reported free -- and
+// the caller's batch buffers, 7.4 GB for 2 M-entry batches, are reserved right behind the build.  The price: the last slices sort in less room.)
+static int words_reserve_range(WordBuild &b) {
+	Handle *h = b.h;
+	size_t free_b = 0, total_b = 0;
+	HIPCHK(hipMemGetInfo(&free_b, &total_b));
+	const double other = (double)b.nw * 4.0 + (double)(b.n_lines + 1) * 64.0 + (double)acx_lines_scratch_bytes(b.nw) + (double)b.nC * 8.0 + 40.0 * b.nC * 4.0 + (double)(24ull << 30);
+	const size_t va_plan = bhip_acx_range_bytes((double)free_b - other, b.total, bhip_acx_run_tuples(b.hist, b.own0(), b.own1()), BHIP_REC_BYTES, DBuf::kChunk);
+	if (!va_plan) return 1;      // (not even the records fit)
+	if (h->acx_rec.reserve_growable(va_plan, h->device)) return 1;
+	b.va_size = h->acx_rec.va_size;
+	if (getenv("BHIP_DEBUG")) fprintf(stderr, "[bhip] word-sliced build: %.2f GB free at its start, %.2f GB set aside for the rest, range of %.2f GB for %.2f GB of records at most\n", free_b / 1e9, other / 1e9, b.va_size / 1e9, (double)b.total * BHIP_REC_BYTES / 1e9);
+	return 0;
+}
+// 5. inside this rank's run the slices (bhip_acx_plan_run); a rank whose run of buckets is empty has none and only receives
+static int words_plan_slices(WordBuild &b) {
+	long long forced_slice = 0;
+	if (const char *ev = getenv("BHIP_MASK_SLICE")) forced_slice = atoll(ev);
+	if (b.own1() > b.own0() && bhip_acx_run_tuples(b.hist, b.own0(), b.own1()) && !bhip_acx_plan_run(b.hist, b.own0(), b.own1(), b.shift, b.va_size, forced_slice, BHIP_REC_BYTES, &b.plan)) return 1;
+	return 0;
+}
+// (the tables that stay: now, while the device has room -- an allocation next to 216 GB of mapped records takes half a second)
+static int words_reserve_tables(WordBuild &b) {
+	Handle *h = b.h;
+	if (const char *ev = getenv("BHIP_TEST_ENTRY_BIAS")) h->acx_bias = strtoull(ev, nullptr, 0);
+	h->K = b.K;
+	ARC(b.d_lens.reserve(b.nw * 4 + 16));
+	HIPCHK(hipMemsetAsync(b.d_lens.p, 0, b.nw * 4, h->stream));
+	ARC(h->acx_lines.reserve_exact((b.n_lines + 1) * 64));
+	ARC(b.lines_scratch.reserve(acx_lines_scratch_bytes(b.nw)));
+	return 0;
+}
+// 6. tuples per (slice, clump) in one scan; the library calls' own scratch for the largest slice, once
+static int words_count(WordBuild &b) {
+	Handle *h = b.h;
+	const uint32_t n_slices = b.plan.n_slices(), nC = b.nC;
+	if (!n_slices) { HIPCHK(hipStreamSynchronize(h->stream)); return 0; }
+	std::vector<uint8_t> b2s(b.n_buckets, 0xFF);
+	for (uint32_t s = 0; s < n_slices; ++s) for (uint32_t bk = b.plan.cuts[s]; bk < b.plan.cuts[s + 1]; ++bk) b2s[bk] = (uint8_t)s;
+	ARC(b.d_b2s.reserve(b.n_buckets)); ARC(b.d_counts.reserve_exact((size_t)n_slices * nC * 4 + 16)); ARC(b.d_off.reserve((size_t)nC * 4 + 16));
+	HIPCHK(hipMemcpyAsync(b.d_b2s.p, b2s.data(), b.n_buckets, hipMemcpyHostToDevice, h->stream));
+	hipLaunchKernelGGL(k_acx_wcount, dim3(b.g), dim3(256), 0, h->stream, h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), b.bad.d_bad.as<uint8_t>(),
+		nC, h->tot_refs, b.K, b.z ? 1 : 0, b.shift, b.n_buckets, b.d_b2s.as<uint8_t>(), n_slices, b.d_counts.as<uint32_t>());
+	HIPCHK(hipGetLastError());
+	ARC(b.nruns.reserve(16));
+	size_t tb = 0, tb1 = 0;
+	hipcub::DoubleBuffer<unsigned long long> dk((unsigned long long *)nullptr, (unsigned long long *)nullptr);
+	HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb1, dk, (int)b.plan.cap_items, (int)b.cbits, (int)(b.cbits + 26), h->stream)); tb = std::max(tb, tb1);
+	hipcub::TransformInputIterator<unsigned long long, AcxWKeyOf, const unsigned long long *> kin((const unsigned long long *)nullptr, AcxWKeyOf());
+	hipcub::TransformInputIterator<uint16_t, AcxWLaneOf, const unsigned long long *> vin((const unsigned long long *)nullptr, AcxWLaneOf());
+	HIPCHK(hipcub::DeviceReduce::ReduceByKey(nullptr, tb1, kin, (unsigned long long *)nullptr, vin, (uint16_t *)nullptr, (uint32_t *)nullptr, BitOrU16(), (int)b.plan.cap_items, h->stream)); tb = std::max(tb, tb1);
+	HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb1, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)nC, h->stream)); tb = std::max(tb, tb1);
+	ARC(b.tmp.reserve(tb + tb / 4 + 4096));
+	HIPCHK(hipStreamSynchronize(h->stream));
+	b.t_count = b.since();
+	return 0;
+}
+// 7. one slice: offsets, tuples, sort over the slice's word bits, fold, records
+struct SliceTimes { double map = 0, scan = 0, fill = 0, wait = 0; };
+static int words_build_slice(WordBuild &b, uint32_t s, RangeMapper &mapper, SliceTimes &tm) {
+	Handle *h = b.h;
+	const uint32_t nC = b.nC;
+	const uint64_t n_items = b.plan.items[s];
+	if (!n_items) return 0;
+	mapper.want(bhip_acx_buf_bytes(n_items), (size_t)(b.rec_n + n_items) * BHIP_REC_BYTES + 16);      // (the records so far are known, this slice's are at most its tuples)
+	if ((size_t)(b.rec_n + n_items) * BHIP_REC_BYTES + 16 + bhip_acx_buf_bytes(n_items) > b.va_size) return fail(BHIP_E_INTERNAL, "accelerator build: slice %u does not fit its plan", s);
+	const auto tm0 = std::chrono::steady_clock::now();
+	const bool top_there = mapper.wait_top(bhip_acx_buf_bytes(n_items));
+	lap(tm.map, tm0);
+	if (!top_there) return fail(BHIP_E_DEVICE, "accelerator build: the sort's part of the record area could not be mapped (%s)", mapper.err);
+	unsigned long long *const k0 = (unsigned long long *)(h->acx_rec.as<char>() + b.va_size - bhip_acx_buf_bytes(n_items));
+	unsigned long long *const k1 = (unsigned long long *)((char *)k0 + bhip_acx_key_bytes(n_items));
+	uint16_t *const v0 = (uint16_t *)((char *)k1 + bhip_acx_key_bytes(n_items));
+	const uint64_t w0 = (uint64_t)b.plan.cuts[s] << b.shift, w1 = (uint64_t)b.plan.cuts[s + 1] << b.shift;
+	uint32_t wl = 1; while ((1ull << wl) < w1 - w0) ++wl;
+	const uint32_t *cnt_s = b.d_counts.as<uint32_t>() + (size_t)s * nC;
+	size_t tb = b.tmp.cap;
+	HIPCHK(hipcub::DeviceScan::ExclusiveSum(b.tmp.p, tb, cnt_s, b.d_off.as<uint32_t>(), (int)nC, h->stream));
+	hipLaunchKernelGGL(k_acx_wwrite, dim3(b.g), dim3(256), 0, h->stream, h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), b.bad.d_bad.as<uint8_t>(),
+		nC, h->tot_refs, b.K, b.z ? 1 : 0, (uint32_t)w0, (uint32_t)std::min<uint64_t>(w1, 0xFFFFFFFFull), b.cbits, b.d_off.as<uint32_t>(), k0);
+	HIPCHK(hipGetLastError());
+	if (b.dbg) { const auto tc0 = std::chrono::steady_clock::now(); HIPCHK(hipStreamSynchronize(h->stream)); lap(tm.scan, tc0); }      // (BHIP_DEBUG: the scan timed on its own)
+	const auto ts0 = std::chrono::steady_clock::now();
+	hipcub::DoubleBuffer<unsigned long long> dk(k0, k1);
+	tb = b.tmp.cap;
+	HIPCHK(hipcub::DeviceRadixSort::SortKeys(b.tmp.p, tb, dk, (int)n_items, (int)b.cbits, (int)(b.cbits + wl), h->stream));
+	unsigned long long *skeys = dk.Current(), *ukeys = dk.Alternate();
+	hipcub::TransformInputIterator<unsigned long long, AcxWKeyOf, const unsigned long long *> kin(skeys, AcxWKeyOf());
+	hipcub::TransformInputIterator<uint16_t, AcxWLaneOf, const unsigned long long *> vin(skeys, AcxWLaneOf());
+	tb = b.tmp.cap;
+	HIPCHK(hipcub::DeviceReduce::ReduceByKey(b.tmp.p, tb, kin, ukeys, vin, v0, b.nruns.as<uint32_t>(), BitOrU16(), (int)n_items, h->stream));
+	uint32_t n_unique = 0, last_off = 0, last_cnt = 0;
+	HIPCHK(hipMemcpyAsync(&n_unique, b.nruns.p, 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(&last_off, b.d_off.as<uint32_t>() + (nC - 1), 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(&last_cnt, cnt_s + (nC - 1), 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
+	// (the tuples the counting scan attributed to this slice are the tuples the plan sized its buffers for: anything else means
+	// the write pass and the sort did not see the same data -- stop before the records are stored)
+	if ((uint64_t)last_off + last_cnt != n_items) return fail(BHIP_E_INTERNAL, "accelerator build: slice %u holds %llu tuples, its plan says %llu", s, (unsigned long long)last_off + last_cnt, (unsigned long long)n_items);
+	if (b.dbg) b.t_sort += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts0).count();
+	const auto tw0 = std::chrono::steady_clock::now();
+	const bool lo_there = mapper.wait_lo((b.rec_n + n_unique) * BHIP_REC_BYTES + 16);
+	lap(tm.wait, tw0);
+	if (!lo_there) return fail(BHIP_E_DEVICE, "accelerator build: the record area could not be mapped (%llu records so far; %s)", (unsigned long long)b.rec_n, mapper.err);
+	const auto tf0 = std::chrono::steady_clock::now();
+	hipLaunchKernelGGL(k_acx_wfill, dim3(b.g), dim3(256), 0, h->stream, ukeys, v0, n_unique, (uint32_t)w0, b.cbits,
+		h->acx_rec.as<uint32_t>() + b.rec_n, b.d_lens.as<uint32_t>(), b.all_lanes);
+	HIPCHK(hipGetLastError());
+	b.rec_n += n_unique;
+	HIPCHK(hipStreamSynchronize(h->stream));
+	lap(tm.fill, tf0);
+	return 0;
+}
+// 7. slice after slice, the range's memory mapped beside them
+// (nothing is unmapped here: the range is cut back to its final size when that is known -- behind the offset lines)
+static int words_run_slices(WordBuild &b) {
+	if (!b.plan.n_slices()) return 0;
+	SliceTimes tm;
+	{
+		RangeMapper mapper(&b.h->acx_rec, b.h->device);
+		for (uint32_t s = 0; s < b.plan.n_slices(); ++s) ARC(words_build_slice(b, s, mapper, tm));
 	}
-	if (rc) return rc;
-	d_lens.release();
-	if (!coop && tot != rec_n) return fail(BHIP_E_INTERNAL, "accelerator build: %llu records written, the list lengths add up to %llu", (unsigned long long)rec_n, (unsigned long long)tot);
+	if (b.dbg) fprintf(stderr, "[bhip] word-sliced build, inside the slices: %.2f s scans, %.2f s sort + fold, %.2f s records, %.2f s waiting for the sort's part of the range, %.2f s for the records' part\n", tm.scan, b.t_sort, tm.fill, tm.map, tm.wait);
+	return 0;
+}
+// 8. the list lengths of the other ranks' words, with this rank's `rc` so far (a rank that could not build its own says so: everyone leaves)
+static int words_exchange_lengths(WordBuild &b, int rc) {
+	if (!b.coop) return rc;
+	for (int r = 0; r <= b.n_parts; ++r) b.boff[r] = ((uint64_t)b.rb[r] << b.shift) * 4ull;
+	const int st = b.share(b.share_ctx, b.d_lens.p, b.boff.data(), b.part, b.n_parts, rc != 0);
+	if (rc < 0) return rc;
+	if (st < 0) return fail(BHIP_E_DEVICE, "cooperative accelerator build: the exchange of the list lengths failed");
+	return rc || st ? 1 : 0;
+}
+// 10. (cooperative) the regions' places from the list lengths, the whole record area, this rank's region moved to its place
+static int words_place_regions(WordBuild &b) {
+	Handle *h = b.h;
+	const int n_parts = b.n_parts, part = b.part;
+	DTmp d_sum, tmp;
+	ARC(d_sum.reserve((size_t)n_parts * 8));
+	hipcub::TransformInputIterator<unsigned long long, U32To64, const uint32_t *> in(b.d_lens.as<uint32_t>(), U32To64());
+	for (int r = 0; r < n_parts; ++r) {
+		const uint64_t w0 = (uint64_t)b.rb[r] << b.shift, w1 = (uint64_t)b.rb[r + 1] << b.shift;
+		ARC(with_scratch(tmp, [&](void *t, size_t &tb) {
+			return hipcub::DeviceReduce::Sum(t, tb, in + w0, d_sum.as<unsigned long long>() + r, (int)(w1 - w0), h->stream) == hipSuccess ? 0 : fail(BHIP_E_DEVICE, "cooperative accelerator build: region sizes"); }));
+	}
+	if (hipMemcpyAsync(b.eoff.data() + 1, d_sum.p, (size_t)n_parts * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+		return fail(BHIP_E_DEVICE, "cooperative accelerator build: region sizes");
+	for (int r = 0; r < n_parts; ++r) b.eoff[r + 1] += b.eoff[r];
+	if (b.eoff[n_parts] != b.tot || b.eoff[part + 1] - b.eoff[part] != b.rec_n)
+		return fail(BHIP_E_INTERNAL, "cooperative accelerator build: rank %d wrote %llu records, its lists add up to %llu (all: %llu of %llu)", part, (unsigned long long)b.rec_n,
+			(unsigned long long)(b.eoff[part + 1] - b.eoff[part]), (unsigned long long)b.eoff[n_parts], (unsigned long long)b.tot);
+	ARC(h->acx_rec.grow_to(b.tot * BHIP_REC_BYTES + 16));
+	ARC(acx_move_up(h, h->acx_rec.as<char>(), b.rec_n * BHIP_REC_BYTES, b.eoff[part] * BHIP_REC_BYTES));
+	if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(BHIP_E_DEVICE, "cooperative accelerator build: moving the region");
+	return 0;
+}
+// 10. the other regions from their builders, with the `rc` of this rank's offset lines (where they failed, the others must not wait)
+static int words_exchange_records(WordBuild &b, int rc) {
+	Handle *h = b.h;
+	if (!b.coop) return rc;
+	if (rc) { (void)b.share(b.share_ctx, h->acx_rec.p, b.boff.data(), b.part, b.n_parts, 1); return rc; }
+	rc = words_place_regions(b);
+	for (int r = 0; r <= b.n_parts; ++r) b.boff[r] = b.eoff[r] * BHIP_REC_BYTES;
+	const int st = b.share(b.share_ctx, h->acx_rec.p, b.boff.data(), b.part, b.n_parts, rc != 0);
+	if (rc < 0) { h->acx_rec.release(); h->acx_lines.release(); return rc; }
+	if (st < 0) { h->acx_rec.release(); h->acx_lines.release(); return fail(BHIP_E_DEVICE, "cooperative accelerator build: the exchange of the records failed"); }
+	return st ? 1 : rc;
+}
+// 11. the range cut back to the records, the BadList, the handle's flags, the report
+static int words_finish(WordBuild &b) {
+	Handle *h = b.h;
+	const uint64_t tot = b.tot;
+	b.d_lens.release();
+	if (!b.coop && tot != b.rec_n) return fail(BHIP_E_INTERNAL, "accelerator build: %llu records written, the list lengths add up to %llu", (unsigned long long)b.rec_n, (unsigned long long)tot);
 	ARC(h->acx_rec.grow_to(tot * BHIP_REC_BYTES + 16));
 	h->acx_rec.shrink_to(tot * BHIP_REC_BYTES + 16);      // (the sort's part of the range and what was mapped ahead of the records go back)
-	ARC(set_badlist(h, badlist.data(), (uint32_t)badlist.size()));
-	h->has_acx = true; h->n_ent = tot; h->has_masks = !all_lanes;
-	if (dbg) fprintf(stderr, "[bhip] accelerator built on the device by word ranges%s: K=%d, %llu entries from %llu word tuples, %u slice(s) of at most %llu tuples here (%llu records), %zu clump(s) on the BadList, %.2f B per entry; "
-		"%.2f s (%.2f s histogram, %.2f s counts, %.2f s sort + fold, %.2f s until the own lists stood, %.2f s offset lines)\n", coop ? " (cooperative)" : "", K, (unsigned long long)tot, (unsigned long long)total, n_slices,
-		(unsigned long long)cap_items, (unsigned long long)rec_n, badlist.size(), tot ? (double)(h->acx_rec.cap + n_lines * 64) / (double)tot : 0.0, since(), t_hist, t_count - t_hist, t_sort, t_own, t_lines);
-	if (dbg) { size_t f_ = 0, t_ = 0; if (hipMemGetInfo(&f_, &t_) == hipSuccess) fprintf(stderr, "[bhip] after the build: %.2f GB of the device's %.2f free (record area %.2f GB mapped of a %.2f GB range)\n", f_ / 1e9, t_ / 1e9, h->acx_rec.cap / 1e9, h->acx_rec.va_size / 1e9); }
-	if (dbg && coop) fprintf(stderr, "[bhip] rank %d of %d: words [%llu, %llu), records [%llu, %llu)\n", part, n_parts, (unsigned long long)rb[part] << shift, (unsigned long long)rb[part + 1] << shift,
-		eoff[part], eoff[part + 1]);
+	ARC(set_badlist(h, b.bad.badlist.data(), (uint32_t)b.bad.badlist.size()));
+	h->has_acx = true; h->n_ent = tot; h->has_masks = !b.all_lanes;
+	if (b.dbg) fprintf(stderr, "[bhip] accelerator built on the device by word ranges%s: K=%d, %llu entries from %llu word tuples, %u slice(s) of at most %llu tuples here (%llu records), %zu clump(s) on the BadList, %.2f B per entry; "
+		"%.2f s (%.2f s histogram, %.2f s counts, %.2f s sort + fold, %.2f s until the own lists stood, %.2f s offset lines)\n", b.coop ? " (cooperative)" : "", b.K, (unsigned long long)tot, (unsigned long long)b.total, b.plan.n_slices(),
+		(unsigned long long)b.plan.cap_items, (unsigned long long)b.rec_n, b.bad.badlist.size(), tot ? (double)(h->acx_rec.cap + b.n_lines * 64) / (double)tot : 0.0, b.since(), b.t_hist, b.t_count - b.t_hist, b.t_sort, b.t_own, b.t_lines);
+	if (b.dbg) { size_t f_ = 0, t_ = 0; if (hipMemGetInfo(&f_, &t_) == hipSuccess) fprintf(stderr, "[bhip] after the build: %.2f GB of the device's %.2f free (record area %.2f GB mapped of a %.2f GB range)\n", f_ / 1e9, t_ / 1e9, h->acx_rec.cap / 1e9, h->acx_rec.va_size / 1e9); }
+	if (b.dbg && b.coop) fprintf(stderr, "[bhip] rank %d of %d: words [%llu, %llu), records [%llu, %llu)\n", b.part, b.n_parts, (unsigned long long)b.own0() << b.shift, (unsigned long long)b.own1() << b.shift,
+		b.eoff[b.part], b.eoff[b.part + 1]);
 	return 0;
+}
+// The steps in their order.  1 .. 7 are everything a rank does on its own (then: records [0, rec_n) of the record area are its lists, their
+// lengths in d_lens); a rank that fails in them still goes through the first exchange, so that nobody waits for it.
+static int build_accelerator_by_words(Handle *h, int K, int z, int part = 0, int n_parts = 1, bhip_share_fn share = nullptr, void *share_ctx = nullptr) {
+	WordBuild b(h, K, z, part, n_parts, share, share_ctx);
+	int rc = words_mark_bad(b);                                          // 1. the bad clumps
+	if (!rc) rc = words_histogram(b);                                    // 2. the bucket histogram
+	if (!rc) b.rb = bhip_acx_rank_runs(b.hist, n_parts);                 // 3. the ranks' runs of buckets (equal numbers of tuples)
+	if (!rc) rc = words_reserve_range(b);                                // 4. the record area's range
+	if (!rc) rc = words_plan_slices(b);                                  // 5. the slices of the own run
+	if (!rc) rc = words_reserve_tables(b);
+	if (!rc) rc = words_count(b);                                        // 6. tuples per (slice, clump), the library's scratch
+	if (!rc) rc = words_run_slices(b);                                   // 7. the slices
+	b.release_own_scratch();
+	if ((rc = words_exchange_lengths(b, rc))) return rc;                 // 8. the list lengths of all words
+	b.t_own = b.since();
+	uint32_t maxlen = 0;
+	rc = acx_lines_from_lens(h, b.d_lens.as<uint32_t>(), b.nw, &b.tot, &maxlen, &b.lines_scratch);      // 9. the offset lines
+	b.t_lines = b.since() - b.t_own;
+	if ((rc = words_exchange_records(b, rc))) return rc;                 // 10. the regions' places, the records of all words
+	return words_finish(b);                                              // 11.
 }
 
 static int build_accelerator_by_clumps(Handle *h, int K, int z);
@@ -1006,29 +1030,18 @@ static int build_accelerator_by_clumps(Handle *h, int K, int z) {
 	auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); };
 	if (const char *ev = getenv("BHIP_TEST_ENTRY_BIAS")) h->acx_bias = strtoull(ev, nullptr, 0);
 	h->K = K;
-	// 1. expansion estimate and true expansion per clump -> BadList
-	std::vector<unsigned long long> tsum(nC), nexp(nC);
-	std::vector<uint8_t> is_bad(nC, 0);
-	std::vector<uint32_t> badlist;
-	DTmp d_bad, d_soff;
-	{
-		DTmp d_ts, d_nx;
-		ARC(d_ts.reserve((size_t)nC * 8)); ARC(d_nx.reserve((size_t)nC * 8));
-		HIPCHK(hipMemsetAsync(d_ts.p, 0, (size_t)nC * 8, h->stream)); HIPCHK(hipMemsetAsync(d_nx.p, 0, (size_t)nC * 8, h->stream));
-		hipLaunchKernelGGL(k_acx_budget, dim3(std::min<uint32_t>((nC * 16u + 255u) / 256u, (uint32_t)h->n_cu * 16)), dim3(256), 0, h->stream, h->ref_lane.as<uint4>(), h->ref_off.as<uint64_t>(),
-			h->clump_len.as<uint32_t>(), nC, h->tot_refs, K, z ? 1 : 0, d_ts.as<unsigned long long>(), d_nx.as<unsigned long long>());
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(tsum.data(), d_ts.p, (size_t)nC * 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipMemcpyAsync(nexp.data(), d_nx.p, (size_t)nC * 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipStreamSynchronize(h->stream));
-	}
-	const unsigned long long full_size = K > 14 ? 0x7FFFFFFFull : (1ull << 24);      // burst.c:3322
-	for (uint32_t c = 0; c < nC; ++c) if (tsum[c] >= full_size) { is_bad[c] = 1; badlist.push_back(c); nexp[c] = 0; }
+	// 1. expansion estimate and true expansion per clump -> BadList (a bad clump has no tuples: its expansion does not count)
+	AcxBudget bg;
+	ARC(acx_mark_bad_clumps(h, K, z, bg));
+	std::vector<unsigned long long> &nexp = bg.nexp;
+	const std::vector<uint32_t> &badlist = bg.badlist;
+	DTmp &d_bad = bg.d_bad;
+	DTmp d_soff;
+	for (uint32_t c : badlist) nexp[c] = 0;
 	std::vector<uint64_t> slot_off(nC + 1), item_off(nC + 1);
 	slot_off[0] = item_off[0] = 0;
 	for (uint32_t c = 0; c < nC; ++c) { slot_off[c + 1] = slot_off[c] + 16ull * h->h_clump_len[c]; item_off[c + 1] = item_off[c] + 16ull * h->h_clump_len[c] + nexp[c]; }
-	ARC(d_bad.reserve((size_t)nC + 16)); ARC(d_soff.reserve(((size_t)nC + 1) * 8));
-	HIPCHK(hipMemcpyAsync(d_bad.p, is_bad.data(), nC, hipMemcpyHostToDevice, h->stream));
+	ARC(d_soff.reserve(((size_t)nC + 1) * 8));
 	HIPCHK(hipMemcpyAsync(d_soff.p, slot_off.data(), ((size_t)nC + 1) * 8, hipMemcpyHostToDevice, h->stream));
 	// 2. slices of clumps whose tuples fit the sort buffers (two 8-byte tuple arrays + the folded lane masks + the sort's own scratch; ONE budget: 33 bytes per tuple, planned
 	// with slack) next to what is resident at that time, of at most 2^cb clumps each (the slice-local clump number in the tuple).  The records
@@ -1117,15 +1130,12 @@ static int build_accelerator_by_clumps(Handle *h, int K, int z) {
 			h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), d_soff.as<uint64_t>(), d_bad.as<uint8_t>(), c0, c1, h->tot_refs, K, z ? 1 : 0,
 			cb, k0.as<unsigned long long>(), (unsigned long long)n_slots, d_xcur.as<unsigned long long>());
 		HIPCHK(hipGetLastError());
-		size_t tb = 0;
 		hipcub::DoubleBuffer<unsigned long long> dk(k0.as<unsigned long long>(), k1.as<unsigned long long>());
 		// The slots of a slice are laid out clump after clump, and the radix sort is stable: ordering the WORD bits (and the no-word bit
 		// above them) leaves the tuples of a word in ascending clump order -- 2 K + 1 bits, four passes, instead of 48 bits in six.  Only
 		// a slice with IUPAC expansions (appended behind the slots, out of clump order) needs the clump bits sorted as well.
 		const int bit0 = n_items == n_slots ? cb : 0;
-		HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, dk, (int)n_items, bit0, BHIP_ACX_KEYBITS, h->stream));
-		ARC(tmp.reserve(tb));
-		HIPCHK(hipcub::DeviceRadixSort::SortKeys(tmp.p, tb, dk, (int)n_items, bit0, BHIP_ACX_KEYBITS, h->stream));
+		ARC(with_scratch(tmp, [&](void *t, size_t &tb) { HIPCHK(hipcub::DeviceRadixSort::SortKeys(t, tb, dk, (int)n_items, bit0, BHIP_ACX_KEYBITS, h->stream)); return 0; }));
 		unsigned long long *skeys = dk.Current();
 		if (count_only) {      // first pass: the list lengths from the sorted tuples themselves (no folded copy is written or read)
 			hipLaunchKernelGGL(k_acx_hist_sorted, dim3((uint32_t)h->n_cu * 16), dim3(256), 0, h->stream, skeys, (uint32_t)n_items, cb, d_lens.as<uint32_t>());
@@ -1136,10 +1146,7 @@ static int build_accelerator_by_clumps(Handle *h, int K, int z) {
 		ukeys = dk.Alternate(); umasks = v0.as<uint16_t>(); spare = skeys;
 		hipcub::TransformInputIterator<unsigned long long, AcxKeyOf, const unsigned long long *> kin(skeys, AcxKeyOf());
 		hipcub::TransformInputIterator<uint16_t, AcxLanesOf, const unsigned long long *> vin(skeys, AcxLanesOf());
-		size_t tb2 = 0;
-		HIPCHK(hipcub::DeviceReduce::ReduceByKey(nullptr, tb2, kin, ukeys, vin, umasks, nruns.as<uint32_t>(), BitOrU16(), (int)n_items, h->stream));
-		ARC(tmp.reserve(tb2));
-		HIPCHK(hipcub::DeviceReduce::ReduceByKey(tmp.p, tb2, kin, ukeys, vin, umasks, nruns.as<uint32_t>(), BitOrU16(), (int)n_items, h->stream));
+		ARC(with_scratch(tmp, [&](void *t, size_t &tb) { HIPCHK(hipcub::DeviceReduce::ReduceByKey(t, tb, kin, ukeys, vin, umasks, nruns.as<uint32_t>(), BitOrU16(), (int)n_items, h->stream)); return 0; }));
 		HIPCHK(hipMemcpyAsync(&n_unique, nruns.p, 4, hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));
 		return 0;
@@ -1180,10 +1187,7 @@ static int build_accelerator_by_clumps(Handle *h, int K, int z) {
 		uint32_t *head_in = (uint32_t *)spare, *head = head_in + n_unique;      // 8 bytes per tuple of scratch: the sorted key buffer
 		hipLaunchKernelGGL(k_acx_heads, dim3(g), dim3(256), 0, h->stream, ukeys, n_unique, cb, head_in);
 		HIPCHK(hipGetLastError());
-		size_t tb = 0;
-		HIPCHK(hipcub::DeviceScan::InclusiveScan(nullptr, tb, head_in, head, hipcub::Max(), (int)n_unique, h->stream));
-		ARC(tmp.reserve(tb));
-		HIPCHK(hipcub::DeviceScan::InclusiveScan(tmp.p, tb, head_in, head, hipcub::Max(), (int)n_unique, h->stream));
+		ARC(with_scratch(tmp, [&](void *t, size_t &tb) { HIPCHK(hipcub::DeviceScan::InclusiveScan(t, tb, head_in, head, hipcub::Max(), (int)n_unique, h->stream)); return 0; }));
 		hipLaunchKernelGGL(k_acx_fill, dim3(g), dim3(256), 0, h->stream, h->acx_view(), ukeys, umasks, head, n_unique, cb, cuts[s],
 			refold ? d_cursor.as<uint32_t>() : (const uint32_t *)nullptr, (uint32_t *)h->acx_view().rec, all_lanes);
 		HIPCHK(hipGetLastError());

@@ -186,6 +186,38 @@ def test_cooperative_build_equals_the_single_rank_build(db, K, z, n_ranks, slice
     d.close()
 
 
+def test_cooperative_build_with_a_rank_that_only_receives(tmp_path, monkeypatch, capfd):
+    """a rank whose run of word buckets is empty builds nothing and only receives -- and still takes part in both exchanges.  40 references
+    of 300 A's with one substitution each: nearly every K = 12 word lies in the first bucket of 2^12 words (AAAAAA......), so of three ranks
+    the first gets that bucket, the last every other one and the middle one none (its BHIP_DEBUG line reads `words [4096, 4096)`).  Every
+    rank's four tables equal the single-rank build's."""
+    from burst_amd import host
+    fa = str(tmp_path / "polya.fa")
+    with open(fa, "w") as f:
+        for i in range(40):
+            s = bytearray(b"A" * 300)
+            s[5 + 7 * i] = b"CGT"[i % 3]
+            f.write(">r%d\n%s\n" % (i, s.decode()))
+    d = host.Db.from_fasta(fa, 120, 0.95, shear_len=500)
+    monkeypatch.setenv("BHIP_ACX_BUILD", "clumps")
+    solo = d.open_device(0, 1, build_K=12)
+    want = _export(solo, 12)
+    solo.close()
+    monkeypatch.delenv("BHIP_ACX_BUILD")
+    assert len(want[1]) > 100
+    monkeypatch.setenv("BHIP_DEBUG", "1")
+    capfd.readouterr()
+    devs = d.open_devices_team([0, 0, 0], 1, build_K=12)
+    err = capfd.readouterr().err
+    print(err)
+    assert err.count("(cooperative)") == 3 and "rank 1 of 3: words [4096, 4096), records [" in err, err[-3000:]
+    for r, dev in enumerate(devs):
+        for name, a, b in zip(("list lengths", "clump ids", "lane sets", "BadList"), want, _export(dev, 12)):
+            assert np.array_equal(a, b), "rank %d's %s differ" % (r, name)
+        dev.close()
+    d.close()
+
+
 def test_cooperative_build_falls_back_together(monkeypatch):
     """a rank that cannot do its share announces it in the first exchange and EVERY rank builds alone (nobody waits, same tables)"""
     from burst_amd import host

@@ -521,3 +521,39 @@ def test_prefilter_variant_table_keeps_the_rules_it_was_made_from(tmp_path):
              ((-1, 2, 0, 1, 25.0, 4.0, 8), 3)]                                 # t_all = 100 counts as long enough: 100 x 3/4 x 0.93 = 69.75, / 1024 = 0.068
     got = ask(["need %d %d %d %d %r %r %d" % k for k, _ in needs])
     assert [int(x) for x in got] == [w for _, w in needs], [(k, w, int(g)) for (k, w), g in zip(needs, got) if int(g) != w]
+
+
+def test_accelerator_build_plan_keeps_the_rules_it_was_made_from(tmp_path):
+    """burst_amd/csrc/bhip_acx_plan.h on the host: the arithmetic that decides whether the word-sliced accelerator build fits a device -- the
+    sort's part of the range, the ranks' runs of word buckets, the size of the record range, the slice plans by target (BHIP_MASK_SLICE) and
+    by room, and the rule a plan must meet (1 .. 255 slices, none of 2 147 483 000 tuples or more).  The rows were computed on the host from
+    the rules as build_accelerator_by_words spelled them out in place before the header existed (4-byte records, 1 GiB chunks); a plan by
+    room of more than one slice is otherwise only ever run at the metric's size."""
+    exe = str(tmp_path / "acx_plan_host")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "burst_amd", "csrc"), os.path.join(ROOT, "tests", "csrc", "acx_plan_host.cpp"), "-o", exe])
+    H = "100 0 300 50 50 0 0 500 10 90 400 0 250 150 0 100"          # 16 buckets, 2000 tuples
+    GiB2 = 2 << 30
+    rows = [("buf 0", "768"), ("buf 1", "768"), ("buf 30", "768"), ("buf 1000", "18432"),
+            ("runs 1 " + H, "0 16"), ("runs 2 " + H, "0 8 16"), ("runs 3 " + H, "0 8 11 16"), ("runs 4 " + H, "0 5 8 11 16"), ("runs 5 " + H, "0 3 8 11 13 16"),
+            ("runs 3 0 0 0 7 0 0 0 0", "0 4 4 8"),                   # rank 1's run is empty
+            ("target 0 16 16384 %d 500 %s" % (GiB2, H), "0 7 8 12 16 | 500 500 500 500"),
+            ("target 0 16 2 %d 500 %s" % (GiB2, H), "0 2 4 6 8 10 12 14 16 | 100 350 50 500 100 400 400 100"),
+            ("target 2 10 16384 %d 600 %s" % (GiB2, H), "2 7 10 | 400 600"),
+            ("target 0 16 16384 20000 500 " + H, "0 7 8 12 16 | 500 500 500 500"),
+            ("target 0 16 16384 10000 500 " + H, "-"),
+            ("room 0 16 16384 %d %s" % (GiB2, H), "0 16 | 2000"),
+            ("room 0 16 16384 26096 " + H, "0 8 13 16 | 1000 750 250"),
+            ("room 0 16 16384 20000 " + H, "0 7 10 12 15 16 | 500 600 400 400 100"),
+            ("room 0 16 16384 16000 " + H, "-"),
+            # the plan the build takes: by room without BHIP_MASK_SLICE; with it, slices of max(that size, the run's biggest bucket) -- 2^12 words
+            # per bucket: at most 2^14 buckets per slice
+            ("plan 0 16 12 20000 0 " + H, "0 7 10 12 15 16 | 500 600 400 400 100"), ("plan 0 16 12 %d 1 %s" % (GiB2, H), "0 7 8 12 16 | 500 500 500 500"),
+            ("plan 2 10 12 %d 600 %s" % (GiB2, H), "2 7 10 | 400 600"), ("plan 0 16 12 10000 1 " + H, "-"),
+            ("range %d 2000 2000" % (100 << 30), "8016"), ("range 250e9 50e9 50e9", "236507214592"), ("range 220e9 50e9 50e9", "217852516352"),
+            ("range 201e9 50e9 50e9", "200000000016"), ("range 200e9 50e9 50e9", "0"), ("range 250e9 50e9 12.5e9", "200000000016"),
+            ("range 12112 2000 2000", "8016"), ("range 12111 2000 2000", "0")]
+    r = subprocess.run([exe], input="".join(q + "\n" for q, _ in rows), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    got = r.stdout.split("\n")[:-1]
+    assert len(got) == len(rows)
+    assert got == [w for _, w in rows], [(q, w, g) for (q, w), g in zip(rows, got) if g != w]
