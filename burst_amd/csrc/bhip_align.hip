@@ -988,6 +988,9 @@ static void print_chain_counters(const Handle *h, const BatchCall &b) {      // 
 			fprintf(stderr, "[bhip] lane %u class NW=%d: prefiltered %u exhaustive %u maxE %u maxwords %u | tasks %u + deferred %u (kept %u) clump pairs %u windows %u + %u | fallback queries(last class) %u raw %u\n",
 				l, kClasses[cls], L->npf[cls], L->nex[cls], L->maxE[cls], L->maxwords[cls], L->hc.n_tasks_cls[cls], L->hc.n_tasks2_cls[cls], L->hc.n_tasks2k_cls[cls], L->hc.n_cand_cls[cls], L->hc.n_wins_cls[cls], L->hc.n_wins2_cls[cls], L->hc.n_fb, L->hc.n_raw);
 		if (L->hc.n_fb) fprintf(stderr, "[bhip] lane %u: %u queries overflowed the first prefilter pass, %u the second (dense fallback)\n", l, L->hc.n_fb, L->hc.n_fb2);
+		const uint32_t *rs = L->hc.n_rs;      // hits per re-scorer variant (k_rescore_classify's buckets; exact matches leave there and are not counted)
+		fprintf(stderr, "[bhip] lane %u: re-scorer bands 4:%u 6:%u 8:%u 12:%u 16:%u 24:%u 32:%u 40:%u 48:%u lds:%u scratch:%u\n",
+			l, rs[0], rs[1], rs[2], rs[3], rs[4], rs[5], rs[6], rs[7], rs[8], rs[9], L->hc.n_wide);
 	}
 }
 // capacity checks of the lanes' buffers (first call of a workload: grow and redo)
