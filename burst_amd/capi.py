@@ -48,7 +48,7 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_comm_create", "bhip_comm_unique_id", "bhip_comm_create_rank", "bhip_comm_allreduce_min", "bhip_comm_fetch_gathered", "bhip_comm_gather_hits", "bhip_comm_stage_device", "bhip_comm_gather_staged", "bhip_comm_stage_reset", "bhip_comm_destroy", "bhip_acx_export", "bhip_reserve", "bhip_reserve_symbols", "bhip_sort_queries", "bhip_stage_spans", "bhip_alloc_host", "bhip_free_host", "bhip_host_register", "bhip_host_unregister", "bhip_set_enqueued_hook", "bhip_acx_export_entries",
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
-           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info"]
+           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run"]
 
 # BhipMateLine, 20 bytes: pair and header numbers, .b6 columns 9 and 10 (signed), column 11
 MATE_LINE_DTYPE = np.dtype([("pair", "<u4"), ("ref", "<u4"), ("st", "<i4"), ("ed", "<i4"), ("edits", "<u4")])
@@ -73,6 +73,21 @@ def cigar_text(ops):
 # BhipCovLine, 16 bytes: header, .b6 columns 9 and 10, weight (bits 0..30) | unique << 31
 COV_LINE_DTYPE = np.dtype([("ref", "<u4"), ("st", "<u4"), ("ed", "<u4"), ("w", "<u4")])
 assert COV_LINE_DTYPE.itemsize == 16
+
+
+# BhipEmLine, 8 bytes: group and header numbers of one printed line (bhip_em_run)
+EM_LINE_DTYPE = np.dtype([("group", "<u4"), ("ref", "<u4")])
+assert EM_LINE_DTYPE.itemsize == 8
+
+
+def em_lines(rows):
+    """an EM_LINE_DTYPE array as it is, rows (group, ref) as one"""
+    if isinstance(rows, np.ndarray) and rows.dtype == EM_LINE_DTYPE:
+        return np.ascontiguousarray(rows)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 2)
+    out = np.zeros(len(rows), EM_LINE_DTYPE)
+    out["group"], out["ref"] = rows[:, 0], rows[:, 1]
+    return out
 
 
 def _mate_lines(rows):
@@ -183,6 +198,8 @@ def _load():
     lib.bhip_mates_join.restype = i32
     lib.bhip_mates_info.argtypes = [vp, vp]
     lib.bhip_mates_info.restype = i32
+    lib.bhip_em_run.argtypes = [vp, u32, u32, vp, vp, u64, u32, u64, vp, vp]
+    lib.bhip_em_run.restype = i32
     for f in (lib.bhip_cov_begin, lib.bhip_cov_add, lib.bhip_cov_sample_stats, lib.bhip_cov_dataset_stats, lib.bhip_cov_info, lib.bhip_cov_end, lib.bhip_lane_extents):
         f.restype = i32
     return lib
@@ -428,6 +445,16 @@ class Device:
         info = np.zeros(4, np.uint64)
         _chk(lib().bhip_mates_info(self._h, _ptr(info)))
         return dict(zip(("us_last", "us_total", "lines", "combinations"), (int(x) for x in info)))
+
+    def em_run(self, n_headers, group_w, lines, max_iters=1000, tol=1024):
+        """abundance of one sample (bhip_em_run): group_w[g] = reads of group g, lines: EM_LINE_DTYPE array (or rows group, ref).  Returns
+        (counts uint64 [n_headers] in units of 2^-30 read, info uint64 [8]: iterations, pairs, classes, last delta, stopped on tol, device
+        microseconds, peak device bytes, 0)"""
+        group_w = np.ascontiguousarray(group_w, dtype=np.uint32)
+        lines = em_lines(lines)
+        counts, info = np.zeros(max(int(n_headers), 1), np.uint64), np.zeros(8, np.uint64)
+        _chk(lib().bhip_em_run(self._h, int(n_headers), len(group_w), _ptr(group_w), _ptr(lines), len(lines), int(max_iters), int(tol), _ptr(counts), _ptr(info)))
+        return counts[:int(n_headers)], info
 
     def cov_begin(self, lengths, pad=0):
         """coverage over len(lengths) reference headers (bhip_cov_begin); cov_add() one whole sample at a time"""

@@ -447,6 +447,9 @@ struct Handle {
 	void *cov = nullptr;          // coverage state between bhip_cov_begin and bhip_cov_end (bhip_cov.hip)
 	void *paths = nullptr;        // buffers, events and totals of bhip_trace_paths (bhip_paths.hip), made by the first call
 	void *mates = nullptr;        // buffers, events and totals of bhip_mates_join (bhip_mates.hip), made by the first call that launches
+	void *em = nullptr;           // scratch buffers and events of bhip_em_run (bhip_em.hip), made by the first call that launches
+	int opt_em_weak_hash = 0;     // 1 = candidate sets hashed to two bits: the element-by-element comparison decides which groups merge (tests)
+	int opt_em_thread_max = 0, opt_em_wave_max = 0;   // largest candidate set a thread / a wave takes in the abundance step (0 = EM_THREAD_MAX, EM_WAVE_MAX of bhip_em.hip)
 	long long opt_cov_event_cap = 0;   // bytes the coverage event sets may take before they are compacted (0 = a fifth of the memory free at the first bhip_cov_add)
 };
 
@@ -464,4 +467,5 @@ int  bhip_build_accelerator(Handle *h, int K, int z);
 void bhip_cov_release(Handle *h);                                            // bhip_cov.hip
 void bhip_paths_release(Handle *h);                                          // bhip_paths.hip
 void bhip_mates_release(Handle *h);                                          // bhip_mates.hip
+void bhip_em_release(Handle *h);                                             // bhip_em.hip
 #endif

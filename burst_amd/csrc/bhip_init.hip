@@ -73,6 +73,7 @@ extern "C" void bhip_destroy(void *handle) {
 	bhip_cov_release(h);
 	bhip_paths_release(h);
 	bhip_mates_release(h);
+	bhip_em_release(h);
 	if (h->hsc_pinned) (void)hipHostFree(h->hsc_pinned);
 	if (h->nsel_pinned) (void)hipHostFree(h->nsel_pinned);
 	for (Lane *L : h->lanes) lane_destroy(L);
@@ -245,6 +246,9 @@ extern "C" int bhip_set_option(void *handle, const char *name, long long value) 
 	if (!strcmp(name, "prefilter_bytes")) { h->opt_pf_bytes = value != 0; return BHIP_OK; }
 	if (!strcmp(name, "prefilter_rb")) { if (value != 0 && (value < 2 || value > 4)) return fail(BHIP_E_ARG, "prefilter_rb must be 0, 2, 3 or 4"); h->opt_pf_rb = (int)value; return BHIP_OK; }
 	if (!strcmp(name, "cov_event_cap")) { if (value < 0) return fail(BHIP_E_ARG, "cov_event_cap must be >= 0 bytes (0 = a fifth of the free memory)"); h->opt_cov_event_cap = value; return BHIP_OK; }
+	if (!strcmp(name, "em_weak_hash")) { h->opt_em_weak_hash = value != 0; return BHIP_OK; }
+	if (!strcmp(name, "em_thread_max")) { if (value < 0 || value > 64) return fail(BHIP_E_ARG, "em_thread_max must be 0 (built in) .. 64"); h->opt_em_thread_max = (int)value; return BHIP_OK; }
+	if (!strcmp(name, "em_wave_max")) { if (value < 0 || value > (1 << 24)) return fail(BHIP_E_ARG, "em_wave_max must be 0 (built in) .. 2^24"); h->opt_em_wave_max = (int)value; return BHIP_OK; }
 	if (!strcmp(name, "lanes")) {
 		if (value < 1 || value > BHIP_MAX_LANES) return fail(BHIP_E_ARG, "lanes must be 1 .. %d", BHIP_MAX_LANES);
 		h->opt_lanes = (int)value; for (StageSlot &S : h->slots) { S.state = 0; S.st_valid = false; } return BHIP_OK;

@@ -138,14 +138,18 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 	return bh_report_view_sink(out, db, Q, view, mode, flags, tx, nLines, NULL);
 }
 /* one placement into a chunk's sink buffer (0 = no memory) */
-static inline int pl_push(BhPlaceSink *b, uint32_t ref, uint32_t st, uint32_t ed, uint32_t w) {
+static inline int pl_push(BhPlaceSink *b, uint32_t ref, uint32_t st, uint32_t ed, uint32_t w, uint32_t uq) {
 	if (b->n == b->cap) {
 		const uint64_t nc = b->cap ? b->cap * 2 : 1024;
 		BhipCovLine *np = realloc(b->lines, nc * sizeof(*np));
-		if (!np) return 0;
-		b->lines = np; b->cap = nc;
+		if (np) b->lines = np;
+		uint32_t *nu = realloc(b->uq, nc * sizeof(*nu));
+		if (nu) b->uq = nu;
+		if (!np || !nu) return 0;
+		b->cap = nc;
 	}
 	const BhipCovLine l = {ref, st, ed, w};
+	b->uq[b->n] = uq;
 	b->lines[b->n++] = l;
 	return 1;
 }
@@ -157,15 +161,19 @@ static int pl_append(BhPlaceSink *sink, BhPlaceSink *b) {
 			uint64_t nc = sink->cap ? sink->cap * 2 : 4096;
 			while (nc < sink->n + b->n) nc *= 2;
 			BhipCovLine *np = realloc(sink->lines, nc * sizeof(*np));
-			if (np) { sink->lines = np; sink->cap = nc; } else ok = 0;
+			if (np) sink->lines = np;
+			uint32_t *nu = realloc(sink->uq, nc * sizeof(*nu));
+			if (nu) sink->uq = nu;
+			if (np && nu) sink->cap = nc; else ok = 0;
 		}
-		if (ok) { memcpy(sink->lines + sink->n, b->lines, b->n * sizeof(*b->lines)); sink->n += b->n; }
+		if (ok) { memcpy(sink->lines + sink->n, b->lines, b->n * sizeof(*b->lines)); memcpy(sink->uq + sink->n, b->uq, b->n * sizeof(*b->uq)); sink->n += b->n; }
 	}
-	free(b->lines); b->lines = NULL; b->n = b->cap = 0;
+	free(b->lines); free(b->uq); b->lines = NULL; b->uq = NULL; b->n = b->cap = 0;
 	return ok;
 }
 /* The same with an optional placement sink: for every line printed, (header of column 2, column 9, column 10, unique flag), the lines a
- * unique query's reads print for one placement folded into one entry whose weight is the number of those reads.  The chunks are
+ * unique query's reads print for one placement folded into one entry whose weight is the number of those reads; beside every entry the
+ * number of its unique query (sink->uq: the forward and the reverse-complement entry of a query are one query, one number).  The chunks are
  * rendered by a team: every chunk fills a buffer of its own and the buffers are concatenated in chunk order, as the text is.
  * sink == NULL is bh_report_view. */
 int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx,
@@ -293,7 +301,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 	if (!cbuf || !coff || (sink && !pbuf) || (paths && !lbuf)) { free(cbuf); free(coff); free(pbuf); free(lbuf); free(start); free(count); free(RefCounts); return bh_set_error(BH_E_OOM, "OOM:report"); }
 	if (sink) sink->n = 0;
 	/* header of a placement: the unique-header number of the .edx (RefMap), which direct-FASTA runs keep as well */
-	#define SINK(rix, st, ed, reads, uniq) do { if (sink && (reads) && !pl_push(&pbuf[ch], db->refMap ? db->refMap[rix] : (rix), st, ed, (uint32_t)(reads) | ((uniq) ? 0x80000000u : 0u))) out->oom = 1; } while (0)
+	#define SINK(rix, st, ed, reads, uniq) do { if (sink && (reads) && !pl_push(&pbuf[ch], db->refMap ? db->refMap[rix] : (rix), st, ed, (uint32_t)(reads) | ((uniq) ? 0x80000000u : 0u), (uint32_t)i)) out->oom = 1; } while (0)
 	/* the line just printed shows record rp against reference rix */
 	#define PLINE(rp, rix) do { if (paths && !bh_paths_push(&lbuf[ch], (uint64_t)((rp) - hits), db->refStart ? db->refStart[rix] : 0)) out->oom = 1; } while (0)
 	/* the rendered chunks of a group are written side by side at their offsets (pwrite) when the output is a seekable file: one

@@ -34,7 +34,8 @@ struct BhSession {
 	BhRun block, all;
 	SessIngest *cur, *ahead; pthread_t th; char *pending;
 	FILE *out; char *out_path;
-	char *cov_name;                 /* with a coverage: the output the loaded sample was given (names its column, also when the sample fails) */
+	char *cov_name;                 /* with a coverage or an abundance: the output the loaded sample was given (names its column, also when the sample fails) */
+	int cov_col, em_col;            /* the loaded sample has its column in the coverage / the abundance already */
 	BhPlaceSink sink;               /* the report's placements of the current sample (buffer kept across samples) */
 	BhMates *mates;                 /* bh_session_run_mates: the joiner, made on first use */
 	BhPaths *paths;                 /* with o.cigar: the tracer on the reporting rank's handle, opened by the first sample that reports */
@@ -106,6 +107,7 @@ int bh_session_open(const BhDb *db, BhMultiRank *ranks, int n_local, int n_ranks
 int bh_session_ended(const BhSession *s) { return s ? s->dead : 0; }
 void bh_session_set_node(BhSession *s, BhNode *node) { if (s) s->node = node; }
 void bh_session_set_coverage(BhSession *s, BhCov *cov) { if (s) s->o.cov = cov; }
+void bh_session_set_abundance(BhSession *s, BhEm *em) { if (s) s->o.em = em; }
 const BhQueries *bh_session_sample(const BhSession *s) { return s && s->cur ? &s->cur->Q : NULL; }
 
 int bh_session_prefetch(BhSession *s, const char *queries) {
@@ -132,7 +134,11 @@ static int sample_fail_ex(BhSession *s, BhSampleResult *res, int rc, const char 
 	if (fatal || (rc != BH_E_USAGE && rc != BH_E_IO)) s->dead = rc;
 	if (s->o.cov && s->i0 >= 0) {      /* a sample that fails alone is an all-zero column; a run that ends here writes no tables */
 		if (s->dead) bh_cov_abort(s->o.cov);
-		else if (s->cov_name) (void)bh_cov_sample_failed(s->o.cov, s->cov_name);
+		else if (s->cov_name && !s->cov_col) (void)bh_cov_sample_failed(s->o.cov, s->cov_name);
+	}
+	if (s->o.em && s->i0 >= 0) {
+		if (s->dead) bh_em_abort(s->o.em);
+		else if (s->cov_name && !s->em_col) (void)bh_em_sample_failed(s->o.em, s->cov_name);
 	}
 	free(s->cov_name); s->cov_name = NULL;
 	return bh_set_error(rc, "%s", res->err);
@@ -147,8 +153,8 @@ int bh_session_load(BhSession *s, const char *queries, const char *out_path, BhS
 	if (s->dead) { res->rc = s->dead; snprintf(res->err, sizeof res->err, "the session was ended by an earlier error (code %d)", s->dead); return bh_set_error(s->dead, "%s", res->err); }
 	if (s->cur) return bh_set_error(BH_E_USAGE, "bh_session_load: the previous sample has not been finished or dropped");
 	s->tLoad = wall();
-	free(s->cov_name); s->cov_name = NULL;
-	if (s->o.cov && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
+	free(s->cov_name); s->cov_name = NULL; s->cov_col = s->em_col = 0;
+	if ((s->o.cov || s->o.em) && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
 	SessIngest *g = NULL;
 	/* the outstanding ingest is this sample's: take it.  If it is another one's (prefetched before this sample was named) it stays
 	 * outstanding and this sample is read here */
@@ -196,6 +202,7 @@ int bh_session_drop(BhSession *s) {
 	/* a loaded sample that is given up (another rank could not have it) is a failed sample to the coverage: an all-zero column under
 	 * its name, so that the later samples keep their columns */
 	if (s->o.cov && s->cur && s->cov_name && !s->dead) (void)bh_cov_sample_failed(s->o.cov, s->cov_name);
+	if (s->o.em && s->cur && s->cov_name && !s->dead) (void)bh_em_sample_failed(s->o.em, s->cov_name);
 	drop_sample(s);
 	return BH_OK;
 }
@@ -302,7 +309,7 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		uint64_t lines = 0;
 		setvbuf(s->out, NULL, _IOFBF, 1 << 22);
 		rc = o->cigar && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
-		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov ? &s->sink : NULL, s->paths);
+		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov || o->em ? &s->sink : NULL, s->paths);
 		if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
 		FILE *f = s->out; s->out = NULL;
 		if (fclose(f)) { char msg[512]; snprintf(msg, sizeof msg, "ERROR: write failed: %s", s->out_path); return sample_fail(s, res, BH_E_IO, msg); }      /* (a full disk must not end in success) */
@@ -314,10 +321,18 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		if (o->cov) {      /* the sample's column: its placements to rank 0's device (no collective: the lines exist only here) */
 			rc = S > 1 ? bh_cov_lengths_host(o->cov) : BH_OK;      /* (database-sharded: rank 0's handle holds a slice, the default lengths come from host memory) */
 			if (!rc) rc = bh_cov_sample(o->cov, R[s->i0].hh, s->cov_name, s->sink.lines, s->sink.n);
-			free(s->cov_name); s->cov_name = NULL;      /* (the column exists: a failure below must not add another) */
+			s->cov_col = 1;      /* (the column exists: a failure below must not add another) */
 			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
 			PHASE("coverage of the sample");
 		}
+		if (o->em) {       /* the sample's abundance column, on rank 0's device as well */
+			rc = bh_em_sample(o->em, R[s->i0].hh, s->cov_name, s->sink.uq, s->sink.lines, s->sink.n);
+			s->em_col = 1;
+			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
+			if (o->verbose) bh_em_print_info(o->em);
+			PHASE("abundance of the sample");
+		}
+		free(s->cov_name); s->cov_name = NULL;
 	}
 	#undef PHASE
 	ingest_free(s->cur); s->cur = NULL;      /* the sample's tables and page-lockings; the record buffers stay */
@@ -354,6 +369,7 @@ int bh_session_run_mates(BhSession *s, const char *queries1, const char *queries
 	if (s->o.mode != BH_ALLPATHS && s->o.mode != BH_FORAGE) return mates_fail(s, res, BH_E_USAGE, "ERROR: mates are joined from ALLPATHS or FORAGE placements (the other modes discard the ties the join needs)");
 	if (!s->o.do_rc) return mates_fail(s, res, BH_E_USAGE, "ERROR: mates need both strands searched (-fr)");
 	if (s->o.cov || s->o.cigar) return mates_fail(s, res, BH_E_USAGE, "ERROR: coverage and alignment paths of paired output are out of scope: mates go with neither");
+	if (s->o.em) return mates_fail(s, res, BH_E_USAGE, "ERROR: the abundance of paired output is out of scope: mates do not go with it");
 	if (s->o.mates.orientation > BHIP_MATES_FF || s->o.mates.report > BHIP_MATES_BEST || s->o.mates.ins_min > s->o.mates.ins_max)
 		return mates_fail(s, res, BH_E_USAGE, "ERROR: mates: orientation fr|rf|ff, report all|best, insert-min <= insert-max");
 	if (s->dead) { res->rc = s->dead; snprintf(res->err, sizeof res->err, "the session was ended by an earlier error (code %d)", s->dead); return bh_set_error(s->dead, "%s", res->err); }
@@ -407,7 +423,7 @@ void bh_session_close(BhSession *s) {
 	/* the ranks' runs belong to the caller (BhMultiRank.run); slices of the session's block must not outlive it */
 	for (int i = 0; i < s->n_local; ++i) if (s->block.hits && s->ranks[i].run.hitsPinned == 2 && s->ranks[i].run.hits >= s->block.hits && s->ranks[i].run.hits < s->block.hits + s->block.capHits) memset(&s->ranks[i].run, 0, sizeof s->ranks[i].run);
 	bh_run_free(&s->block); bh_run_free(&s->all);
-	free(s->sink.lines); free(s->cov_name); bh_paths_close(s->paths); bh_mates_close(s->mates);
+	free(s->sink.lines); free(s->sink.uq); free(s->cov_name); bh_paths_close(s->paths); bh_mates_close(s->mates);
 	pthread_mutex_destroy(&s->mu);
 	free(s);
 }

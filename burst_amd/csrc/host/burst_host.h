@@ -266,8 +266,9 @@ int  bh_report_view(FILE *out, const BhDb *db, const BhQueries *q, const BhRunVi
 /* the same with a placement sink (bh_report.c): sink->lines (malloc'd, the caller's to free; may be handed in again) holds, in the order
  * of the file, one entry per (unique query, placement): header number (RefMap of the reference of column 2), columns 9 and 10, and
  * w = the number of lines the entry stands for (the reads of the unique query) | unique << 31 -- unique: each of those reads is on this one
- * line of the file only.  sink = NULL: bh_report_view. */
-typedef struct BhPlaceSink { BhipCovLine *lines; uint64_t n, cap; } BhPlaceSink;
+ * line of the file only.  sink->uq holds, entry by entry, the number of the entry's unique query: the entries of one query, those of its
+ * reverse complement included, are the placements of the same reads (the groups of bh_em.c).  sink = NULL: bh_report_view. */
+typedef struct BhPlaceSink { BhipCovLine *lines; uint64_t n, cap; uint32_t *uq; } BhPlaceSink;      /* uq[k] (malloc'd like lines): the unique query number of entry k */
 int  bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx, uint64_t *nLines, BhPlaceSink *sink);
 
 /* ---- alignment paths of the printed lines (bh_paths.c; burst_hip --cigar) ----
@@ -361,6 +362,38 @@ int  bh_cov_lengths_host(BhCov *cov);           /* no lengths table: take them f
 int  bh_cov_write_tables(const char *prefix, uint32_t n_headers, const char *const *headers, const uint32_t *lengths, uint32_t n_columns,
                          const char *const *col_names, const uint64_t *shared, const uint64_t *unique);
 
+/* ---- abundance tables: the reads of multi-mapped lines split over their references (bh_em.c; burst_hip --abundance) ----
+ * The definition is bhip_em_run's (include/burst_hip.h): per sample, group = a unique query of the report's sink (its number in sink->uq),
+ * W = the reads of that query, candidates = the distinct headers of its entries.  PREFIXabundance.txt: `#OTU ID<TAB>Dataset[<TAB>sample...]`,
+ * one row per header whose Dataset value is not zero, in strcmp order of the header, cells %.4f of count / 2^30; Dataset = the integer sum
+ * of the sample columns (a pooled EM over the study is out of scope).  Written under a temporary name and renamed.
+ *   bh_em_open           the headers are the database's unique-header numbers (RefMap), as the coverage's; bh_em_open_heads: any headers
+ *   bh_em_sample         the next sample (column): reads[k] = the unique query number of placement lines[k]; solved on `hip_handle`
+ *   bh_em_sample_failed  the next column stays all zero (a sample that failed alone); named on standard output
+ *   bh_em_abort          the run ends on an error: nothing will be written
+ *   bh_em_stats          columns x headers counts in units of 2^-30 read, column 0 = Dataset
+ *   bh_em_print_info     the `Abundance:` line of the last sample on standard output; bh_em_last_info: the same figures (bhip_em_run's info)
+ *   bh_em_set_solver     another solver (tests): bhip_em_run's arguments behind ctx, return codes in this file's terms; fn = NULL: the device
+ *   bh_em_host           the definition in plain C, a solver (its first argument is ignored): the tests without a device, the yardstick
+ * Any error of the solver is final: later calls return it and nothing is written. */
+typedef struct BhEm BhEm;
+typedef int (*bh_em_solver_fn)(void *ctx, uint32_t n_headers, uint32_t n_groups, const uint32_t *group_w, const BhipEmLine *lines, uint64_t n_lines,
+                               uint32_t max_iters, uint64_t tol, uint64_t *counts, uint64_t info[8]);
+int  bh_em_open(const BhDb *db, const char *prefix, uint32_t max_iters, uint64_t tol, BhEm **em);
+int  bh_em_open_heads(const char *prefix, uint32_t n_headers, const char *const *heads, uint32_t max_iters, uint64_t tol, BhEm **em);
+void bh_em_set_solver(BhEm *em, bh_em_solver_fn fn, void *ctx);
+int  bh_em_sample(BhEm *em, void *hip_handle, const char *out_path, const uint32_t *reads, const BhipCovLine *lines, uint64_t n);
+int  bh_em_sample_failed(BhEm *em, const char *out_path);
+void bh_em_abort(BhEm *em);
+void bh_em_dims(const BhEm *em, uint32_t *n_columns, uint32_t *n_headers);
+int  bh_em_stats(BhEm *em, uint64_t *columns);
+int  bh_em_write(BhEm *em);
+void bh_em_print_info(BhEm *em);
+void bh_em_last_info(const BhEm *em, uint64_t info[8], uint64_t *reads);
+void bh_em_close(BhEm *em);
+int  bh_em_host(void *unused, uint32_t n_headers, uint32_t n_groups, const uint32_t *group_w, const BhipEmLine *lines, uint64_t n_lines, uint32_t max_iters,
+                uint64_t tol, uint64_t *counts, uint64_t info[8]);
+
 /* ---- a session: the database stays on the devices, a list of query files runs through it (bh_session.c) ---- */
 typedef struct BhSession BhSession;
 typedef struct BhSessionOpts {            /* fixed for the whole session */
@@ -373,6 +406,7 @@ typedef struct BhSessionOpts {            /* fixed for the whole session */
 	BhCov *cov;                           /* NULL, or the coverage every reported sample feeds (rank 0's process; the caller opens it, writes the tables and closes it) */
 	int cigar;                            /* 1 = every line carries its path's position and CIGAR (bh_paths.c), traced on the handle of the rank that reports */
 	BhMatesOpts mates;                    /* bh_session_run_mates: orientation, bounds of the fragment length, report (all zero: fr, [0, 0], all -- set the bounds) */
+	BhEm *em;                             /* NULL, or the abundance every reported sample feeds (as cov: rank 0's process; the caller opens it, writes the table and closes it) */
 } BhSessionOpts;
 typedef struct BhSampleResult {
 	int rc; char err[512];
@@ -402,7 +436,7 @@ int  bh_session_drop(BhSession *s);
 int  bh_session_run(BhSession *s, const char *queries, const char *out_path, BhSampleResult *res);
 /* a pair of mate files: queries1 and then queries2 through the per-sample path above (queries2's ingest ahead, beside queries1's
  * search), each into a temporary file beside out_path; the two outputs joined (bh_mates.c, on the handle of the rank that reports) into
- * out_path, written under a temporary name and renamed.  Needs mode ALLPATHS or FORAGE, do_rc, no coverage and no cigar (BH_E_USAGE
+ * out_path, written under a temporary name and renamed.  Needs mode ALLPATHS or FORAGE, do_rc, no coverage, no abundance and no cigar (BH_E_USAGE
  * otherwise, before anything runs).  `res`: the two mates' counts and times summed, nLines = lines of the paired output.  A mate file that
  * fails fails the pair under the rule above; no output and no temporary file stays.  bh_session_mates: the session's joiner object (made
  * on first use: bh_mates_set_join, bh_mates_stats). */
@@ -411,6 +445,7 @@ BhMates *bh_session_mates(BhSession *s);
 const BhQueries *bh_session_sample(const BhSession *s);
 void bh_session_set_node(BhSession *s, BhNode *node);
 void bh_session_set_coverage(BhSession *s, BhCov *cov);      /* BhSessionOpts.cov for a session opened before its database was read */
+void bh_session_set_abundance(BhSession *s, BhEm *em);       /* BhSessionOpts.em likewise */
 int  bh_session_ended(const BhSession *s);      /* 0, or the code of the error that ended the session */
 void bh_session_close(BhSession *s);
 

@@ -7,6 +7,7 @@
  *   burst_hip -r DB.edx (-a DB.acx | -ad) -q R1.fq --mates R2.fq -o out.b6 -m ALLPATHS|FORAGE -i ... [--insert-min N] [--insert-max N]
  *             [--mates-orientation fr|rf|ff] [--mates-report all|best]      paired-end reads: the concordant combinations of the two mates' placements (bh_mates.c)
  *   ... -q / -o or --samples ... --coverage PREFIX [--coverage-lengths FILE] [--coverage-pad N]      coverage and count tables per reference and sample (bh_cov.c)
+ *   ... -q / -o or --samples ... --abundance PREFIX [--abundance-iters N] [--abundance-tol UNITS]   multi-mapped reads split over their references by EM (bh_em.c)
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
  * reference's exit code 1.  Extra flags: --device N, --batch N (unique queries per device call), -k {12|15}.
@@ -120,6 +121,7 @@ typedef struct {
 	const char *cov_prefix, *cov_lengths; uint32_t cov_pad; int cigar;
 	const char *q1_FN, *mates_FN, *out_FN;      /* --mates: the one pair of -q / --mates / -o in place of a list (list_FN = NULL) */
 	BhMatesOpts mates; int mates_opts_given;
+	const char *em_prefix; uint32_t em_iters; uint64_t em_tol;
 } SamplesArgs;
 typedef struct { char *q, *o, *m; int line; } Sample;      /* m: the mates file of a three-field line, or NULL */
 
@@ -171,6 +173,7 @@ static int samples_main(SamplesArgs *a) {
 	if (any_mates && a->mode != BH_ALLPATHS && a->mode != BH_FORAGE) { puts("ERROR: mates are joined from the placements of -m ALLPATHS or -m FORAGE (BEST, CAPITALIST and ANY discard the ties the join needs)"); return 1; }
 	if (any_mates && !a->do_rc) { puts("ERROR: a --samples line with a mates file needs both strands searched: add -fr"); return 1; }
 	if (any_mates && (a->cigar || a->cov_prefix)) { puts("ERROR: --cigar and --coverage of paired output are out of scope: neither goes with mates"); return 1; }
+	if (any_mates && a->em_prefix) { puts("ERROR: --abundance of paired output is out of scope: it does not go with mates"); return 1; }
 	const int usedb = bh_is_edx(a->ref_FN);
 	if (usedb < 0) DIE(usedb);
 	/* direct FASTA references: their clumps depend on the longest query (burst.c:5151) -- there is nothing to keep resident */
@@ -227,6 +230,11 @@ static int samples_main(SamplesArgs *a) {
 		if ((rc = bh_cov_open(&db, a->cov_prefix, a->cov_lengths, a->cov_pad, &cov))) DIES(rc);
 		bh_session_set_coverage(ses, cov);
 	}
+	BhEm *em = NULL;
+	if (a->em_prefix) {
+		if ((rc = bh_em_open(&db, a->em_prefix, a->em_iters, a->em_tol, &em))) DIES(rc);
+		bh_session_set_abundance(ses, em);
+	}
 	if (shard_db && (uint32_t)n_shards > db.numRclumps) { bh_session_close(ses); puts("ERROR: more database shards than clumps"); return 1; }
 	{ const int e = open_devices(&db, n_gpus, dev_list, shard_db, n_shards, a->accel_dev, K, a->z, hhs, ranks, slices); if (e) { bh_session_close(ses); return e; } }
 	for (int r = 0; r < n_gpus; ++r) ranks[r].hh = hhs[r];
@@ -252,13 +260,18 @@ static int samples_main(SamplesArgs *a) {
 		if ((rc = bh_cov_write(cov))) { fprintf(stderr, "%s\n", bh_last_error()); if (!first_fail) first_fail = code_to_exit(rc); }
 		else { printf("Coverage tables written: %sshared.txt, %sunique.txt, %sshared_binary.txt, %sunique_binary.txt, %scounts.txt\n", a->cov_prefix, a->cov_prefix, a->cov_prefix, a->cov_prefix, a->cov_prefix); PHASE("coverage tables"); bh_cov_print_info(cov); }
 	} else if (cov) puts("No coverage tables are written: the run ended on an error");
+	if (em && !bh_session_ended(ses)) {
+		tp = wall();
+		if ((rc = bh_em_write(em))) { fprintf(stderr, "%s\n", bh_last_error()); if (!first_fail) first_fail = code_to_exit(rc); }
+		else { printf("Abundance table written: %sabundance.txt\n", a->em_prefix); PHASE("abundance table"); }
+	} else if (em) puts("No abundance table is written: the run ended on an error");
 	printf("\nSamples: %d done, %d failed. Alignment time: %f seconds\n", n_done, n_failed, wall() - start);
 	fflush(NULL);
 	#undef PHASE
 	#undef DIES
 	if (!getenv("BURST_HOST_TEARDOWN")) _exit(first_fail);      /* (as the single-sample path: the operating system releases a finished process's memory faster) */
 	bh_session_close(ses);
-	bh_cov_close(cov);
+	bh_cov_close(cov); bh_em_close(em);
 	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); bh_run_free(&ranks[r].run); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
 	bh_db_free(&db); bh_tax_free(&taxonomy);
 	for (int i = 0; i < nS; ++i) { free(S[i].q); free(S[i].o); free(S[i].m); }
@@ -296,6 +309,10 @@ static void usage(void) {
 	puts("--coverage <prefix> [--coverage-lengths <file>] [--coverage-pad <int>]: with -q / -o or --samples, leave coverage and count tables per");
 	puts("                  reference and sample next to the .b6 files: <prefix>shared.txt, unique.txt, shared_binary.txt, unique_binary.txt,");
 	puts("                  counts.txt; lengths from a 'name<TAB>length' table, else the database's own extent of every reference");
+	puts("--abundance <prefix> [--abundance-iters <int>] [--abundance-tol <units>]: with -q / -o or --samples, leave <prefix>abundance.txt: per reference and");
+	puts("                  sample the reads, a read placed on several references split over them by expectation-maximisation (every -m mode; ALLPATHS");
+	puts("                  gives it the ties); at most --abundance-iters iterations (1000), until no count moves by more than --abundance-tol (1024)");
+	puts("                  units of 2^-30 read");
 	puts("--host-acx: build accelerators (-d ... -a, --make-acx) with the host builder instead of the device");
 }
 
@@ -311,6 +328,7 @@ int main(int argc, char **argv) {
 	uint64_t batch = 1u << 21;      /* unique queries per device batch: the fixed cost of a batch (launches, synchronisation) is about 1 ms of device time */
 	const char *ref_FN = 0, *query_FN = 0, *output_FN = 0, *xcel_FN = 0, *mkacx_FN = 0, *tax_FN = 0, *samples_FN = 0, *cov_prefix = 0, *cov_lengths = 0;
 	uint32_t cov_pad = 0;
+	const char *em_prefix = 0; uint32_t em_iters = 1000; uint64_t em_tol = 1024; int em_opts_given = 0;
 	const char *mates_FN = 0; BhMatesOpts mopts = {BHIP_MATES_FR, 0, 1000, BHIP_MATES_ALL}; int mates_opts_given = 0;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
 	BhTaxOpts txo; memset(&txo, 0, sizeof txo); txo.taxacut = 10;   /* burst.c:92 */
@@ -363,6 +381,15 @@ int main(int argc, char **argv) {
 		else if (!strcmp(a, "--samples")) { NEEDARG("--samples"); samples_FN = argv[i]; }
 		else if (!strcmp(a, "--make-acx")) { NEEDARG("--make-acx"); mkacx_FN = argv[i]; }
 		else if (!strcmp(a, "--coverage")) { NEEDARG("--coverage"); cov_prefix = argv[i]; }
+		else if (!strcmp(a, "--abundance")) { NEEDARG("--abundance"); em_prefix = argv[i]; }
+		else if (!strcmp(a, "--abundance-iters") || !strcmp(a, "--abundance-tol")) {
+			const int is_tol = !strcmp(a, "--abundance-tol");
+			NEEDARG(a);
+			char *end = NULL; const unsigned long long v = strtoull(argv[i], &end, 10);
+			if (!*argv[i] || *argv[i] == '-' || *end || (!is_tol && (!v || v > 0xFFFFFFFFull))) { printf("ERROR: %s takes %s\n", a, is_tol ? "a count of units of 2^-30 read (0 ..)" : "a number of iterations (1 .. 4294967295)"); return 1; }
+			if (is_tol) em_tol = v; else em_iters = (uint32_t)v;
+			em_opts_given = 1;
+		}
 		else if (!strcmp(a, "--cigar")) cigar = 1;
 		else if (!strcmp(a, "--mates")) { NEEDARG("--mates"); mates_FN = argv[i]; }
 		else if (!strcmp(a, "--insert-min") || !strcmp(a, "--insert-max")) {
@@ -449,6 +476,10 @@ int main(int argc, char **argv) {
 	if (n_dev_list && n_dev_list != n_gpus) { puts("ERROR: --devices must name one device per --gpus rank"); return 1; }
 	if ((cov_lengths || cov_pad) && !cov_prefix) { puts("ERROR: --coverage-lengths and --coverage-pad go with --coverage <prefix>"); return 1; }
 	if (cov_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --coverage works from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (em_opts_given && !em_prefix) { puts("ERROR: --abundance-iters and --abundance-tol go with --abundance <prefix>"); return 1; }
+	if (em_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --abundance works from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (em_prefix && shard_db && n_gpus == 1 && n_shards > 1) { puts("ERROR: --abundance needs a resident device handle: it does not go with the serial-shards path (--gpus 1 --shards S)"); return 1; }
+	if (em_prefix && mates_FN) { puts("ERROR: --abundance of paired output is out of scope: it does not go with --mates"); return 1; }
 	/* (refused before a device is touched: the paths are traced on ONE handle that holds the whole database in the nucleotide alphabet) */
 	if (cigar && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --cigar adds the alignment paths to the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
 	if (cigar && (shard_db || n_shards)) { puts("ERROR: --cigar traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
@@ -476,7 +507,7 @@ int main(int argc, char **argv) {
 		if (accel_dev && xcel_FN) { puts("ERROR: -ad builds the accelerator on the device; drop -a"); return 1; }
 		SamplesArgs sa = {ref_FN, xcel_FN, tax_FN, samples_FN, mode, thres, z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device,
 		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo, cov_prefix, cov_lengths, cov_pad, cigar,
-		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given};
+		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given, em_prefix, em_iters, em_tol};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
@@ -608,6 +639,8 @@ int main(int argc, char **argv) {
 	if (cov_prefix && shard_db && n_gpus == 1 && n_shards > 1) { JOIN_INGEST(); puts("ERROR: --coverage needs a resident device handle: it does not go with the serial-shards path (--gpus 1 --shards S)"); return 1; }
 	BhCov *cov = NULL;
 	if (cov_prefix && (rc = bh_cov_open(&db, cov_prefix, cov_lengths, cov_pad, &cov))) DIEJ(rc);      /* (before a device is touched) */
+	BhEm *em = NULL;
+	if (em_prefix && (rc = bh_em_open(&db, em_prefix, em_iters, em_tol, &em))) DIEJ(rc);
 	if (shard_db && n_gpus == 1 && n_shards > 1 && !use_rccl) {
 		/* more shards than devices: the shards take turns on the one device (bh_search_serial_shards) -- a database larger than the
 		 * device's memory, at the price of one upload per shard */
@@ -735,7 +768,7 @@ int main(int argc, char **argv) {
 	BhPlaceSink sink; memset(&sink, 0, sizeof sink);
 	BhPaths *paths = NULL;
 	if (cigar && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
-	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov ? &sink : NULL, paths))) DIE(rc);
+	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em ? &sink : NULL, paths))) DIE(rc);
 	if (fclose(output)) { fprintf(stderr, "ERROR: write failed: %s\n", output_FN); return 2; }      /* (the last buffer of the report: a full disk must not end in exit code 0) */
 	printf("Wrote %lu alignments\n", (unsigned long)lines);
 	if (paths) bh_paths_print_info(paths, hhs[0]);
@@ -746,13 +779,19 @@ int main(int argc, char **argv) {
 		PHASE("coverage");
 		bh_cov_print_info(cov);
 	}
+	if (em) {       /* likewise: one sample, so Dataset = its column */
+		if ((rc = bh_em_sample(em, hhs[0], output_FN, sink.uq, sink.lines, sink.n)) || (rc = bh_em_write(em))) DIE(rc);
+		bh_em_print_info(em);
+		printf("Abundance table written: %sabundance.txt\n", em_prefix);
+		PHASE("abundance");
+	}
 	printf("\nAlignment time: %f seconds\n", wall() - start);
 	fflush(NULL);
 	/* The job is done and its output is on disk.  Unpinning and unmapping tens of gigabytes one table after the other took about a
 	 * second for a 32 M-read job; the operating system releases a finished process's memory (host and device) far faster.
 	 * BURST_HOST_TEARDOWN=1 walks through the orderly release instead (leak checks). */
 	if (!getenv("BURST_HOST_TEARDOWN")) _exit(0);
-	bh_cov_close(cov); free(sink.lines); bh_paths_close(paths);
+	bh_cov_close(cov); bh_em_close(em); free(sink.lines); free(sink.uq); bh_paths_close(paths);
 	if (comm) bhip_comm_destroy(comm);
 	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
 	for (int r = 0; r < n_gpus; ++r) bh_run_free(&ranks[r].run);

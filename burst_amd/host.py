@@ -87,7 +87,8 @@ class BhSessionOpts(C.Structure):
     _fields_ = [("mode", C.c_int), ("thres", C.c_float), ("do_rc", C.c_int), ("incl_ws", C.c_int), ("z", C.c_int), ("do_accel", C.c_int), ("K", C.c_int),
                 ("skip_ambig", C.c_int), ("rep_flags", C.c_int), ("batch", C.c_uint64), ("shard_db", C.c_int), ("tax", C.POINTER(BhTaxOpts)),
                 ("ingest_ahead", C.c_int), ("verbose", C.c_int), ("cov", C.c_void_p), ("cigar", C.c_int),
-                ("mates_orientation", C.c_uint32), ("mates_ins_min", C.c_uint32), ("mates_ins_max", C.c_uint32), ("mates_report", C.c_uint32)]
+                ("mates_orientation", C.c_uint32), ("mates_ins_min", C.c_uint32), ("mates_ins_max", C.c_uint32), ("mates_report", C.c_uint32),
+                ("em", C.c_void_p)]
 
 
 class BhMatesStats(C.Structure):
@@ -101,6 +102,8 @@ E_CAPACITY = -6
 
 
 COV_TAP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64)
+# a solver in place of bhip_em_run (bh_em_set_solver): ctx, n_headers, n_groups, group_w, lines, n_lines, max_iters, tol, counts, info
+EM_SOLVER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p)
 
 
 class BhSampleResult(C.Structure):
@@ -223,8 +226,37 @@ def lib():
         L.bh_cov_extents_host.argtypes = [C.POINTER(BhDb), C.c_void_p]
         L.bh_cov_extents_host.restype = None
         L.bh_cov_write_tables.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p]
+        L.bh_em_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.bh_em_open_heads.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.bh_em_set_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_em_set_solver.restype = None
+        L.bh_em_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.bh_em_sample_failed.argtypes = [C.c_void_p, C.c_char_p]
+        L.bh_em_abort.argtypes = [C.c_void_p]
+        L.bh_em_abort.restype = None
+        L.bh_em_dims.argtypes = [C.c_void_p, u32p, u32p]
+        L.bh_em_dims.restype = None
+        L.bh_em_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_em_write.argtypes = [C.c_void_p]
+        L.bh_em_print_info.argtypes = [C.c_void_p]
+        L.bh_em_print_info.restype = None
+        L.bh_em_last_info.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.bh_em_last_info.restype = None
+        L.bh_em_close.argtypes = [C.c_void_p]
+        L.bh_em_close.restype = None
+        L.bh_em_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
+
+
+def em_host(n_headers, group_w, lines, max_iters=1000, tol=1024):
+    """bh_em_host, the abundance definition in plain C (no device): (counts uint64 [n_headers], info uint64 [8]); lines: capi.EM_LINE_DTYPE
+    or rows (group, ref)"""
+    group_w = np.ascontiguousarray(group_w, dtype=np.uint32)
+    lines = capi.em_lines(lines)
+    counts, info = np.zeros(max(int(n_headers), 1), np.uint64), np.zeros(8, np.uint64)
+    _chk(lib().bh_em_host(None, int(n_headers), len(group_w), group_w.ctypes.data, lines.ctypes.data, len(lines), int(max_iters), int(tol), counts.ctypes.data, info.ctypes.data))
+    return counts[:int(n_headers)], info
 
 
 def _chk(rc):
@@ -566,17 +598,22 @@ class Session:
                  taxonomy=None, taxacut=10, tax_ncbi=False, tax_suppress=False, tax_strict=False, rep_flags=0, ingest_ahead=True,
                  align=None, reduce_min=None, rank=0, world=None, c0=0, node=None, comm=None, verbose=False,
                  coverage=None, coverage_lengths=None, coverage_pad=0, coverage_tap=None, cigar=False,
-                 mates_orientation="fr", insert_min=0, insert_max=1000, mates_report="all", mates_join=None):
+                 mates_orientation="fr", insert_min=0, insert_max=1000, mates_report="all", mates_join=None,
+                 abundance=None, abundance_iters=1000, abundance_tol=1024, abundance_host=False):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
         reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
         process only).
         coverage = prefix: every reported sample feeds the coverage (bh_cov.c) on rank 0's device handle; close() writes the five tables
         prefix{shared,unique,shared_binary,unique_binary,counts}.txt unless the session ended on an error; coverage() returns the integer
         statistics.  coverage_lengths: a `name<TAB>length` table (default: the database's own extents); coverage_tap(sample, lines):
-        called with every sample's placements (capi.COV_LINE_DTYPE) before they go to the device, a true return keeps them from it."""
+        called with every sample's placements (capi.COV_LINE_DTYPE) before they go to the device, a true return keeps them from it.
+        abundance = prefix: every reported sample gets a column of the abundance table (bh_em.c: a read placed on several references split
+        over them by expectation-maximisation, at most abundance_iters iterations, until no count moves by more than abundance_tol units of
+        2^-30 read), solved on rank 0's device handle -- or by bh_em_host with abundance_host=True (sessions without a device); close()
+        writes prefix + "abundance.txt" unless the session ended on an error; abundance() returns the integer columns.  Not with mates."""
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
         self._mates_join = mates_join
-        self.cov = C.c_void_p()
+        self.cov, self.em = C.c_void_p(), C.c_void_p()
         devs = list(devs) if isinstance(devs, (list, tuple)) else [devs]
         n_local = len(devs)
         world = world or n_local
@@ -626,6 +663,11 @@ class Session:
                 self._cb.append(COV_TAP_FN(_tap))
                 lib().bh_cov_set_tap(self.cov, self._cb[-1], None)
             o.cov = self.cov
+        if abundance is not None and (rank == 0 or len(devs) > 1):
+            _chk(lib().bh_em_open(C.byref(db.c), abundance.encode(), int(abundance_iters), int(abundance_tol), C.byref(self.em)))
+            if abundance_host:
+                lib().bh_em_set_solver(self.em, C.cast(lib().bh_em_host, C.c_void_p), None)
+            o.em = self.em
         _chk(lib().bh_session_open(C.byref(db.c), self.ranks, n_local, world, comm, node.h if node is not None else None, C.byref(o), C.byref(self.h)))
 
     def _align_cb(self, align):
@@ -740,6 +782,24 @@ class Session:
         _chk(lib().bh_cov_stats(self.cov, sh.ctypes.data, un.ctypes.data))
         return sh, un
 
+    def abundance(self):
+        """the abundance columns so far: uint64 [columns][headers] in units of 2^-30 read; column 0 = Dataset, the sum of the sample columns"""
+        if not self.em:
+            raise HostError("the session has no abundance")
+        nc, nh = C.c_uint32(), C.c_uint32()
+        lib().bh_em_dims(self.em, C.byref(nc), C.byref(nh))
+        cols = np.zeros((nc.value, nh.value), np.uint64)
+        _chk(lib().bh_em_stats(self.em, cols.ctypes.data))
+        return cols
+
+    def abundance_info(self):
+        """the last solved sample's figures: iterations, pairs, classes, delta, converged, device_us, peak_bytes, reads"""
+        info, reads = np.zeros(8, np.uint64), C.c_uint64()
+        lib().bh_em_last_info(self.em, info.ctypes.data, C.byref(reads))
+        d = dict(zip(("iterations", "pairs", "classes", "delta", "converged", "device_us", "peak_bytes"), (int(x) for x in info)))
+        d["reads"] = reads.value
+        return d
+
     def coverage_abort(self):
         """the walk ends on an error that the session itself has not seen (another rank's): close() writes no tables"""
         if self.cov:
@@ -760,6 +820,11 @@ class Session:
                     err = lib().bh_last_error().decode("utf-8", "replace")
                 lib().bh_cov_close(self.cov)
                 self.cov = C.c_void_p()
+            if self.em:
+                if not lib().bh_session_ended(self.h) and not self.cov_aborted and lib().bh_em_write(self.em):
+                    err = lib().bh_last_error().decode("utf-8", "replace")
+                lib().bh_em_close(self.em)
+                self.em = C.c_void_p()
             lib().bh_session_close(self.h)
             self.h = C.c_void_p()
             for i in range(len(self.ranks)):
@@ -767,7 +832,7 @@ class Session:
             if self.tax.n or self.tax.blob:
                 lib().bh_tax_free(C.byref(self.tax))
             if err:
-                raise HostError("coverage tables not written: " + err)
+                raise HostError("tables not written: " + err)
 
     def __enter__(self):
         return self

@@ -384,6 +384,28 @@ BHIP_API int bhip_mates_join(void *handle, const BhipMateLine *a, uint64_t na, c
                              uint32_t *out_a, uint32_t *out_b, uint64_t cap, uint64_t *n_out);
 BHIP_API int bhip_mates_info(void *handle, uint64_t info[4]);
 
+/* Abundance: the reads of multi-mapped lines split over their references by expectation-maximisation (burst_hip --abundance; no reference
+ * counterpart: its README leaves "EM interpolation" of ALLPATHS output to the user and its COMMUNIST mode is a stub).  The input is what a
+ * sample prints: groups g (a group = the reads that print exactly these lines) of weight group_w[g] reads, and lines (group, ref).  The
+ * candidate set S_g is the set of DISTINCT ref among the lines of g; a group without a line or of weight 0 takes no part.  With
+ * ONE = 2^30, c0[h] = ONE for every header, and per iteration t >= 1, starting from ct[h] = 0, every participating group adds, with
+ * d = the integer sum of c(t-1) over S_g and q_h = (uint64) floor(((double)c(t-1)[h] / (double)d) * 1073741824.0) (one IEEE division):
+ * W_g q_h to ct[h] for each h of S_g, and W_g (ONE - sum of the q_h) to the candidate with the largest c(t-1), the lowest header among equals.
+ * delta_t = the largest |ct[h] - c(t-1)[h]| over all headers; the loop ends after the first t with delta_t <= tol or after max_iters.
+ * Everything but the division is 64-bit integer addition, which commutes: the result is bit-exact whatever the order.
+ *   counts  [n_headers], units of 2^-30 read; their sum is ONE x the reads of the participating groups
+ *   info    [0] iterations run, [1] distinct (group, ref) pairs of participating groups, [2] classes (groups of equal candidate set are
+ *           merged into one class of summed weight: equal to the number of distinct sets, larger only under option "em_weak_hash"),
+ *           [3] the last delta, [4] 1 if the loop ended on tol, [5] device microseconds (HIP events around everything launched), [6] peak
+ *           device bytes, [7] 0
+ * No participating group: all counts 0, 0 iterations, nothing is launched.  BHIP_E_ARG with a text, the handle staying usable, for a
+ * ref >= n_headers, a group >= n_groups, summed weights beyond 2^31 - 1, n_lines >= 2^31 and max_iters = 0.  The call leaves nothing
+ * resident but scratch buffers of the handle, which bhip_destroy frees.  Option "em_weak_hash": 1 = the candidate sets are hashed to two
+ * bits, so that the element-by-element comparison decides which groups merge (tests); no count changes.  Device side: csrc/bhip_em.hip. */
+typedef struct BhipEmLine { uint32_t group, ref; } BhipEmLine;
+BHIP_API int bhip_em_run(void *handle, uint32_t n_headers, uint32_t n_groups, const uint32_t *group_w, const BhipEmLine *lines, uint64_t n_lines,
+                         uint32_t max_iters, uint64_t tol, uint64_t *counts /* [n_headers], units of 2^-30 read */, uint64_t info[8]);
+
 /* Tuning knobs.  "prefilter_stride": 0 (default) = automatic sparse seeds -- per query the largest stride s <= K for
  * which an alignment within budget still keeps >= 3 of the words starting at 0, s, 2s, ... (one edit destroys at most
  * ceil(K/s) of them), fewest .acx look-ups with the same no-false-negative guarantee; s >= 1 forces every s-th word,
