@@ -215,11 +215,13 @@ static uint32_t blocks_per_cu(const void *fn, uint32_t threads, size_t dyn_lds, 
 	hipFuncAttributes fa_here, &fa = fa_out ? *fa_out : fa_here;
 	memset(&fa, 0, sizeof fa);
 	if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return 4;
-	const uint32_t waves_per_block = (threads + 63) / 64;
-	const uint32_t by_reg = 4u * std::min(8u, 512u / (uint32_t)std::max(8, (fa.numRegs + 7) & ~7)) / waves_per_block;
-	const size_t lds = fa.sharedSizeBytes + dyn_lds;
-	const uint32_t by_lds = lds ? (uint32_t)((148u * 1024u) / std::max<size_t>(512, (lds + 511) & ~(size_t)511)) : 64u;
-	return std::max(1u, std::min(by_reg, by_lds));
+	return bhip_resident_blocks(threads, {fa.numRegs, fa.sharedSizeBytes}, dyn_lds);      // (the arithmetic: bhip_fetch_plan.h)
+}
+// registers and static LDS of a kernel, asked once per kernel (bhip_fetch_plan.h plans with them at every launch); {0, 0}: the runtime does not say
+template <auto FN> static BhipKernelRes kernel_res() {      // (one instance, and one cached answer, per kernel)
+	static const BhipKernelRes res = [] { hipFuncAttributes fa; memset(&fa, 0, sizeof fa);
+		return hipFuncGetAttributes(&fa, (const void *)FN) == hipSuccess ? BhipKernelRes{fa.numRegs, fa.sharedSizeBytes} : BhipKernelRes{0, 0}; }();
+	return res;
 }
 
 static void launch_window(Handle *h, Lane *L, hipStream_t wst, int cls, int NWP, uint32_t grid_cap, const BhipWin *wins, const uint32_t *n_wins, Counters *dc) {
@@ -755,10 +757,18 @@ static int enqueue_rescore(Handle *h, Lane *L, const BatchCall &b) {
 	if (h->opt_rescore_reg) {
 		for_each_int(SetList{}, [&](auto set) {
 			constexpr int SET = decltype(set)::value;
-			const uint32_t grid = (uint32_t)h->n_cu * std::min<uint32_t>(32u, blocks_per_cu((const void *)k_rescore_reg<SET>, 64, 0)) * (uint32_t)h->opt_oversub;
-			hipLaunchKernelGGL(k_rescore_reg<SET>, dim3(grid), dim3(64), 0, po, L->raw.as<BhipRawHit>(), L->rs_lists.as<uint32_t>(), dc->n_rs, (uint32_t)L->raw_cap,
-				h->cur->qoff.as<uint64_t>(), rc_or_null(h), h->cur->qpack.as<uint32_t>(), qw_g,
-				R.bytes(), R.off, R.len, h->lut.as<uint8_t>(), h->out.as<BhipHit>(), &sc->n_out, (uint32_t)h->out_cap, &sc->err);
+			// where a hit's packed query comes from (option "fetch_once"): copied once into LDS where the set's registers and the rows' qw_g
+			// dwords leave every resident wave in place, else 16 bytes per 32 rows, else a dword per 8 rows
+			const BhipKernelRes res[BHIP_QF_COUNT] = {kernel_res<k_rescore_reg<SET, BHIP_QF_DWORD>>(), kernel_res<k_rescore_reg<SET, BHIP_QF_LDS>>(), kernel_res<k_rescore_reg<SET, BHIP_QF_CHUNK>>()};
+			const BhipQueryFetch qf = bhip_plan_query_fetch(qw_g, h->opt_fetch_once && res[0].regs && res[1].regs && res[2].regs, res);
+			L->qfetch[SET] = qf;
+			const uint32_t grid = (uint32_t)h->n_cu * std::min<uint32_t>(32u, qf.blocks) * (uint32_t)h->opt_oversub;
+			auto launch = [&](auto form) {
+				hipLaunchKernelGGL((k_rescore_reg<SET, decltype(form)::value>), dim3(grid), dim3(64), qf.lds_bytes, po, L->raw.as<BhipRawHit>(), L->rs_lists.as<uint32_t>(), dc->n_rs, (uint32_t)L->raw_cap,
+					h->cur->qoff.as<uint64_t>(), rc_or_null(h), h->cur->qpack.as<uint32_t>(), qw_g,
+					R.bytes(), R.off, R.len, h->lut.as<uint8_t>(), h->out.as<BhipHit>(), &sc->n_out, (uint32_t)h->out_cap, &sc->err);
+			};
+			dispatch_int(IntList<BHIP_QF_DWORD, BHIP_QF_LDS, BHIP_QF_CHUNK>{}, qf.form, launch);
 		});
 		HIPCHK(hipGetLastError());
 	}
@@ -991,6 +1001,13 @@ static void print_chain_counters(const Handle *h, const BatchCall &b) {      // 
 		const uint32_t *rs = L->hc.n_rs;      // hits per re-scorer variant (k_rescore_classify's buckets; exact matches leave there and are not counted)
 		fprintf(stderr, "[bhip] lane %u: re-scorer bands 4:%u 6:%u 8:%u 12:%u 16:%u 24:%u 32:%u 40:%u 48:%u lds:%u scratch:%u\n",
 			l, rs[0], rs[1], rs[2], rs[3], rs[4], rs[5], rs[6], rs[7], rs[8], rs[9], L->hc.n_wide);
+		// where the packed queries came from (option "fetch_once", bhip_fetch_plan.h): form / bytes of dynamic LDS per block
+		if (h->opt_rescore_reg) {
+			static const char *const qf_name[BHIP_QF_COUNT] = {"dword", "lds", "chunk"};
+			const BhipQueryFetch *f = L->qfetch;      // (by register set: 0 = 4 .. 8 diagonals, 3 = 12, 1 = 16 / 24, 2 = 32 .. 48)
+			fprintf(stderr, "[bhip] lane %u: re-scorer query fetch 4-8:%s/%u 12:%s/%u 16-24:%s/%u 32-48:%s/%u\n", l, qf_name[f[0].form], f[0].lds_bytes,
+				qf_name[f[3].form], f[3].lds_bytes, qf_name[f[1].form], f[1].lds_bytes, qf_name[f[2].form], f[2].lds_bytes);
+		}
 	}
 }
 // capacity checks of the lanes' buffers (first call of a workload: grow and redo)

@@ -21,6 +21,7 @@
 #include <thread>
 #include "burst_hip.h"
 #include "bhip_internal.h"
+#include "bhip_fetch_plan.h"
 
 // ---- kernels (bhip_kernels.hip) -------------------------------------------------------------------
 __global__ void k_acx_offsets(const uint32_t *, uint64_t, int, uint32_t *, unsigned long long *);
@@ -77,7 +78,7 @@ __global__ void k_route(const uint64_t *, const uint32_t *, uint32_t, const uint
 	uint32_t *, uint8_t *, uint32_t *, BhipStageInfo *, BhipAlt);
 __global__ void k_rescore_classify(const BhipRawHit *, const uint32_t *, uint32_t, const uint32_t *, int, const uint64_t *, const uint32_t *, const uint8_t *,
 	const uint32_t *, BhipHit *, uint32_t *, uint32_t, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t, int);
-template <int SET> __global__ void k_rescore_reg(const BhipRawHit *, const uint32_t *, const uint32_t *, uint32_t, const uint64_t *, const uint8_t *, const uint32_t *, uint32_t,
+template <int SET, int FORM> __global__ void k_rescore_reg(const BhipRawHit *, const uint32_t *, const uint32_t *, uint32_t, const uint64_t *, const uint8_t *, const uint32_t *, uint32_t,
 	const uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *, BhipHit *, uint32_t *, uint32_t, uint32_t *);
 // error text of the calling thread (bhip_last_error); defined in bhip_init.hip
 int bhip_fail_msg(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -350,6 +351,7 @@ struct Lane {
 	Counters hc;
 	uint32_t launches = 0, prefix_words = 0;
 	uint64_t n_pairs_ex = 0;
+	BhipQueryFetch qfetch[4] = {};        // what bhip_fetch_plan.h chose for this batch's re-scorer launches, per register set (BHIP_DEBUG prints it)
 	bool masked = false;
 };
 
@@ -429,6 +431,7 @@ struct Handle {
 	int opt_prune = 1;            // second sweep for lanes whose seed count bounds their edit distance above the first sweep's best
 	int opt_lane_min = 32768;     // fewest entries a sub-pipeline is worth opening for
 	int opt_rescore_reg = 1;      // register-band re-scorer for narrow bands (0 = LDS band only)
+	int opt_fetch_once = 1;       // the register-band re-scorer fetches a hit's packed query once, into LDS, where bhip_fetch_plan.h says it costs no resident wave (0 = a dword per 8 rows)
 	int opt_pf_waves = 0;         // single-wave blocks per CU of the lane-resolved prefilter (0 = as many as the LDS allows, <= 12)
 	int opt_pf_algo = -1;         // 0 = counting filter + exact lane table (k_prefilter_cf), 1 = exact clump hash table in two passes
 	                              // (k_prefilter_mask), -1 = start with 0 and switch a lane to 1 when more than 20 % of its records survive the filter

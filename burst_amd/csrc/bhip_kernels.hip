@@ -20,6 +20,7 @@
 #include <type_traits>
 #include "burst_hip.h"
 #include "bhip_internal.h"
+#include "bhip_fetch_plan.h"
 
 // ------------------------------------------------------------------------------------------------
 // DB upload: byte transpose of the .edx clump area
@@ -1325,9 +1326,14 @@ __global__ __launch_bounds__(256) void k_rescore_classify(
 	}
 }
 
-template <int WB>
+// FORM (bhip_fetch_plan.h, option "fetch_once"): where the packed query comes from.  BHIP_QF_DWORD: one dword of its row every 8 rows.
+// BHIP_QF_LDS: the ceil(m / 8) dwords of the row are copied once, as aligned 16-byte chunks issued four at a time, into the thread's
+// column of s_q ([dword][thread], qw dwords); the row loop reads them from there.  BHIP_QF_CHUNK: one aligned 16-byte chunk every 32
+// rows, the next one loaded a chunk ahead.  A row starts at any dword of a chunk (qw need not be a multiple of four) and the chunk of
+// its last dword may reach into the next row, behind the last row into the slack the array is reserved with: those dwords are not used.
+template <int WB, int FORM>
 __device__ __forceinline__ void rescore_reg_one(
-		const BhipRawHit *__restrict__ hp, bool live, uint32_t *s_mm, uint32_t fastq, uint32_t lane,
+		const BhipRawHit *__restrict__ hp, bool live, uint32_t *s_mm, uint32_t *s_q, uint32_t fastq, uint32_t lane,
 		const uint64_t *__restrict__ qoff, const uint8_t *__restrict__ qrc, const uint32_t *__restrict__ qpack, uint32_t qw,
 		const uint32_t *__restrict__ refw, const uint64_t *__restrict__ ref_off, const uint32_t *__restrict__ clump_len,
 		BhipHit *__restrict__ out, uint32_t *__restrict__ n_out, uint32_t out_cap, uint32_t *__restrict__ err_flags) {
@@ -1364,11 +1370,45 @@ __device__ __forceinline__ void rescore_reg_one(
 		int jn = j8 + NW;                                      // dword index of the next refill
 		uint4 ahead = ref_chunk_at(refw, rbase, jn >> 2, nchunks);
 		const uint32_t *qp = qpack + (uint64_t)q * qw;
-		uint32_t qd = qp[0], q_next = qw > 1 ? qp[1] : 0u;
+		const uint32_t q_off = (uint32_t)((uint64_t)q * qw) & 3u;                     // dword of its first chunk the row starts at
+		const uint4 *qc4 = (const uint4 *)qpack + (((uint64_t)q * qw) >> 2);
+		uint32_t nd = (m + 7) >> 3;                                                    // dwords of the row that hold symbols
+		nd = nd < 1 ? 1u : (nd > qw ? qw : nd);
+		const uint32_t q_chunks = (q_off + nd + 3) >> 2;
+		uint32_t qd, q_next = 0, q_ci = 0;
+		uint4 q_cur = make_uint4(0, 0, 0, 0), q_nx = make_uint4(0, 0, 0, 0);
+		if constexpr (FORM == BHIP_QF_LDS) {
+			uint32_t *sq = s_q + lane;
+			for (uint32_t c0 = 0; c0 < q_chunks; c0 += 4) {
+				uint4 v[4];
+				#pragma unroll
+				for (uint32_t c = 0; c < 4; ++c) v[c] = c0 + c < q_chunks ? qc4[c0 + c] : make_uint4(0, 0, 0, 0);
+				#pragma unroll
+				for (uint32_t c = 0; c < 4; ++c) {
+					const uint32_t i = 4 * (c0 + c) - q_off;      // dword of the row in v[c].x (wraps below 0 in the first chunk)
+					if (i < nd) sq[64 * i] = v[c].x;
+					if (i + 1 < nd) sq[64 * (i + 1)] = v[c].y;
+					if (i + 2 < nd) sq[64 * (i + 2)] = v[c].z;
+					if (i + 3 < nd) sq[64 * (i + 3)] = v[c].w;
+				}
+			}
+			qd = sq[0]; q_next = nd > 1 ? sq[64] : 0u;
+		} else if constexpr (FORM == BHIP_QF_CHUNK) {
+			q_cur = qc4[0];
+			if (q_chunks > 1) q_nx = qc4[1];
+			qd = pick4(q_cur, q_off);
+		} else { qd = qp[0]; q_next = qw > 1 ? qp[1] : 0u; }
 		uint32_t prev_sym = (ref_dword_at(refw, rbase, (p - 1) >> 3, nchunks) >> (4 * ((p - 1) & 7))) & 15u;
 		for (int y = 1; y <= (int)m; ++y) {
 			const uint32_t qi = (uint32_t)(y - 1);
-			if ((qi & 7u) == 0 && qi) { qd = q_next; q_next = (qi >> 3) + 1 < qw ? qp[(qi >> 3) + 1] : 0u; }
+			if ((qi & 7u) == 0 && qi) {
+				if constexpr (FORM == BHIP_QF_LDS) { qd = q_next; q_next = (qi >> 3) + 1 < nd ? s_q[64 * ((qi >> 3) + 1) + lane] : 0u; }
+				else if constexpr (FORM == BHIP_QF_CHUNK) {
+					const uint32_t gi = q_off + (qi >> 3);
+					if ((gi & 3u) == 0) { q_cur = q_nx; ++q_ci; if (q_ci + 1 < q_chunks) q_nx = qc4[q_ci + 1]; }
+					qd = pick4(q_cur, gi & 3u);
+				} else { qd = q_next; q_next = (qi >> 3) + 1 < qw ? qp[(qi >> 3) + 1] : 0u; }
+			}
 			const uint32_t qc = (qd >> (4 * (qi & 7u))) & 15u;
 			const uint32_t col0 = (uint32_t)y <= B ? (((uint32_t)y << SS) | Z0 | (uint32_t)y) : INVALID;   // D=y, H=0, V=y (burst.c:747-750)
 			const int x0 = y + dlo;
@@ -1482,7 +1522,7 @@ __device__ __forceinline__ void rescore_reg_one(
 	}
 }
 
-template <int SET>       // 0: bands of 4 / 6 / 8 diagonals, 3: 12, 1: 16 / 24, 2: 32 / 40 / 48 (separate kernels: the register budget of the wide ones would halve the occupancy of the narrow ones)
+template <int SET, int FORM>       // SET 0: bands of 4 / 6 / 8 diagonals, 3: 12, 1: 16 / 24, 2: 32 / 40 / 48 (separate kernels: the register budget of the wide ones would halve the occupancy of the narrow ones); FORM: rescore_reg_one
 __global__ __launch_bounds__(64) void k_rescore_reg(
 		const BhipRawHit *__restrict__ raw, const uint32_t *__restrict__ lists, const uint32_t *__restrict__ counts, uint32_t raw_cap,
 		const uint64_t *__restrict__ qoff, const uint8_t *__restrict__ qrc, const uint32_t *__restrict__ qpack, uint32_t qw,
@@ -1491,6 +1531,7 @@ __global__ __launch_bounds__(64) void k_rescore_reg(
 		BhipHit *__restrict__ out, uint32_t *__restrict__ n_out, uint32_t out_cap, uint32_t *__restrict__ err_flags) {
 	__shared__ uint32_t s_mm[16];      // match masks: bit r of s_mm[q] = (cost(q, r) == 0), bit 16 + r = (cost(q, r) != 255): a finite cost is 0 or 1
 	                                   // (nucleotide table: 255 exactly against the pad code 0; -x: the identity table, a pad costs 1 like any other symbol, burst.c:696-697)
+	extern __shared__ uint32_t s_qcol[];   // BHIP_QF_LDS: the packed queries of the block's hits, [dword][thread] (qw * 256 bytes of dynamic LDS)
 	const uint32_t tid = threadIdx.x;
 	if (tid < 16) { uint32_t mm = 0; for (int r = 0; r < 16; ++r) mm |= (lut[16 * tid + r] == 0 ? 1u : 0u) << r | (lut[16 * tid + r] != 255 ? 1u : 0u) << (16 + r); s_mm[tid] = mm; }
 	__syncthreads();
@@ -1504,7 +1545,7 @@ __global__ __launch_bounds__(64) void k_rescore_reg(
 		const uint32_t n_round = (n + 63u) & ~63u; \
 		for (uint32_t i = blockIdx.x * 64 + tid; i < n_round; i += gridDim.x * 64) { \
 			const bool live = i < n; \
-			rescore_reg_one<WB>(raw + (live ? lst[i] : 0u), live, s_mm, fastq, tid, qoff, qrc, qpack, qw, refw, ref_off, clump_len, out, n_out, out_cap, err_flags); \
+			rescore_reg_one<WB, FORM>(raw + (live ? lst[i] : 0u), live, s_mm, s_qcol, fastq, tid, qoff, qrc, qpack, qw, refw, ref_off, clump_len, out, n_out, out_cap, err_flags); \
 		} }
 	if (SET == 0) { BHIP_RS_RUN(0, 4) BHIP_RS_RUN(1, 6) BHIP_RS_RUN(2, 8) }
 	else if (SET == 3) { BHIP_RS_RUN(3, 12) }
@@ -1512,14 +1553,11 @@ __global__ __launch_bounds__(64) void k_rescore_reg(
 	else { BHIP_RS_RUN(6, 32) BHIP_RS_RUN(7, 40) BHIP_RS_RUN(8, 48) }
 #undef BHIP_RS_RUN
 }
-template __global__ void k_rescore_reg<0>(const BhipRawHit *, const uint32_t *, const uint32_t *, uint32_t, const uint64_t *, const uint8_t *, const uint32_t *, uint32_t,
-	const uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *, BhipHit *, uint32_t *, uint32_t, uint32_t *);
-template __global__ void k_rescore_reg<1>(const BhipRawHit *, const uint32_t *, const uint32_t *, uint32_t, const uint64_t *, const uint8_t *, const uint32_t *, uint32_t,
-	const uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *, BhipHit *, uint32_t *, uint32_t, uint32_t *);
-template __global__ void k_rescore_reg<2>(const BhipRawHit *, const uint32_t *, const uint32_t *, uint32_t, const uint64_t *, const uint8_t *, const uint32_t *, uint32_t,
-	const uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *, BhipHit *, uint32_t *, uint32_t, uint32_t *);
-template __global__ void k_rescore_reg<3>(const BhipRawHit *, const uint32_t *, const uint32_t *, uint32_t, const uint64_t *, const uint8_t *, const uint32_t *, uint32_t,
-	const uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *, BhipHit *, uint32_t *, uint32_t, uint32_t *);
+#define BHIP_INST_RESCORE_REG(SET, FORM) \
+	template __global__ void k_rescore_reg<SET, FORM>(const BhipRawHit *, const uint32_t *, const uint32_t *, uint32_t, const uint64_t *, const uint8_t *, const uint32_t *, uint32_t, \
+		const uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *, BhipHit *, uint32_t *, uint32_t, uint32_t *);
+#define BHIP_INST_RESCORE_SET(SET) BHIP_INST_RESCORE_REG(SET, BHIP_QF_DWORD) BHIP_INST_RESCORE_REG(SET, BHIP_QF_LDS) BHIP_INST_RESCORE_REG(SET, BHIP_QF_CHUNK)
+BHIP_INST_RESCORE_SET(0) BHIP_INST_RESCORE_SET(1) BHIP_INST_RESCORE_SET(2) BHIP_INST_RESCORE_SET(3)
 
 template __global__ void k_rescore<false>(const BhipRawHit *, const uint32_t *, uint32_t, const uint32_t *, const uint32_t *, const uint32_t *, int,
 	const uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *, const uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *,

@@ -421,6 +421,8 @@ BHIP_API int bhip_em_run(void *handle, uint32_t n_headers, uint32_t n_groups, co
  * above the query's best bound are swept only if the first sweep leaves room for them (exact: the bound is a lower bound).
  * "async_d2h": 0 (default) / 1 = asynchronous hand-over of the records, see bhip_sync_hits.
  * "rescore_reg": 1 (default) = register-band re-scorer for narrow bands, 0 = LDS band only.
+ * "fetch_once": 1 (default) = the register-band re-scorer copies a hit's packed query once into LDS, or takes it 16 bytes at a time where
+ * the length class is too long for that, each only where it costs no resident wave; 0 = a dword of the query per 8 rows.  Same records.
  * "band": 1 (default) = windows whose flagged diagonals fit two to four words of the bit-vector column are swept by the banded kernel
  * (only those words are stepped; exact), 0 = every window through the full column.  "oversub": 1..16 (default 2) = blocks launched per
  * resident block slot of the per-item kernels (prefix tasks, windows, re-scoring); "band_blocks": 0 (default, as many as fit) or the
