@@ -48,7 +48,7 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_comm_create", "bhip_comm_unique_id", "bhip_comm_create_rank", "bhip_comm_allreduce_min", "bhip_comm_fetch_gathered", "bhip_comm_gather_hits", "bhip_comm_stage_device", "bhip_comm_gather_staged", "bhip_comm_stage_reset", "bhip_comm_destroy", "bhip_acx_export", "bhip_reserve", "bhip_reserve_symbols", "bhip_sort_queries", "bhip_stage_spans", "bhip_alloc_host", "bhip_free_host", "bhip_host_register", "bhip_host_unregister", "bhip_set_enqueued_hook", "bhip_acx_export_entries",
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
-           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run"]
+           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_pile_run"]
 
 # BhipMateLine, 20 bytes: pair and header numbers, .b6 columns 9 and 10 (signed), column 11
 MATE_LINE_DTYPE = np.dtype([("pair", "<u4"), ("ref", "<u4"), ("st", "<i4"), ("ed", "<i4"), ("edits", "<u4")])
@@ -78,6 +78,31 @@ assert COV_LINE_DTYPE.itemsize == 16
 # BhipEmLine, 8 bytes: group and header numbers of one printed line (bhip_em_run)
 EM_LINE_DTYPE = np.dtype([("group", "<u4"), ("ref", "<u4")])
 assert EM_LINE_DTYPE.itemsize == 8
+
+
+# BhipPileLine, 40 bytes: a path (query entry, lane, first lane column, its ops) placed on a header at a position, for w reads (bhip_pile_run)
+PILE_LINE_DTYPE = np.dtype({"names": ["q", "refIx", "ref_first", "header", "pos", "w", "n_ops", "op_off"], "formats": ["<u4"] * 7 + ["<u8"],
+                            "offsets": [0, 4, 8, 12, 16, 20, 24, 32], "itemsize": 40})
+# BhipPileSite, 44 bytes: header, position, reference code, depth, the reads per class (A C G T Del Other), insertion marks
+PILE_SITE_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("ref", "<u4"), ("depth", "<u4"), ("n", "<u4", (6,)), ("ins", "<u4")])
+assert PILE_LINE_DTYPE.itemsize == 40 and PILE_SITE_DTYPE.itemsize == 44
+PILE_INFO = ("events", "candidates", "sites", "device_us", "peak_bytes")
+
+
+def pile_lines(rows):
+    """a PILE_LINE_DTYPE array as it is (contiguous), rows (q, refIx, ref_first, header, pos, w, n_ops, op_off) as one"""
+    if isinstance(rows, np.ndarray) and rows.dtype == PILE_LINE_DTYPE:
+        return np.ascontiguousarray(rows)
+    if isinstance(rows, np.ndarray) and rows.dtype.names == PILE_LINE_DTYPE.names:      # (the same fields without the padding: numpy packs what it concatenates)
+        out = np.zeros(len(rows), PILE_LINE_DTYPE)
+        for name in PILE_LINE_DTYPE.names:
+            out[name] = rows[name]
+        return out
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 8)
+    out = np.zeros(len(rows), PILE_LINE_DTYPE)
+    for k, name in enumerate(PILE_LINE_DTYPE.names):
+        out[name] = rows[:, k]
+    return out
 
 
 def em_lines(rows):
@@ -200,6 +225,8 @@ def _load():
     lib.bhip_mates_info.restype = i32
     lib.bhip_em_run.argtypes = [vp, u32, u32, vp, vp, u64, u32, u64, vp, vp]
     lib.bhip_em_run.restype = i32
+    lib.bhip_pile_run.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, C.POINTER(u64), vp]
+    lib.bhip_pile_run.restype = i32
     for f in (lib.bhip_cov_begin, lib.bhip_cov_add, lib.bhip_cov_sample_stats, lib.bhip_cov_dataset_stats, lib.bhip_cov_info, lib.bhip_cov_end, lib.bhip_lane_extents):
         f.restype = i32
     return lib
@@ -455,6 +482,30 @@ class Device:
         counts, info = np.zeros(max(int(n_headers), 1), np.uint64), np.zeros(8, np.uint64)
         _chk(lib().bhip_em_run(self._h, int(n_headers), len(group_w), _ptr(group_w), _ptr(lines), len(lines), int(max_iters), int(tol), _ptr(counts), _ptr(info)))
         return counts[:int(n_headers)], info
+
+    def pile_run(self, q, lines, ops, min_depth=4, min_alt=2, cap=None):
+        """variant sites of one sample (bhip_pile_run).  q: the Queries the lines' entry numbers refer to; lines: PILE_LINE_DTYPE array (or
+        rows q, refIx, ref_first, header, pos, w, n_ops, op_off); ops: the uint32 op words the lines point into.  Returns the sites
+        (PILE_SITE_DTYPE, ascending header then position); pile_info() has the call's figures.  cap: room offered at first (default: one site
+        per line); a capacity answer is retried once with the wanted room"""
+        lines = pile_lines(lines)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        cap = max(len(lines), 16) if cap is None else int(cap)
+        n, info = C.c_uint64(0), np.zeros(8, np.uint64)
+        for _ in range(2):
+            sites = np.zeros(max(cap, 1), PILE_SITE_DTYPE)
+            rc = lib().bhip_pile_run(self._h, _ptr(q.codes), _ptr(q.off), q.n, _ptr(lines), len(lines), _ptr(ops), len(ops), int(min_depth), int(min_alt),
+                                     _ptr(sites), cap, C.byref(n), _ptr(info))
+            if rc != BHIP_E_CAPACITY or n.value <= cap:
+                break
+            cap = n.value
+        self._pile_info = dict(zip(PILE_INFO, (int(x) for x in info)))
+        _chk(rc)
+        return sites[:n.value]
+
+    def pile_info(self):
+        """the last pile_run's figures: events, candidates, sites, device_us, peak_bytes"""
+        return dict(getattr(self, "_pile_info", dict.fromkeys(PILE_INFO, 0)))
 
     def cov_begin(self, lengths, pad=0):
         """coverage over len(lengths) reference headers (bhip_cov_begin); cov_add() one whole sample at a time"""

@@ -451,6 +451,7 @@ struct Handle {
 	void *paths = nullptr;        // buffers, events and totals of bhip_trace_paths (bhip_paths.hip), made by the first call
 	void *mates = nullptr;        // buffers, events and totals of bhip_mates_join (bhip_mates.hip), made by the first call that launches
 	void *em = nullptr;           // scratch buffers and events of bhip_em_run (bhip_em.hip), made by the first call that launches
+	void *pile = nullptr;         // scratch buffers and events of bhip_pile_run (bhip_pile.hip), made by the first call that launches
 	int opt_em_weak_hash = 0;     // 1 = candidate sets hashed to two bits: the element-by-element comparison decides which groups merge (tests)
 	int opt_em_thread_max = 0, opt_em_wave_max = 0;   // largest candidate set a thread / a wave takes in the abundance step (0 = EM_THREAD_MAX, EM_WAVE_MAX of bhip_em.hip)
 	long long opt_cov_event_cap = 0;   // bytes the coverage event sets may take before they are compacted (0 = a fifth of the memory free at the first bhip_cov_add)
@@ -471,4 +472,5 @@ void bhip_cov_release(Handle *h);                                            // 
 void bhip_paths_release(Handle *h);                                          // bhip_paths.hip
 void bhip_mates_release(Handle *h);                                          // bhip_mates.hip
 void bhip_em_release(Handle *h);                                             // bhip_em.hip
+void bhip_pile_release(Handle *h);                                           // bhip_pile.hip
 #endif

@@ -21,6 +21,7 @@ struct BhPaths {
 	BhipPathReq *req; uint32_t *first, *gapr; uint64_t *off; uint64_t reqCap;
 	uint32_t *ops; uint64_t opsCap;
 	char *text; size_t textCap;
+	bh_paths_collect_fn collect; void *collectCtx; int plain;      /* bh_paths_set_collector: who else gets the traced groups; plain = the lines are written without the two columns */
 };
 
 static int trace_device(void *ctx, const BhQueries *Q, const BhipPathReq *req, uint64_t n, uint32_t *ops, uint64_t ops_cap, uint64_t *op_off,
@@ -40,6 +41,7 @@ int bh_paths_open(void *hip_handle, BhPaths **out) {
 	return BH_OK;
 }
 void bh_paths_set_trace(BhPaths *p, bh_paths_trace_fn fn, void *ctx) { p->trace = fn; p->ctx = ctx; }
+void bh_paths_set_collector(BhPaths *p, bh_paths_collect_fn fn, void *ctx, int columns) { if (p) { p->collect = fn; p->collectCtx = ctx; p->plain = !columns; } }
 void bh_paths_totals(const BhPaths *p, uint64_t *requests, uint64_t *ops, uint64_t *lines) {
 	if (requests) *requests = p->nRequests;
 	if (ops) *ops = p->nOps;
@@ -59,14 +61,15 @@ void bh_paths_close(BhPaths *p) {
 	free(p);
 }
 
-int bh_paths_push(BhPathBuf *b, uint64_t hit, uint32_t ref_off) {
+int bh_paths_push(BhPathBuf *b, uint64_t hit, uint32_t ref_off) { return bh_paths_push_line(b, hit, ref_off, 0, 1); }
+int bh_paths_push_line(BhPathBuf *b, uint64_t hit, uint32_t ref_off, uint32_t header, int uniq) {
 	if (b->n == b->cap) {
 		const uint64_t nc = b->cap ? b->cap * 2 : 1024;
 		BhPathLine *np = realloc(b->l, nc * sizeof(*np));
 		if (!np) return 0;
 		b->l = np; b->cap = nc;
 	}
-	b->l[b->n].hit = hit; b->l[b->n].refOff = ref_off; ++b->n;
+	b->l[b->n].hit = hit; b->l[b->n].refOff = ref_off; b->l[b->n].header = header; b->l[b->n].uniq = uniq != 0; ++b->n;
 	return 1;
 }
 
@@ -131,6 +134,11 @@ int bh_paths_emit(BhPaths *p, FILE *out, const BhQueries *Q, const BhipHit *hits
 	}
 	if (rc) return rc;
 	p->nRequests += nr; p->nOps += p->off[nr]; p->nLines += nl; ++p->nCalls;
+	if (p->collect && (rc = p->collect(p->collectCtx, p->idx, p->req, p->first, p->off, p->ops, nr, bufs, n_chunks))) return rc;
+	if (p->plain) {      /* the lines as they were rendered */
+		for (uint64_t c = 0; c < n_chunks; ++c) if (text_len[c] && fwrite(text[c], 1, text_len[c], out) != text_len[c]) return bh_set_error(BH_E_IO, "short write on the output file");
+		return BH_OK;
+	}
 	/* every line again, its two columns behind what it had */
 	for (uint64_t c = 0; c < n_chunks; ++c) {
 		const char *s = text[c], *end = s + text_len[c];

@@ -303,7 +303,8 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 	/* header of a placement: the unique-header number of the .edx (RefMap), which direct-FASTA runs keep as well */
 	#define SINK(rix, st, ed, reads, uniq) do { if (sink && (reads) && !pl_push(&pbuf[ch], db->refMap ? db->refMap[rix] : (rix), st, ed, (uint32_t)(reads) | ((uniq) ? 0x80000000u : 0u), (uint32_t)i)) out->oom = 1; } while (0)
 	/* the line just printed shows record rp against reference rix */
-	#define PLINE(rp, rix) do { if (paths && !bh_paths_push(&lbuf[ch], (uint64_t)((rp) - hits), db->refStart ? db->refStart[rix] : 0)) out->oom = 1; } while (0)
+	#define PLINE_U(rp, rix, uniq) do { if (paths && !bh_paths_push_line(&lbuf[ch], (uint64_t)((rp) - hits), db->refStart ? db->refStart[rix] : 0, db->refMap ? db->refMap[rix] : (rix), uniq)) out->oom = 1; } while (0)
+	#define PLINE(rp, rix) PLINE_U(rp, rix, 1)      /* (one line per read: the sink's unique bit is set) */
 	/* the rendered chunks of a group are written side by side at their offsets (pwrite) when the output is a seekable file: one
 	 * thread copying gigabytes into the page cache was the other half of the report's time */
 	fflush(real_out);
@@ -439,7 +440,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) for (uint64_t zz = 0; zz < rix_ix; ++zz) {
 				const BhipHit *rp = RPcache[zz]; const uint32_t rix = RIXcache[zz];
 				uint32_t st, ed; coords(db, rp, rix, qlen, &st, &ed);
-				print_line_tax(out, Q->heads[j], db->refHead[rix], rp, qlen, st, ed, i, wt, wt ? bh_tax_lookup(T, db->refHead[rix], ncbi) : NULL); PLINE(rp, rix); ++lines;   /* burst.c:4631-4633, 4685-4687 */
+				print_line_tax(out, Q->heads[j], db->refHead[rix], rp, qlen, st, ed, i, wt, wt ? bh_tax_lookup(T, db->refHead[rix], ncbi) : NULL); PLINE_U(rp, rix, rix_ix == 1); ++lines;   /* burst.c:4631-4633, 4685-4687 */
 			}
 			if (sink) for (uint64_t zz = 0; zz < rix_ix; ++zz) {      /* a read with one placement only is on one line of the file */
 				uint32_t st, ed; coords(db, RPcache[zz], RIXcache[zz], qlen, &st, &ed);
@@ -613,6 +614,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 	if (use_pwrite && lseek(out_fd, file_pos, SEEK_SET) == (off_t)-1) wr = 1;      /* the stream continues behind what was written */
 	#undef SINK
 	#undef PLINE
+	#undef PLINE_U
 	if (lbuf) for (uint64_t ch = 0; ch < nChunks; ++ch) free(lbuf[ch].l);
 	free(cbuf); free(coff); free(pbuf); free(lbuf);
 	free(start); free(count); free(RefCounts);

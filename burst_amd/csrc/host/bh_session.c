@@ -35,10 +35,10 @@ struct BhSession {
 	SessIngest *cur, *ahead; pthread_t th; char *pending;
 	FILE *out; char *out_path;
 	char *cov_name;                 /* with a coverage or an abundance: the output the loaded sample was given (names its column, also when the sample fails) */
-	int cov_col, em_col;            /* the loaded sample has its column in the coverage / the abundance already */
+	int cov_col, em_col, pile_col;  /* the loaded sample has its column in the coverage / the abundance, its block in the variants already */
 	BhPlaceSink sink;               /* the report's placements of the current sample (buffer kept across samples) */
 	BhMates *mates;                 /* bh_session_run_mates: the joiner, made on first use */
-	BhPaths *paths;                 /* with o.cigar: the tracer on the reporting rank's handle, opened by the first sample that reports */
+	BhPaths *paths;                 /* with o.cigar or o.pile: the tracer on the reporting rank's handle, opened by the first sample that reports */
 	int dead, dbg, threads_ok;
 	int alive;                      /* query tables alive (the current sample's and the prefetched one's) */
 	pthread_mutex_t mu;             /* `alive` and its debug line */
@@ -108,6 +108,7 @@ int bh_session_ended(const BhSession *s) { return s ? s->dead : 0; }
 void bh_session_set_node(BhSession *s, BhNode *node) { if (s) s->node = node; }
 void bh_session_set_coverage(BhSession *s, BhCov *cov) { if (s) s->o.cov = cov; }
 void bh_session_set_abundance(BhSession *s, BhEm *em) { if (s) s->o.em = em; }
+void bh_session_set_variants(BhSession *s, BhPile *pile) { if (s) s->o.pile = pile; }
 const BhQueries *bh_session_sample(const BhSession *s) { return s && s->cur ? &s->cur->Q : NULL; }
 
 int bh_session_prefetch(BhSession *s, const char *queries) {
@@ -140,6 +141,10 @@ static int sample_fail_ex(BhSession *s, BhSampleResult *res, int rc, const char 
 		if (s->dead) bh_em_abort(s->o.em);
 		else if (s->cov_name && !s->em_col) (void)bh_em_sample_failed(s->o.em, s->cov_name);
 	}
+	if (s->o.pile && s->i0 >= 0) {
+		if (s->dead) bh_pile_abort(s->o.pile);
+		else if (s->cov_name && !s->pile_col) (void)bh_pile_sample_failed(s->o.pile, s->cov_name);
+	}
 	free(s->cov_name); s->cov_name = NULL;
 	return bh_set_error(rc, "%s", res->err);
 }
@@ -153,8 +158,8 @@ int bh_session_load(BhSession *s, const char *queries, const char *out_path, BhS
 	if (s->dead) { res->rc = s->dead; snprintf(res->err, sizeof res->err, "the session was ended by an earlier error (code %d)", s->dead); return bh_set_error(s->dead, "%s", res->err); }
 	if (s->cur) return bh_set_error(BH_E_USAGE, "bh_session_load: the previous sample has not been finished or dropped");
 	s->tLoad = wall();
-	free(s->cov_name); s->cov_name = NULL; s->cov_col = s->em_col = 0;
-	if ((s->o.cov || s->o.em) && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
+	free(s->cov_name); s->cov_name = NULL; s->cov_col = s->em_col = s->pile_col = 0;
+	if ((s->o.cov || s->o.em || s->o.pile) && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
 	SessIngest *g = NULL;
 	/* the outstanding ingest is this sample's: take it.  If it is another one's (prefetched before this sample was named) it stays
 	 * outstanding and this sample is read here */
@@ -203,6 +208,7 @@ int bh_session_drop(BhSession *s) {
 	 * its name, so that the later samples keep their columns */
 	if (s->o.cov && s->cur && s->cov_name && !s->dead) (void)bh_cov_sample_failed(s->o.cov, s->cov_name);
 	if (s->o.em && s->cur && s->cov_name && !s->dead) (void)bh_em_sample_failed(s->o.em, s->cov_name);
+	if (s->o.pile && s->cur && s->cov_name && !s->dead) (void)bh_pile_sample_failed(s->o.pile, s->cov_name);
 	drop_sample(s);
 	return BH_OK;
 }
@@ -308,7 +314,8 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		const double tr = wall();
 		uint64_t lines = 0;
 		setvbuf(s->out, NULL, _IOFBF, 1 << 22);
-		rc = o->cigar && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
+		rc = (o->cigar || o->pile) && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
+		if (!rc && s->paths) bh_paths_set_pile(s->paths, o->pile, o->cigar);
 		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov || o->em ? &s->sink : NULL, s->paths);
 		if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
 		FILE *f = s->out; s->out = NULL;
@@ -331,6 +338,13 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
 			if (o->verbose) bh_em_print_info(o->em);
 			PHASE("abundance of the sample");
+		}
+		if (o->pile) {     /* the sample's variant sites: one call over the lines the tracer handed over, on rank 0's device as well */
+			rc = bh_pile_sample(o->pile, R[s->i0].hh, s->cov_name, Q->codes, Q->qoff, Q->numEntries);
+			s->pile_col = 1;
+			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
+			if (o->verbose) bh_pile_print_info(o->pile);
+			PHASE("variant sites of the sample");
 		}
 		free(s->cov_name); s->cov_name = NULL;
 	}
@@ -370,6 +384,7 @@ int bh_session_run_mates(BhSession *s, const char *queries1, const char *queries
 	if (!s->o.do_rc) return mates_fail(s, res, BH_E_USAGE, "ERROR: mates need both strands searched (-fr)");
 	if (s->o.cov || s->o.cigar) return mates_fail(s, res, BH_E_USAGE, "ERROR: coverage and alignment paths of paired output are out of scope: mates go with neither");
 	if (s->o.em) return mates_fail(s, res, BH_E_USAGE, "ERROR: the abundance of paired output is out of scope: mates do not go with it");
+	if (s->o.pile) return mates_fail(s, res, BH_E_USAGE, "ERROR: variants of paired output are out of scope: mates do not go with them");
 	if (s->o.mates.orientation > BHIP_MATES_FF || s->o.mates.report > BHIP_MATES_BEST || s->o.mates.ins_min > s->o.mates.ins_max)
 		return mates_fail(s, res, BH_E_USAGE, "ERROR: mates: orientation fr|rf|ff, report all|best, insert-min <= insert-max");
 	if (s->dead) { res->rc = s->dead; snprintf(res->err, sizeof res->err, "the session was ended by an earlier error (code %d)", s->dead); return bh_set_error(s->dead, "%s", res->err); }

@@ -285,7 +285,7 @@ int  bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *q, const Bh
 typedef struct BhPaths BhPaths;
 typedef int (*bh_paths_trace_fn)(void *ctx, const BhQueries *q, const BhipPathReq *req, uint64_t n, uint32_t *ops, uint64_t ops_cap, uint64_t *op_off,
                                  uint32_t *ref_first, uint32_t *gap_r);
-typedef struct BhPathLine { uint64_t hit; uint32_t refOff; } BhPathLine;
+typedef struct BhPathLine { uint64_t hit; uint32_t refOff, header, uniq; } BhPathLine;      /* header, uniq: what the placement sink notes (bh_paths_push: 0, 1) */
 typedef struct BhPathBuf { BhPathLine *l; uint64_t n, cap; } BhPathBuf;
 int  bh_paths_open(void *hip_handle, BhPaths **paths);
 void bh_paths_set_trace(BhPaths *paths, bh_paths_trace_fn fn, void *ctx);
@@ -293,6 +293,16 @@ void bh_paths_totals(const BhPaths *paths, uint64_t *requests, uint64_t *ops, ui
 void bh_paths_print_info(BhPaths *paths, void *hip_handle);      /* one `Paths:` line on standard output: requests, ops, device milliseconds since the last one */
 void bh_paths_close(BhPaths *paths);
 int  bh_paths_push(BhPathBuf *b, uint64_t hit, uint32_t ref_off);
+/* the same with the line's header number (RefMap of its reference) and whether its read is on this one line of the file only */
+int  bh_paths_push_line(BhPathBuf *b, uint64_t hit, uint32_t ref_off, uint32_t header, int uniq);
+/* every traced group -- its distinct records idx[0 .. n_records) (ascending) with their requests, first columns and ops, and the notes of
+ * the lines printed from them -- also goes to fn (NULL: to nobody); columns = 0: the lines are written as they are rendered, without the
+ * two columns.  bh_paths_set_pile (bh_pile.c): the collector is a variants object (--variants, with or without --cigar) */
+typedef int (*bh_paths_collect_fn)(void *ctx, const uint64_t *idx, const BhipPathReq *req, const uint32_t *first, const uint64_t *off, const uint32_t *ops, uint64_t n_records,
+                                   const BhPathBuf *bufs, uint64_t n_chunks);
+void bh_paths_set_collector(BhPaths *paths, bh_paths_collect_fn fn, void *ctx, int columns);
+struct BhPile;
+void bh_paths_set_pile(BhPaths *paths, struct BhPile *pile, int columns);
 int  bh_paths_emit(BhPaths *paths, FILE *out, const BhQueries *q, const BhipHit *hits, char *const *text, const size_t *text_len, const BhPathBuf *bufs, uint64_t n_chunks);
 size_t bh_cigar_text(const uint32_t *ops, uint64_t n, char *out, size_t cap);
 int  bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx, uint64_t *nLines,
@@ -394,6 +404,46 @@ void bh_em_close(BhEm *em);
 int  bh_em_host(void *unused, uint32_t n_headers, uint32_t n_groups, const uint32_t *group_w, const BhipEmLine *lines, uint64_t n_lines, uint32_t max_iters,
                 uint64_t tol, uint64_t *counts, uint64_t info[8]);
 
+/* ---- variant sites per sample from the alignment paths (bh_pile.c; burst_hip --variants) ----
+ * The definition is bhip_pile_run's (include/burst_hip.h): per sample, every printed line is a line of the pile-up -- its record's path
+ * (the tracer of the --cigar columns, traced once), the header of column 2, the position the --cigar column prints, weight = the reads it
+ * stands for; with unique_only only the lines whose read is on exactly one line of the sample (the sink's bit 31).  PREFIXvariants.txt:
+ * `#Reference<TAB>Position<TAB>Ref<TAB>Sample<TAB>Depth<TAB>A<TAB>C<TAB>G<TAB>T<TAB>Del<TAB>Other<TAB>Ins`, then one block per sample in
+ * study order, rows in strcmp order of the header, then ascending position.  Written under a temporary name (opened by bh_pile_open,
+ * a block appended per sample) and renamed by bh_pile_write; bh_pile_close removes a temporary file that was not renamed.  No Dataset
+ * block: a pooled call over the samples is out of scope.
+ *   bh_pile_open           the headers are the database's unique-header numbers (RefMap); bh_pile_open_heads: any headers
+ *   bh_pile_collect        bh_paths_emit's hand-over of a traced group (records, paths, the notes of the printed lines)
+ *   bh_pile_sample         the end of a sample: ONE solver call over its lines, its block appended; q_codes / q_off: the sample's entries
+ *   bh_pile_sample_failed  the sample has no rows (it failed alone); named on standard output
+ *   bh_pile_abort          the run ends on an error: nothing will be written
+ *   bh_pile_rows           the rows so far (headers as unique-header numbers) and the sample of each; returns their number
+ *   bh_pile_print_info     the `Variants:` line of the last sample on standard output; bh_pile_last_info: the same figures
+ *   bh_pile_set_solver     another solver (tests): bhip_pile_run's arguments behind ctx, return codes in this file's terms
+ *                          (BH_E_CAPACITY = *n_sites wanted); fn = NULL: the device
+ *   bh_pile_host           the definition in plain C, a solver: ctx = a BhPileRefs (the packed references as bhip_init takes them); one record
+ *                          per observed base, so its cost is lines x read length -- the tests without a device, the yardstick
+ * Any error of the solver is final: later calls return it and nothing is written. */
+typedef struct BhPile BhPile;
+typedef struct BhPileRefs { const uint8_t *packed; const uint32_t *clump_len; uint32_t n_clumps, tot_refs; } BhPileRefs;
+typedef int (*bh_pile_solver_fn)(void *ctx, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
+                                 const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]);
+int  bh_pile_open(const BhDb *db, const char *prefix, uint32_t min_depth, uint32_t min_alt, int unique_only, BhPile **pile);
+int  bh_pile_open_heads(const char *prefix, uint32_t n_headers, const char *const *heads, uint32_t min_depth, uint32_t min_alt, int unique_only, BhPile **pile);
+void bh_pile_set_solver(BhPile *pile, bh_pile_solver_fn fn, void *ctx);
+int  bh_pile_collect(BhPile *pile, const uint64_t *idx, const BhipPathReq *req, const uint32_t *first, const uint64_t *off, const uint32_t *ops, uint64_t n_records,
+                     const BhPathBuf *bufs, uint64_t n_chunks);
+int  bh_pile_sample(BhPile *pile, void *hip_handle, const char *out_path, const uint8_t *q_codes, const uint64_t *q_off, uint64_t n_queries);
+int  bh_pile_sample_failed(BhPile *pile, const char *out_path);
+void bh_pile_abort(BhPile *pile);
+uint64_t bh_pile_rows(const BhPile *pile, BhipPileSite *rows, uint32_t *samples, uint64_t cap);
+int  bh_pile_write(BhPile *pile);
+void bh_pile_print_info(BhPile *pile);
+void bh_pile_last_info(const BhPile *pile, uint64_t info[8], uint64_t *lines);
+void bh_pile_close(BhPile *pile);
+int  bh_pile_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
+                  const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]);
+
 /* ---- a session: the database stays on the devices, a list of query files runs through it (bh_session.c) ---- */
 typedef struct BhSession BhSession;
 typedef struct BhSessionOpts {            /* fixed for the whole session */
@@ -407,6 +457,7 @@ typedef struct BhSessionOpts {            /* fixed for the whole session */
 	int cigar;                            /* 1 = every line carries its path's position and CIGAR (bh_paths.c), traced on the handle of the rank that reports */
 	BhMatesOpts mates;                    /* bh_session_run_mates: orientation, bounds of the fragment length, report (all zero: fr, [0, 0], all -- set the bounds) */
 	BhEm *em;                             /* NULL, or the abundance every reported sample feeds (as cov: rank 0's process; the caller opens it, writes the table and closes it) */
+	BhPile *pile;                         /* NULL, or the variant sites every reported sample feeds (as em); opens the path tracer even without cigar */
 } BhSessionOpts;
 typedef struct BhSampleResult {
 	int rc; char err[512];
@@ -446,6 +497,7 @@ const BhQueries *bh_session_sample(const BhSession *s);
 void bh_session_set_node(BhSession *s, BhNode *node);
 void bh_session_set_coverage(BhSession *s, BhCov *cov);      /* BhSessionOpts.cov for a session opened before its database was read */
 void bh_session_set_abundance(BhSession *s, BhEm *em);       /* BhSessionOpts.em likewise */
+void bh_session_set_variants(BhSession *s, BhPile *pile);    /* BhSessionOpts.pile likewise */
 int  bh_session_ended(const BhSession *s);      /* 0, or the code of the error that ended the session */
 void bh_session_close(BhSession *s);
 

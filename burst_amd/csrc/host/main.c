@@ -8,6 +8,7 @@
  *             [--mates-orientation fr|rf|ff] [--mates-report all|best]      paired-end reads: the concordant combinations of the two mates' placements (bh_mates.c)
  *   ... -q / -o or --samples ... --coverage PREFIX [--coverage-lengths FILE] [--coverage-pad N]      coverage and count tables per reference and sample (bh_cov.c)
  *   ... -q / -o or --samples ... --abundance PREFIX [--abundance-iters N] [--abundance-tol UNITS]   multi-mapped reads split over their references by EM (bh_em.c)
+ *   ... -q / -o or --samples ... --variants PREFIX [--variants-min-depth N] [--variants-min-alt N] [--variants-reads all|unique]   variant sites per sample (bh_pile.c)
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
  * reference's exit code 1.  Extra flags: --device N, --batch N (unique queries per device call), -k {12|15}.
@@ -122,6 +123,7 @@ typedef struct {
 	const char *q1_FN, *mates_FN, *out_FN;      /* --mates: the one pair of -q / --mates / -o in place of a list (list_FN = NULL) */
 	BhMatesOpts mates; int mates_opts_given;
 	const char *em_prefix; uint32_t em_iters; uint64_t em_tol;
+	const char *var_prefix; uint32_t var_min_depth, var_min_alt; int var_unique;
 } SamplesArgs;
 typedef struct { char *q, *o, *m; int line; } Sample;      /* m: the mates file of a three-field line, or NULL */
 
@@ -174,6 +176,7 @@ static int samples_main(SamplesArgs *a) {
 	if (any_mates && !a->do_rc) { puts("ERROR: a --samples line with a mates file needs both strands searched: add -fr"); return 1; }
 	if (any_mates && (a->cigar || a->cov_prefix)) { puts("ERROR: --cigar and --coverage of paired output are out of scope: neither goes with mates"); return 1; }
 	if (any_mates && a->em_prefix) { puts("ERROR: --abundance of paired output is out of scope: it does not go with mates"); return 1; }
+	if (any_mates && a->var_prefix) { puts("ERROR: --variants of paired output are out of scope: they do not go with mates"); return 1; }
 	const int usedb = bh_is_edx(a->ref_FN);
 	if (usedb < 0) DIE(usedb);
 	/* direct FASTA references: their clumps depend on the longest query (burst.c:5151) -- there is nothing to keep resident */
@@ -239,6 +242,11 @@ static int samples_main(SamplesArgs *a) {
 	{ const int e = open_devices(&db, n_gpus, dev_list, shard_db, n_shards, a->accel_dev, K, a->z, hhs, ranks, slices); if (e) { bh_session_close(ses); return e; } }
 	for (int r = 0; r < n_gpus; ++r) ranks[r].hh = hhs[r];
 	PHASE("device database upload");
+	BhPile *pile = NULL;      /* (opened last: its table grows under a temporary name from here on) */
+	if (a->var_prefix) {
+		if ((rc = bh_pile_open(&db, a->var_prefix, a->var_min_depth, a->var_min_alt, a->var_unique, &pile))) DIES(rc);
+		bh_session_set_variants(ses, pile);
+	}
 	int n_failed = 0, first_fail = 0, n_done = 0;
 	for (int i = 0; i < nS; ++i) {
 		if (S[i].m) printf("Sample %d/%d: %s + %s -> %s\n", i + 1, nS, S[i].q, S[i].m, S[i].o);
@@ -265,6 +273,11 @@ static int samples_main(SamplesArgs *a) {
 		if ((rc = bh_em_write(em))) { fprintf(stderr, "%s\n", bh_last_error()); if (!first_fail) first_fail = code_to_exit(rc); }
 		else { printf("Abundance table written: %sabundance.txt\n", a->em_prefix); PHASE("abundance table"); }
 	} else if (em) puts("No abundance table is written: the run ended on an error");
+	if (pile && !bh_session_ended(ses)) {
+		if ((rc = bh_pile_write(pile))) { fprintf(stderr, "%s\n", bh_last_error()); if (!first_fail) first_fail = code_to_exit(rc); }
+		else printf("Variants table written: %svariants.txt\n", a->var_prefix);
+	} else if (pile) puts("No variants table is written: the run ended on an error");
+	bh_pile_close(pile); pile = NULL;      /* (a table that was not written leaves no temporary file) */
 	printf("\nSamples: %d done, %d failed. Alignment time: %f seconds\n", n_done, n_failed, wall() - start);
 	fflush(NULL);
 	#undef PHASE
@@ -313,6 +326,11 @@ static void usage(void) {
 	puts("                  sample the reads, a read placed on several references split over them by expectation-maximisation (every -m mode; ALLPATHS");
 	puts("                  gives it the ties); at most --abundance-iters iterations (1000), until no count moves by more than --abundance-tol (1024)");
 	puts("                  units of 2^-30 read");
+	puts("--variants <prefix> [--variants-min-depth <int>] [--variants-min-alt <int>] [--variants-reads all|unique]: with -q / -o or --samples, leave");
+	puts("                  <prefix>variants.txt: per sample the reference positions where its reads differ from the reference, with the reads per base");
+	puts("                  (Depth, A, C, G, T, Del, Other) and the insertions behind the position (Ins), counted from the alignment paths of the");
+	puts("                  printed lines; a position is listed when its reference base is A/C/G/T, Depth >= --variants-min-depth (4) and the reads");
+	puts("                  that differ, or Ins, are >= --variants-min-alt (2); --variants-reads unique counts only reads printed on one line");
 	puts("--host-acx: build accelerators (-d ... -a, --make-acx) with the host builder instead of the device");
 }
 
@@ -329,6 +347,7 @@ int main(int argc, char **argv) {
 	const char *ref_FN = 0, *query_FN = 0, *output_FN = 0, *xcel_FN = 0, *mkacx_FN = 0, *tax_FN = 0, *samples_FN = 0, *cov_prefix = 0, *cov_lengths = 0;
 	uint32_t cov_pad = 0;
 	const char *em_prefix = 0; uint32_t em_iters = 1000; uint64_t em_tol = 1024; int em_opts_given = 0;
+	const char *var_prefix = 0; uint32_t var_min_depth = 4, var_min_alt = 2; int var_unique = 0, var_opts_given = 0;
 	const char *mates_FN = 0; BhMatesOpts mopts = {BHIP_MATES_FR, 0, 1000, BHIP_MATES_ALL}; int mates_opts_given = 0;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
 	BhTaxOpts txo; memset(&txo, 0, sizeof txo); txo.taxacut = 10;   /* burst.c:92 */
@@ -391,6 +410,19 @@ int main(int argc, char **argv) {
 			em_opts_given = 1;
 		}
 		else if (!strcmp(a, "--cigar")) cigar = 1;
+		else if (!strcmp(a, "--variants")) { NEEDARG("--variants"); var_prefix = argv[i]; }
+		else if (!strcmp(a, "--variants-min-depth") || !strcmp(a, "--variants-min-alt")) {
+			const int is_alt = !strcmp(a, "--variants-min-alt");
+			NEEDARG(a);
+			char *end = NULL; const unsigned long long v = strtoull(argv[i], &end, 10);
+			if (!*argv[i] || *end || !v || v > 0x7FFFFFFFull) { printf("ERROR: %s takes a number of reads (1 .. 2147483647)\n", a); return 1; }
+			if (is_alt) var_min_alt = (uint32_t)v; else var_min_depth = (uint32_t)v;
+			var_opts_given = 1;
+		}
+		else if (!strcmp(a, "--variants-reads")) {
+			NEEDARG("--variants-reads"); var_opts_given = 1;
+			if (!strcmp(argv[i], "all")) var_unique = 0; else if (!strcmp(argv[i], "unique")) var_unique = 1; else { puts("ERROR: --variants-reads all|unique"); return 1; }
+		}
 		else if (!strcmp(a, "--mates")) { NEEDARG("--mates"); mates_FN = argv[i]; }
 		else if (!strcmp(a, "--insert-min") || !strcmp(a, "--insert-max")) {
 			const int is_max = !strcmp(a, "--insert-max");
@@ -484,6 +516,12 @@ int main(int argc, char **argv) {
 	if (cigar && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --cigar adds the alignment paths to the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
 	if (cigar && (shard_db || n_shards)) { puts("ERROR: --cigar traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
 	if (cigar && !gather_host) { puts("ERROR: --cigar takes the host gather only (drop --gather rccl)"); return 1; }
+	/* (--variants counts from the same paths, traced on the same handle: it refuses what --cigar refuses) */
+	if (var_opts_given && !var_prefix) { puts("ERROR: --variants-min-depth, --variants-min-alt and --variants-reads go with --variants <prefix>"); return 1; }
+	if (var_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --variants counts from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (var_prefix && (shard_db || n_shards)) { puts("ERROR: --variants traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
+	if (var_prefix && !gather_host) { puts("ERROR: --variants takes the host gather only (drop --gather rccl)"); return 1; }
+	if (var_prefix && mates_FN) { puts("ERROR: --variants of paired output are out of scope: they do not go with --mates"); return 1; }
 	if (mates_opts_given && mopts.ins_min > mopts.ins_max) { puts("ERROR: --insert-min is larger than --insert-max"); return 1; }
 	if (mates_opts_given && !mates_FN && !samples_FN) { puts("ERROR: --insert-min, --insert-max, --mates-orientation and --mates-report go with --mates"); return 1; }
 	if (mates_FN) {
@@ -507,7 +545,8 @@ int main(int argc, char **argv) {
 		if (accel_dev && xcel_FN) { puts("ERROR: -ad builds the accelerator on the device; drop -a"); return 1; }
 		SamplesArgs sa = {ref_FN, xcel_FN, tax_FN, samples_FN, mode, thres, z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device,
 		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo, cov_prefix, cov_lengths, cov_pad, cigar,
-		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given, em_prefix, em_iters, em_tol};
+		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given, em_prefix, em_iters, em_tol,
+		                  var_prefix, var_min_depth, var_min_alt, var_unique};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
@@ -767,12 +806,26 @@ int main(int argc, char **argv) {
 	setvbuf(output, NULL, _IOFBF, 1 << 22);
 	BhPlaceSink sink; memset(&sink, 0, sizeof sink);
 	BhPaths *paths = NULL;
-	if (cigar && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
-	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em ? &sink : NULL, paths))) DIE(rc);
+	if ((cigar || var_prefix) && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
+	BhPile *pile = NULL;      /* a study of one sample; opened here: its temporary file exists from now until it is renamed or the object is closed */
+	#define DIEP(rc) do { bh_pile_close(pile); DIE(rc); } while (0)
+	if (var_prefix) {
+		if (!db.refMap || !db.numRefHeads) { puts("ERROR: --variants needs the reference headers of the database"); return 1; }
+		if ((rc = bh_pile_open(&db, var_prefix, var_min_depth, var_min_alt, var_unique, &pile))) DIE(rc);
+		bh_paths_set_pile(paths, pile, cigar);
+	}
+	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em ? &sink : NULL, paths))) DIEP(rc);
 	if (fclose(output)) { fprintf(stderr, "ERROR: write failed: %s\n", output_FN); return 2; }      /* (the last buffer of the report: a full disk must not end in exit code 0) */
 	printf("Wrote %lu alignments\n", (unsigned long)lines);
-	if (paths) bh_paths_print_info(paths, hhs[0]);
+	if (paths && cigar) bh_paths_print_info(paths, hhs[0]);
 	PHASE("consolidation, output");
+	if (pile) {     /* first of the tables: a failure below must not leave its temporary file */
+		if ((rc = bh_pile_sample(pile, hhs[0], output_FN, Q.codes, Q.qoff, Q.numEntries)) || (rc = bh_pile_write(pile))) DIEP(rc);
+		bh_pile_print_info(pile);
+		printf("Variants table written: %svariants.txt\n", var_prefix);
+		PHASE("variants");
+		bh_pile_close(pile); pile = NULL;
+	}
 	if (cov) {      /* a study of one sample: the Dataset column and the sample's (rank 0's handle; the lines exist only here) */
 		if ((shard_db && (rc = bh_cov_lengths_host(cov))) || (rc = bh_cov_sample(cov, hhs[0], output_FN, sink.lines, sink.n)) || (rc = bh_cov_write(cov))) DIE(rc);
 		printf("Coverage tables written: %sshared.txt, %sunique.txt, %sshared_binary.txt, %sunique_binary.txt, %scounts.txt\n", cov_prefix, cov_prefix, cov_prefix, cov_prefix, cov_prefix);

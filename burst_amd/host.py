@@ -88,7 +88,19 @@ class BhSessionOpts(C.Structure):
                 ("skip_ambig", C.c_int), ("rep_flags", C.c_int), ("batch", C.c_uint64), ("shard_db", C.c_int), ("tax", C.POINTER(BhTaxOpts)),
                 ("ingest_ahead", C.c_int), ("verbose", C.c_int), ("cov", C.c_void_p), ("cigar", C.c_int),
                 ("mates_orientation", C.c_uint32), ("mates_ins_min", C.c_uint32), ("mates_ins_max", C.c_uint32), ("mates_report", C.c_uint32),
-                ("em", C.c_void_p)]
+                ("em", C.c_void_p), ("pile", C.c_void_p)]
+
+
+class BhPileRefs(C.Structure):      # the packed references as bhip_init takes them: what bh_pile_host reads the reference codes from
+    _fields_ = [("packed", C.c_void_p), ("clump_len", C.c_void_p), ("n_clumps", C.c_uint32), ("tot_refs", C.c_uint32)]
+
+
+class BhPathBuf(C.Structure):        # the notes of a chunk's printed lines: l = BhPathLine records (PATH_LINE_DTYPE)
+    _fields_ = [("l", C.c_void_p), ("n", C.c_uint64), ("cap", C.c_uint64)]
+
+
+# BhPathLine, 24 bytes: record number, refStart of the line's reference, its header number, whether its read is on this one line only
+PATH_LINE_DTYPE = np.dtype({"names": ["hit", "refOff", "header", "uniq"], "formats": ["<u8", "<u4", "<u4", "<u4"], "offsets": [0, 8, 12, 16], "itemsize": 24})
 
 
 class BhMatesStats(C.Structure):
@@ -245,6 +257,28 @@ def lib():
         L.bh_em_close.argtypes = [C.c_void_p]
         L.bh_em_close.restype = None
         L.bh_em_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.bh_pile_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        L.bh_pile_open_heads.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        L.bh_pile_set_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_pile_set_solver.restype = None
+        L.bh_pile_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BhPathBuf), C.c_uint64]
+        L.bh_pile_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.bh_pile_sample_failed.argtypes = [C.c_void_p, C.c_char_p]
+        L.bh_pile_abort.argtypes = [C.c_void_p]
+        L.bh_pile_abort.restype = None
+        L.bh_pile_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.bh_pile_rows.restype = C.c_uint64
+        L.bh_pile_write.argtypes = [C.c_void_p]
+        L.bh_pile_print_info.argtypes = [C.c_void_p]
+        L.bh_pile_print_info.restype = None
+        L.bh_pile_last_info.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.bh_pile_last_info.restype = None
+        L.bh_pile_close.argtypes = [C.c_void_p]
+        L.bh_pile_close.restype = None
+        L.bh_pile_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                   C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+        L.bh_session_set_variants.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_session_set_variants.restype = None
         _lib = L
     return _lib
 
@@ -257,6 +291,34 @@ def em_host(n_headers, group_w, lines, max_iters=1000, tol=1024):
     counts, info = np.zeros(max(int(n_headers), 1), np.uint64), np.zeros(8, np.uint64)
     _chk(lib().bh_em_host(None, int(n_headers), len(group_w), group_w.ctypes.data, lines.ctypes.data, len(lines), int(max_iters), int(tol), counts.ctypes.data, info.ctypes.data))
     return counts[:int(n_headers)], info
+
+
+def pile_refs(packed, clump_len, tot_refs):
+    """a BhPileRefs over the packed references (dbutil.pack_clumps / bhip_init's form); the arrays must outlive it (kept as attributes)"""
+    r = BhPileRefs()
+    r._keep = (np.ascontiguousarray(packed, dtype=np.uint8), np.ascontiguousarray(clump_len, dtype=np.uint32))
+    r.packed, r.clump_len, r.n_clumps, r.tot_refs = r._keep[0].ctypes.data, r._keep[1].ctypes.data, len(r._keep[1]), int(tot_refs)
+    return r
+
+
+def pile_host(refs, q_codes, q_off, lines, ops, min_depth=4, min_alt=2, cap=None):
+    """bh_pile_host, the variant-site definition in plain C (no device; one record per observed base): (sites capi.PILE_SITE_DTYPE, info
+    uint64 [8]: events, candidate sites, sites).  refs: pile_refs(...); q_codes / q_off: the query entries; lines: capi.PILE_LINE_DTYPE"""
+    q_codes, q_off = np.ascontiguousarray(q_codes, dtype=np.uint8), np.ascontiguousarray(q_off, dtype=np.uint64)
+    lines, ops = capi.pile_lines(lines), np.ascontiguousarray(ops, dtype=np.uint32)
+    cap = max(len(lines), 16) if cap is None else int(cap)
+    n, info = C.c_uint64(0), np.zeros(8, np.uint64)
+    for _ in range(2):
+        sites = np.zeros(max(cap, 1), capi.PILE_SITE_DTYPE)
+        rc = lib().bh_pile_host(C.byref(refs), q_codes.ctypes.data, q_off.ctypes.data, len(q_off) - 1, lines.ctypes.data, len(lines), ops.ctypes.data, len(ops),
+                                int(min_depth), int(min_alt), sites.ctypes.data, cap, C.byref(n), info.ctypes.data)
+        if rc != E_CAPACITY or n.value <= cap:
+            break
+        cap = n.value
+    if rc == E_CAPACITY:
+        raise HostError("bh_pile_host: %d sites, room for %d" % (n.value, cap))
+    _chk(rc)
+    return sites[:n.value], info
 
 
 def _chk(rc):
@@ -599,7 +661,8 @@ class Session:
                  align=None, reduce_min=None, rank=0, world=None, c0=0, node=None, comm=None, verbose=False,
                  coverage=None, coverage_lengths=None, coverage_pad=0, coverage_tap=None, cigar=False,
                  mates_orientation="fr", insert_min=0, insert_max=1000, mates_report="all", mates_join=None,
-                 abundance=None, abundance_iters=1000, abundance_tol=1024, abundance_host=False):
+                 abundance=None, abundance_iters=1000, abundance_tol=1024, abundance_host=False,
+                 variants=None, variants_min_depth=4, variants_min_alt=2, variants_reads="all", variants_host=False):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
         reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
         process only).
@@ -610,10 +673,15 @@ class Session:
         abundance = prefix: every reported sample gets a column of the abundance table (bh_em.c: a read placed on several references split
         over them by expectation-maximisation, at most abundance_iters iterations, until no count moves by more than abundance_tol units of
         2^-30 read), solved on rank 0's device handle -- or by bh_em_host with abundance_host=True (sessions without a device); close()
-        writes prefix + "abundance.txt" unless the session ended on an error; abundance() returns the integer columns.  Not with mates."""
+        writes prefix + "abundance.txt" unless the session ended on an error; abundance() returns the integer columns.  Not with mates.
+        variants = prefix: every reported sample gets a block of prefix + "variants.txt" (bh_pile.c: the reference positions where the sample's
+        reads differ from the reference, counted from the alignment paths of the printed lines; listed from variants_min_depth reads on the
+        position and variants_min_alt that differ; variants_reads "unique" counts only reads printed on one line), counted on rank 0's device
+        handle -- or by bh_pile_host with variants_host=True; variants() returns the rows so far, close() writes the table unless the
+        session ended on an error.  Opens the path tracer without adding the cigar columns; same limits as cigar.  Not with mates."""
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
         self._mates_join = mates_join
-        self.cov, self.em = C.c_void_p(), C.c_void_p()
+        self.cov, self.em, self.pile = C.c_void_p(), C.c_void_p(), C.c_void_p()
         devs = list(devs) if isinstance(devs, (list, tuple)) else [devs]
         n_local = len(devs)
         world = world or n_local
@@ -668,6 +736,18 @@ class Session:
             if abundance_host:
                 lib().bh_em_set_solver(self.em, C.cast(lib().bh_em_host, C.c_void_p), None)
             o.em = self.em
+        if variants is not None:
+            if variants_reads not in ("all", "unique") or not 1 <= int(variants_min_depth) < 1 << 31 or not 1 <= int(variants_min_alt) < 1 << 31:
+                raise ValueError("variants: reads all|unique, 1 <= min_depth, min_alt < 2^31")
+            if shard_db and int(shard_db) > 1:
+                raise ValueError("variants: the paths are traced on one handle, which must hold the whole database (no shard_db)")
+            if align is not None or world != n_local:
+                raise ValueError("variants: needs the device handles of one process (no align back end, no job of processes)")
+            _chk(lib().bh_pile_open(C.byref(db.c), variants.encode(), int(variants_min_depth), int(variants_min_alt), int(variants_reads == "unique"), C.byref(self.pile)))
+            if variants_host:
+                self._pile_refs = BhPileRefs(C.cast(db.c.packed, C.c_void_p), C.cast(db.c.clumpLen, C.c_void_p), db.c.numRclumps, db.c.totR)
+                lib().bh_pile_set_solver(self.pile, C.cast(lib().bh_pile_host, C.c_void_p), C.cast(C.pointer(self._pile_refs), C.c_void_p))
+            o.pile = self.pile
         _chk(lib().bh_session_open(C.byref(db.c), self.ranks, n_local, world, comm, node.h if node is not None else None, C.byref(o), C.byref(self.h)))
 
     def _align_cb(self, align):
@@ -800,6 +880,24 @@ class Session:
         d["reads"] = reads.value
         return d
 
+    def variants(self):
+        """the rows of the variants table so far: (sites capi.PILE_SITE_DTYPE with header = the database's unique-header number, sample uint32
+        per row), in the table's order"""
+        if not self.pile:
+            raise HostError("the session has no variants")
+        n = lib().bh_pile_rows(self.pile, None, None, 0)
+        rows, samples = np.zeros(max(n, 1), capi.PILE_SITE_DTYPE), np.zeros(max(n, 1), np.uint32)
+        lib().bh_pile_rows(self.pile, rows.ctypes.data, samples.ctypes.data, n)
+        return rows[:n], samples[:n]
+
+    def variants_info(self):
+        """the last counted sample's figures: events, candidates, sites, device_us, peak_bytes, lines"""
+        info, lines = np.zeros(8, np.uint64), C.c_uint64()
+        lib().bh_pile_last_info(self.pile, info.ctypes.data, C.byref(lines))
+        d = dict(zip(capi.PILE_INFO, (int(x) for x in info)))
+        d["lines"] = lines.value
+        return d
+
     def coverage_abort(self):
         """the walk ends on an error that the session itself has not seen (another rank's): close() writes no tables"""
         if self.cov:
@@ -825,6 +923,11 @@ class Session:
                     err = lib().bh_last_error().decode("utf-8", "replace")
                 lib().bh_em_close(self.em)
                 self.em = C.c_void_p()
+            if self.pile:
+                if not lib().bh_session_ended(self.h) and not self.cov_aborted and lib().bh_pile_write(self.pile):
+                    err = lib().bh_last_error().decode("utf-8", "replace")
+                lib().bh_pile_close(self.pile)
+                self.pile = C.c_void_p()
             lib().bh_session_close(self.h)
             self.h = C.c_void_p()
             for i in range(len(self.ranks)):

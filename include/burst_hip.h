@@ -406,6 +406,41 @@ typedef struct BhipEmLine { uint32_t group, ref; } BhipEmLine;
 BHIP_API int bhip_em_run(void *handle, uint32_t n_headers, uint32_t n_groups, const uint32_t *group_w, const BhipEmLine *lines, uint64_t n_lines,
                          uint32_t max_iters, uint64_t tol, uint64_t *counts /* [n_headers], units of 2^-30 read */, uint64_t info[8]);
 
+/* Variant sites: which bases one sample's reads show at a reference position, and where they differ from the reference (burst_hip
+ * --variants; no reference counterpart).  The result is a function of the sample's printed lines.  A LINE is a path as bhip_trace_paths
+ * returns it -- query entry q of q_codes / q_off, lane refIx, first lane column ref_first, ops[op_off .. op_off + n_ops) -- placed on the
+ * reference the caller numbers `header`, at 1-based position `pos` (the position of lane column ref_first), standing for `w` reads.
+ * Symbol codes .ACGTNKMRYSWBVHD = 0..15: codes 1..4 are the classes A, C, G, T, every other code is the class Other, Del is a class of its
+ * own.  Walk the ops forwards with reference position p = pos and query index j = 0:
+ *   '=' or X, per symbol   one OBSERVATION (header, p, class of query[j]); p++, j++
+ *   D, per column          one observation (header, p, Del); p++
+ *   I run of n             j += n, and one INSERTION MARK (header, p - 1) unless the run is the first or the last op of the path (a run at
+ *                          an end is what a local aligner would clip)
+ * A SITE is (header, position); observations and marks count w per line.  A, C, G, T, Del, Other = its observations per class, Depth = their
+ * sum, Ins = its marks (not part of Depth), Ref = the code of the lane column the observing paths consumed there.  The lanes of a database
+ * that share a position of a header are cuts of one original sequence and agree there; the smallest code is taken, so that no order matters
+ * (the device takes it among the observations that are not plain, see below, and counts the plain ones as Ref: for lanes that agree the two
+ * are the same).  A site is RETURNED when Ref is 1..4, Depth >= min_depth, and Depth - count[Ref] >= min_alt or Ins >= min_alt; sites come
+ * back in ascending (header, pos) order, n[] = A, C, G, T, Del, Other.  No pooling over samples, no indel alleles, no genotypes.
+ * The cost follows the lines and their edits, never lines x read length: an observation is PLAIN when its op is '=' and its query code is
+ * 1..4; only the others and the marks become events, which are sorted and reduced to candidate sites; the depth of a candidate is the
+ * weight of the lines whose range [pos, pos + ('=' + X + D) - 1] holds it, from two sorted arrays (starts, one-past-ends) with running
+ * weight sums and two binary searches, and the plain observations are depth minus the others (csrc/bhip_pile.hip).
+ * All sums are 64-bit integers: bit-exact whatever the order of threads or lines.
+ * BHIP_E_CAPACITY when cap is too small: *n_sites is the number wanted, nothing is written, the handle stays usable.  n_lines == 0: no
+ * sites, nothing is launched.  BHIP_E_ARG with a text, before any device memory is touched and with the handle staying usable, for a line
+ * whose query is >= n_queries, whose lane is >= 16 n_clumps or >= tot_refs, whose ops leave `ops`, hold a word that is not a run of I / D /
+ * '=' / X of length >= 1 or repeat the code of the op before (runs are merged), consume ('=' + X + I) another number of symbols than the
+ * query has, or leave the columns 1 .. ClumpLen; for pos == 0 or pos + ('=' + X + D) > 2^32 - 1, w == 0, summed weights beyond 2^31 - 1,
+ * and min_depth == 0 or min_alt == 0.
+ * info (may be NULL): [0] events, [1] candidate sites, [2] sites returned, [3] device microseconds (HIP events around everything launched),
+ * [4] peak device bytes of the call's scratch buffers (the handle keeps them; bhip_destroy frees them), [5..7] 0. */
+typedef struct BhipPileLine { uint32_t q, refIx, ref_first, header, pos, w; uint32_t n_ops; uint64_t op_off; } BhipPileLine;
+typedef struct BhipPileSite { uint32_t header, pos, ref, depth, n[6] /* A C G T Del Other */, ins; } BhipPileSite;
+BHIP_API int bhip_pile_run(void *handle, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries,
+                           const BhipPileLine *lines, uint64_t n_lines, const uint32_t *ops, uint64_t n_ops,
+                           uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]);
+
 /* Tuning knobs.  "prefilter_stride": 0 (default) = automatic sparse seeds -- per query the largest stride s <= K for
  * which an alignment within budget still keeps >= 3 of the words starting at 0, s, 2s, ... (one edit destroys at most
  * ceil(K/s) of them), fewest .acx look-ups with the same no-false-negative guarantee; s >= 1 forces every s-th word,
