@@ -48,7 +48,8 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_comm_create", "bhip_comm_unique_id", "bhip_comm_create_rank", "bhip_comm_allreduce_min", "bhip_comm_fetch_gathered", "bhip_comm_gather_hits", "bhip_comm_stage_device", "bhip_comm_gather_staged", "bhip_comm_stage_reset", "bhip_comm_destroy", "bhip_acx_export", "bhip_reserve", "bhip_reserve_symbols", "bhip_sort_queries", "bhip_stage_spans", "bhip_alloc_host", "bhip_free_host", "bhip_host_register", "bhip_host_unregister", "bhip_set_enqueued_hook", "bhip_acx_export_entries",
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
-           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_pile_run"]
+           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_pile_run",
+           "bhip_cluster_run", "bhip_cluster_info"]
 
 # BhipMateLine, 20 bytes: pair and header numbers, .b6 columns 9 and 10 (signed), column 11
 MATE_LINE_DTYPE = np.dtype([("pair", "<u4"), ("ref", "<u4"), ("st", "<i4"), ("ed", "<i4"), ("edits", "<u4")])
@@ -87,6 +88,21 @@ PILE_LINE_DTYPE = np.dtype({"names": ["q", "refIx", "ref_first", "header", "pos"
 PILE_SITE_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("ref", "<u4"), ("depth", "<u4"), ("n", "<u4", (6,)), ("ins", "<u4")])
 assert PILE_LINE_DTYPE.itemsize == 40 and PILE_SITE_DTYPE.itemsize == 44
 PILE_INFO = ("events", "candidates", "sites", "device_us", "peak_bytes")
+
+# BhipClusterEdge, 12 bytes: read q has a printed line against read r with this many edits (bhip_cluster_run)
+CLUSTER_EDGE_DTYPE = np.dtype([("q", "<u4"), ("r", "<u4"), ("edits", "<u4")])
+assert CLUSTER_EDGE_DTYPE.itemsize == 12
+CLUSTER_INFO = ("rounds", "edges_kept", "centroids", "device_us", "device_bytes", "edges", "nodes")
+
+
+def cluster_edges(rows):
+    """a CLUSTER_EDGE_DTYPE array as it is (contiguous), rows (q, r, edits) as one"""
+    if isinstance(rows, np.ndarray) and rows.dtype == CLUSTER_EDGE_DTYPE:
+        return np.ascontiguousarray(rows)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+    out = np.zeros(len(rows), CLUSTER_EDGE_DTYPE)
+    out["q"], out["r"], out["edits"] = rows[:, 0], rows[:, 1], rows[:, 2]
+    return out
 
 
 def pile_lines(rows):
@@ -227,6 +243,10 @@ def _load():
     lib.bhip_em_run.restype = i32
     lib.bhip_pile_run.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, C.POINTER(u64), vp]
     lib.bhip_pile_run.restype = i32
+    lib.bhip_cluster_run.argtypes = [vp, u32, vp, vp, u64, vp, vp]
+    lib.bhip_cluster_run.restype = i32
+    lib.bhip_cluster_info.argtypes = [vp, vp]
+    lib.bhip_cluster_info.restype = i32
     for f in (lib.bhip_cov_begin, lib.bhip_cov_add, lib.bhip_cov_sample_stats, lib.bhip_cov_dataset_stats, lib.bhip_cov_info, lib.bhip_cov_end, lib.bhip_lane_extents):
         f.restype = i32
     return lib
@@ -502,6 +522,23 @@ class Device:
         self._pile_info = dict(zip(PILE_INFO, (int(x) for x in info)))
         _chk(rc)
         return sites[:n.value]
+
+    def cluster_run(self, weights, edges):
+        """greedy centroid clusters (bhip_cluster_run).  weights: uint32 per node (read), edges: CLUSTER_EDGE_DTYPE array (or rows q, r, edits), raw
+        -- duplicates, self edges and edges towards lower priority included.  Returns (centroid uint32 [n], edits uint32 [n]): every node's
+        centroid (itself for a centroid) and the edits of the edge that joined it; cluster_info() has the call's figures"""
+        weights = np.ascontiguousarray(weights, dtype=np.uint32)
+        edges = cluster_edges(edges)
+        n = len(weights)
+        centroid, edits = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        _chk(lib().bhip_cluster_run(self._h, n, _ptr(weights), _ptr(edges), len(edges), _ptr(centroid), _ptr(edits)))
+        return centroid[:n], edits[:n]
+
+    def cluster_info(self):
+        """the last cluster_run's figures: rounds, edges_kept, centroids, device_us, device_bytes, edges, nodes"""
+        info = np.zeros(8, np.uint64)
+        _chk(lib().bhip_cluster_info(self._h, _ptr(info)))
+        return dict(zip(CLUSTER_INFO, (int(x) for x in info)))
 
     def pile_info(self):
         """the last pile_run's figures: events, candidates, sites, device_us, peak_bytes"""

@@ -138,18 +138,21 @@ int bh_report_view(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunVie
 	return bh_report_view_sink(out, db, Q, view, mode, flags, tx, nLines, NULL);
 }
 /* one placement into a chunk's sink buffer (0 = no memory) */
-static inline int pl_push(BhPlaceSink *b, uint32_t ref, uint32_t st, uint32_t ed, uint32_t w, uint32_t uq) {
+static inline int pl_push(BhPlaceSink *b, uint32_t ref, uint32_t st, uint32_t ed, uint32_t w, uint32_t uq, uint64_t re) {
 	if (b->n == b->cap) {
 		const uint64_t nc = b->cap ? b->cap * 2 : 1024;
 		BhipCovLine *np = realloc(b->lines, nc * sizeof(*np));
 		if (np) b->lines = np;
 		uint32_t *nu = realloc(b->uq, nc * sizeof(*nu));
 		if (nu) b->uq = nu;
-		if (!np || !nu) return 0;
+		uint64_t *nr = b->want_re ? realloc(b->re, nc * sizeof(*nr)) : NULL;
+		if (nr) b->re = nr;
+		if (!np || !nu || (b->want_re && !nr)) return 0;
 		b->cap = nc;
 	}
 	const BhipCovLine l = {ref, st, ed, w};
 	b->uq[b->n] = uq;
+	if (b->want_re) b->re[b->n] = re;
 	b->lines[b->n++] = l;
 	return 1;
 }
@@ -164,16 +167,23 @@ static int pl_append(BhPlaceSink *sink, BhPlaceSink *b) {
 			if (np) sink->lines = np;
 			uint32_t *nu = realloc(sink->uq, nc * sizeof(*nu));
 			if (nu) sink->uq = nu;
-			if (np && nu) sink->cap = nc; else ok = 0;
+			uint64_t *nr = sink->want_re ? realloc(sink->re, nc * sizeof(*nr)) : NULL;
+			if (nr) sink->re = nr;
+			if (np && nu && (nr || !sink->want_re)) sink->cap = nc; else ok = 0;
 		}
-		if (ok) { memcpy(sink->lines + sink->n, b->lines, b->n * sizeof(*b->lines)); memcpy(sink->uq + sink->n, b->uq, b->n * sizeof(*b->uq)); sink->n += b->n; }
+		if (ok) {
+			memcpy(sink->lines + sink->n, b->lines, b->n * sizeof(*b->lines)); memcpy(sink->uq + sink->n, b->uq, b->n * sizeof(*b->uq));
+			if (sink->want_re) memcpy(sink->re + sink->n, b->re, b->n * sizeof(*b->re));
+			sink->n += b->n;
+		}
 	}
-	free(b->lines); free(b->uq); b->lines = NULL; b->uq = NULL; b->n = b->cap = 0;
+	free(b->lines); free(b->uq); free(b->re); b->lines = NULL; b->uq = NULL; b->re = NULL; b->n = b->cap = 0;
 	return ok;
 }
 /* The same with an optional placement sink: for every line printed, (header of column 2, column 9, column 10, unique flag), the lines a
  * unique query's reads print for one placement folded into one entry whose weight is the number of those reads; beside every entry the
- * number of its unique query (sink->uq: the forward and the reverse-complement entry of a query are one query, one number).  The chunks are
+ * number of its unique query (sink->uq: the forward and the reverse-complement entry of a query are one query, one number), and with
+ * sink->want_re the reference the entry's line names and column 11 (sink->re, for bh_cluster.c).  The chunks are
  * rendered by a team: every chunk fills a buffer of its own and the buffers are concatenated in chunk order, as the text is.
  * sink == NULL is bh_report_view. */
 int bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *Q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx,
@@ -301,7 +311,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 	if (!cbuf || !coff || (sink && !pbuf) || (paths && !lbuf)) { free(cbuf); free(coff); free(pbuf); free(lbuf); free(start); free(count); free(RefCounts); return bh_set_error(BH_E_OOM, "OOM:report"); }
 	if (sink) sink->n = 0;
 	/* header of a placement: the unique-header number of the .edx (RefMap), which direct-FASTA runs keep as well */
-	#define SINK(rix, st, ed, reads, uniq) do { if (sink && (reads) && !pl_push(&pbuf[ch], db->refMap ? db->refMap[rix] : (rix), st, ed, (uint32_t)(reads) | ((uniq) ? 0x80000000u : 0u), (uint32_t)i)) out->oom = 1; } while (0)
+	#define SINK(rp, rix, st, ed, reads, uniq) do { if (sink && (reads)) { pbuf[ch].want_re = sink->want_re; if (!pl_push(&pbuf[ch], db->refMap ? db->refMap[rix] : (rix), st, ed, (uint32_t)(reads) | ((uniq) ? 0x80000000u : 0u), (uint32_t)i, (uint64_t)(rix) << 32 | (unsigned)(rp)->ed)) out->oom = 1; } } while (0)
 	/* the line just printed shows record rp against reference rix */
 	#define PLINE_U(rp, rix, uniq) do { if (paths && !bh_paths_push_line(&lbuf[ch], (uint64_t)((rp) - hits), db->refStart ? db->refStart[rix] : 0, db->refMap ? db->refMap[rix] : (rix), uniq)) out->oom = 1; } while (0)
 	#define PLINE(rp, rix) PLINE_U(rp, rix, 1)      /* (one line per read: the sink's unique bit is set) */
@@ -379,7 +389,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 				const uint64_t i = bi[k]; const uint32_t qlen = Q->len[i];
 				uint32_t st, ed; coords(db, bb[k], brix[k], qlen, &st, &ed);
 				for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[brix[k]], bb[k], qlen, st, ed, i, 0, NULL); PLINE(bb[k], brix[k]); ++lines; }
-				SINK(brix[k], st, ed, Q->offset[i + 1] - Q->offset[i], 1);
+				SINK(bb[k], brix[k], st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 			}
 		}
 	} else
@@ -410,7 +420,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 				} else FinalTaxon = tt;
 			}
 			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[rix], best, qlen, st, ed, i, wt, FinalTaxon); PLINE(best, rix); ++lines; }
-			SINK(rix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
+			SINK(best, rix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 		} else if (mode == BH_ANY) {                                         /* any valid hit; column 12 = duplicate flag (burst.c:4268-4272) */
 			/* The reference prints the first hit within budget a thread meets and marks the query spent (burst.c:4239-4275, 4457-4475).
 			 * Exhaustive path, one thread: clumps ascending, the entries of a clump in sorted order, lanes ascending -- the LAST
@@ -421,7 +431,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 			const uint32_t rix = db->refIxSrt[rp->refIx];
 			uint32_t st, ed; coords(db, rp, rix, qlen, &st, &ed);
 			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line(out, Q->heads[j], db->refHead[rix], rp, qlen, st, ed, j > Q->offset[i]); PLINE(rp, rix); ++lines; }
-			SINK(rix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
+			SINK(rp, rix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 		} else if (mode == BH_ALLPATHS || mode == BH_FORAGE) {               /* burst.c:4582-4640, 4642-4692 */
 			uint32_t b = 0;
 			if (mode == BH_ALLPATHS) {
@@ -444,7 +454,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 			}
 			if (sink) for (uint64_t zz = 0; zz < rix_ix; ++zz) {      /* a read with one placement only is on one line of the file */
 				uint32_t st, ed; coords(db, RPcache[zz], RIXcache[zz], qlen, &st, &ed);
-				SINK(RIXcache[zz], st, ed, Q->offset[i + 1] - Q->offset[i], rix_ix == 1);
+				SINK(RPcache[zz], RIXcache[zz], st, ed, Q->offset[i + 1] - Q->offset[i], rix_ix == 1);
 			}
 		} else {                                                             /* CAPITALIST pass B (burst.c:4746-4779, 4831-4843) */
 			uint32_t b = 0;
@@ -513,7 +523,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 			}
 			uint32_t st, ed; coords(db, best, bestrix, qlen, &st, &ed);
 			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[bestrix], best, qlen, st, ed, i, wt, Final); PLINE(best, bestrix); ++lines; }
-			SINK(bestrix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
+			SINK(best, bestrix, st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 		}
 	}
 	if (out->oom) {

@@ -38,6 +38,7 @@ struct BhSession {
 	int cov_col, em_col, pile_col;  /* the loaded sample has its column in the coverage / the abundance, its block in the variants already */
 	BhPlaceSink sink;               /* the report's placements of the current sample (buffer kept across samples) */
 	BhMates *mates;                 /* bh_session_run_mates: the joiner, made on first use */
+	BhCluster *cluster;             /* bh_session_set_cluster: NULL, or the clustering every reported sample is given */
 	BhPaths *paths;                 /* with o.cigar or o.pile: the tracer on the reporting rank's handle, opened by the first sample that reports */
 	int dead, dbg, threads_ok;
 	int alive;                      /* query tables alive (the current sample's and the prefetched one's) */
@@ -109,6 +110,13 @@ void bh_session_set_node(BhSession *s, BhNode *node) { if (s) s->node = node; }
 void bh_session_set_coverage(BhSession *s, BhCov *cov) { if (s) s->o.cov = cov; }
 void bh_session_set_abundance(BhSession *s, BhEm *em) { if (s) s->o.em = em; }
 void bh_session_set_variants(BhSession *s, BhPile *pile) { if (s) s->o.pile = pile; }
+int bh_session_set_cluster(BhSession *s, BhCluster *cl) {
+	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_cluster: no session");
+	if (cl && s->o.mode != BH_FORAGE) return bh_set_error(BH_E_USAGE, "ERROR: clusters need every relationship under the identity cutoff: a session in mode FORAGE");
+	if (cl && (s->o.cov || s->o.em || s->o.pile || s->o.shard_db > 1)) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with coverage, abundance, variants or database shards");
+	s->cluster = cl;
+	return BH_OK;
+}
 const BhQueries *bh_session_sample(const BhSession *s) { return s && s->cur ? &s->cur->Q : NULL; }
 
 int bh_session_prefetch(BhSession *s, const char *queries) {
@@ -316,7 +324,8 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		setvbuf(s->out, NULL, _IOFBF, 1 << 22);
 		rc = (o->cigar || o->pile) && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
 		if (!rc && s->paths) bh_paths_set_pile(s->paths, o->pile, o->cigar);
-		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov || o->em ? &s->sink : NULL, s->paths);
+		s->sink.want_re = s->cluster != NULL;
+		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov || o->em || s->cluster ? &s->sink : NULL, s->paths);
 		if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
 		FILE *f = s->out; s->out = NULL;
 		if (fclose(f)) { char msg[512]; snprintf(msg, sizeof msg, "ERROR: write failed: %s", s->out_path); return sample_fail(s, res, BH_E_IO, msg); }      /* (a full disk must not end in success) */
@@ -345,6 +354,13 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
 			if (o->verbose) bh_pile_print_info(o->pile);
 			PHASE("variant sites of the sample");
+		}
+		if (s->cluster) {  /* the sample's reads clustered from its own lines, on rank 0's device as well; the tables at once */
+			rc = bh_cluster_sample(s->cluster, R[s->i0].hh, s->db, Q, &s->sink);
+			if (!rc) rc = bh_cluster_write(s->cluster);
+			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
+			if (o->verbose) bh_cluster_print_info(s->cluster);
+			PHASE("clusters of the sample");
 		}
 		free(s->cov_name); s->cov_name = NULL;
 	}
@@ -385,6 +401,7 @@ int bh_session_run_mates(BhSession *s, const char *queries1, const char *queries
 	if (s->o.cov || s->o.cigar) return mates_fail(s, res, BH_E_USAGE, "ERROR: coverage and alignment paths of paired output are out of scope: mates go with neither");
 	if (s->o.em) return mates_fail(s, res, BH_E_USAGE, "ERROR: the abundance of paired output is out of scope: mates do not go with it");
 	if (s->o.pile) return mates_fail(s, res, BH_E_USAGE, "ERROR: variants of paired output are out of scope: mates do not go with them");
+	if (s->cluster) return mates_fail(s, res, BH_E_USAGE, "ERROR: clusters come from the lines of one query file against itself: mates do not go with them");
 	if (s->o.mates.orientation > BHIP_MATES_FF || s->o.mates.report > BHIP_MATES_BEST || s->o.mates.ins_min > s->o.mates.ins_max)
 		return mates_fail(s, res, BH_E_USAGE, "ERROR: mates: orientation fr|rf|ff, report all|best, insert-min <= insert-max");
 	if (s->dead) { res->rc = s->dead; snprintf(res->err, sizeof res->err, "the session was ended by an earlier error (code %d)", s->dead); return bh_set_error(s->dead, "%s", res->err); }
@@ -438,7 +455,7 @@ void bh_session_close(BhSession *s) {
 	/* the ranks' runs belong to the caller (BhMultiRank.run); slices of the session's block must not outlive it */
 	for (int i = 0; i < s->n_local; ++i) if (s->block.hits && s->ranks[i].run.hitsPinned == 2 && s->ranks[i].run.hits >= s->block.hits && s->ranks[i].run.hits < s->block.hits + s->block.capHits) memset(&s->ranks[i].run, 0, sizeof s->ranks[i].run);
 	bh_run_free(&s->block); bh_run_free(&s->all);
-	free(s->sink.lines); free(s->sink.uq); free(s->cov_name); bh_paths_close(s->paths); bh_mates_close(s->mates);
+	free(s->sink.lines); free(s->sink.uq); free(s->sink.re); free(s->cov_name); bh_paths_close(s->paths); bh_mates_close(s->mates);
 	pthread_mutex_destroy(&s->mu);
 	free(s);
 }

@@ -268,7 +268,10 @@ int  bh_report_view(FILE *out, const BhDb *db, const BhQueries *q, const BhRunVi
  * w = the number of lines the entry stands for (the reads of the unique query) | unique << 31 -- unique: each of those reads is on this one
  * line of the file only.  sink->uq holds, entry by entry, the number of the entry's unique query: the entries of one query, those of its
  * reverse complement included, are the placements of the same reads (the groups of bh_em.c).  sink = NULL: bh_report_view. */
-typedef struct BhPlaceSink { BhipCovLine *lines; uint64_t n, cap; uint32_t *uq; } BhPlaceSink;      /* uq[k] (malloc'd like lines): the unique query number of entry k */
+typedef struct BhPlaceSink {
+	BhipCovLine *lines; uint64_t n, cap; uint32_t *uq;      /* uq[k] (malloc'd like lines): the unique query number of entry k */
+	int want_re; uint64_t *re;      /* want_re set by the caller: re[k] (malloc'd like lines) = reference index of the entry's line (db->refHead[re >> 32] is column 2) << 32 | column 11 */
+} BhPlaceSink;
 int  bh_report_view_sink(FILE *out, const BhDb *db, const BhQueries *q, const BhRunView *view, BhMode mode, int flags, const BhTaxOpts *tx, uint64_t *nLines, BhPlaceSink *sink);
 
 /* ---- alignment paths of the printed lines (bh_paths.c; burst_hip --cigar) ----
@@ -444,6 +447,44 @@ void bh_pile_close(BhPile *pile);
 int  bh_pile_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
                   const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]);
 
+/* ---- greedy centroid clusters of the reads of a query file aligned against itself (bh_cluster.c; burst_hip --cluster) ----
+ * The definition is bhip_cluster_run's (include/burst_hip.h): nodes = the reads in file order, named by column 1; weight 1, or with
+ * use_sizes the N of a trailing `;size=N[;]`; an edge per printed line whose column 2 is the name of another read, its edits the smallest
+ * column 11; a line whose column 2 names no read is foreign (counted), a self line is ignored.  PREFIXclusters.txt:
+ * `#Read<TAB>Centroid<TAB>Role<TAB>Edits<TAB>Weight`, one row per read in file order, Role C or M; PREFIXcluster_sizes.txt:
+ * `#OTU ID<TAB>Reads<TAB>Weight`, one row per centroid in priority order, Weight the 64-bit sum over its cluster.  Both are written under
+ * temporary names and renamed together; neither is written when the run ends on an error.
+ *   bh_cluster_names       the reads: resets the object; two byte-equal names are BH_E_USAGE with a text that names them
+ *   bh_cluster_line        `count` printed lines of read q with this column 2 and column 11
+ *   bh_cluster_add_b6      the lines of a .b6 file (columns 1, 2 and 11)
+ *   bh_cluster_solve       one solver call over the edges collected, on `hip_handle`
+ *   bh_cluster_sample      names + lines + solve for a finished run: the reads of Q, the lines of the report's sink (filled with want_re)
+ *   bh_cluster_result      per read: its centroid's number, the edits that joined it, its weight (any may be NULL)
+ *   bh_cluster_print_info  the `Clusters:` line on standard output; bh_cluster_last_info: the same figures (bhip_cluster_info's, lines, foreign lines)
+ *   bh_cluster_set_solver  another solver (tests): bhip_cluster_run's arguments and bhip_cluster_info's array behind ctx, return codes in
+ *                          this file's terms; fn = NULL: the device
+ *   bh_cluster_host        the definition in plain sequential C, a solver (its first argument is ignored): the tests without a device, the yardstick
+ * Any error is final: later calls return it and nothing is written. */
+typedef struct BhCluster BhCluster;
+typedef int (*bh_cluster_solver_fn)(void *ctx, uint32_t n_nodes, const uint32_t *weights, const BhipClusterEdge *edges, uint64_t n_edges, uint32_t *centroid,
+                                    uint32_t *edits, uint64_t info[8]);
+int  bh_cluster_open(const char *prefix, int use_sizes, BhCluster **cl);
+void bh_cluster_set_solver(BhCluster *cl, bh_cluster_solver_fn fn, void *ctx);
+int  bh_cluster_names(BhCluster *cl, const char *const *names, uint32_t n);
+int  bh_cluster_line(BhCluster *cl, uint32_t q, const char *ref_name, size_t ref_len, uint32_t edits, uint64_t count);
+int  bh_cluster_add_b6(BhCluster *cl, const char *path);
+int  bh_cluster_solve(BhCluster *cl, void *hip_handle);
+int  bh_cluster_sample(BhCluster *cl, void *hip_handle, const BhDb *db, const BhQueries *q, const BhPlaceSink *sink);
+uint32_t bh_cluster_reads(const BhCluster *cl);
+int  bh_cluster_result(const BhCluster *cl, uint32_t *centroid, uint32_t *edits, uint32_t *weights);
+void bh_cluster_last_info(const BhCluster *cl, uint64_t info[8], uint64_t *lines, uint64_t *foreign);
+int  bh_cluster_write(BhCluster *cl);
+void bh_cluster_print_info(BhCluster *cl);
+void bh_cluster_abort(BhCluster *cl);
+void bh_cluster_close(BhCluster *cl);
+int  bh_cluster_host(void *unused, uint32_t n_nodes, const uint32_t *weights, const BhipClusterEdge *edges, uint64_t n_edges, uint32_t *centroid, uint32_t *edits,
+                     uint64_t info[8]);
+
 /* ---- a session: the database stays on the devices, a list of query files runs through it (bh_session.c) ---- */
 typedef struct BhSession BhSession;
 typedef struct BhSessionOpts {            /* fixed for the whole session */
@@ -498,6 +539,10 @@ void bh_session_set_node(BhSession *s, BhNode *node);
 void bh_session_set_coverage(BhSession *s, BhCov *cov);      /* BhSessionOpts.cov for a session opened before its database was read */
 void bh_session_set_abundance(BhSession *s, BhEm *em);       /* BhSessionOpts.em likewise */
 void bh_session_set_variants(BhSession *s, BhPile *pile);    /* BhSessionOpts.pile likewise */
+/* NULL, or the clustering every reported sample is given (rank 0's process; the caller opens and closes it): the sample's reads clustered
+ * from its own lines on the reporting rank's handle, the two tables written at once (a later sample writes them again).  Needs mode FORAGE
+ * (BH_E_USAGE otherwise) and is kept beside the options, not in BhSessionOpts */
+int  bh_session_set_cluster(BhSession *s, BhCluster *cl);
 int  bh_session_ended(const BhSession *s);      /* 0, or the code of the error that ended the session */
 void bh_session_close(BhSession *s);
 

@@ -8,6 +8,7 @@
  *             [--mates-orientation fr|rf|ff] [--mates-report all|best]      paired-end reads: the concordant combinations of the two mates' placements (bh_mates.c)
  *   ... -q / -o or --samples ... --coverage PREFIX [--coverage-lengths FILE] [--coverage-pad N]      coverage and count tables per reference and sample (bh_cov.c)
  *   ... -q / -o or --samples ... --abundance PREFIX [--abundance-iters N] [--abundance-tol UNITS]   multi-mapped reads split over their references by EM (bh_em.c)
+ *   burst_hip -r reads.fa|reads.edx [-a|-ad ...] -q reads.fa -o self.b6 -m FORAGE -i ... [-fr] --cluster PREFIX [--cluster-sizes]      greedy centroid clusters of the reads from their self-hits (bh_cluster.c)
  *   ... -q / -o or --samples ... --variants PREFIX [--variants-min-depth N] [--variants-min-alt N] [--variants-reads all|unique]   variant sites per sample (bh_pile.c)
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
@@ -331,6 +332,10 @@ static void usage(void) {
 	puts("                  (Depth, A, C, G, T, Del, Other) and the insertions behind the position (Ins), counted from the alignment paths of the");
 	puts("                  printed lines; a position is listed when its reference base is A/C/G/T, Depth >= --variants-min-depth (4) and the reads");
 	puts("                  that differ, or Ins, are >= --variants-min-alt (2); --variants-reads unique counts only reads printed on one line");
+	puts("--cluster <prefix> [--cluster-sizes]: with -q reads -r the same reads (FASTA or .edx) -m FORAGE, greedy centroid clusters of the reads from the");
+	puts("                  lines they print against each other: the reads in the order of their weight (1, or with --cluster-sizes the N of a trailing");
+	puts("                  ;size=N of the name), ties in file order; a read with a line to an earlier centroid joins the one with the fewest edits, any");
+	puts("                  other read is a centroid.  Leaves <prefix>clusters.txt (per read) and <prefix>cluster_sizes.txt (per centroid)");
 	puts("--host-acx: build accelerators (-d ... -a, --make-acx) with the host builder instead of the device");
 }
 
@@ -349,6 +354,7 @@ int main(int argc, char **argv) {
 	const char *em_prefix = 0; uint32_t em_iters = 1000; uint64_t em_tol = 1024; int em_opts_given = 0;
 	const char *var_prefix = 0; uint32_t var_min_depth = 4, var_min_alt = 2; int var_unique = 0, var_opts_given = 0;
 	const char *mates_FN = 0; BhMatesOpts mopts = {BHIP_MATES_FR, 0, 1000, BHIP_MATES_ALL}; int mates_opts_given = 0;
+	const char *clu_prefix = 0; int clu_sizes = 0;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
 	BhTaxOpts txo; memset(&txo, 0, sizeof txo); txo.taxacut = 10;   /* burst.c:92 */
 	setenv("GPU_MAX_HW_QUEUES", "8", 0);      /* HIP runtime: hardware queues for the library's four streams (read when the runtime starts) */
@@ -410,6 +416,8 @@ int main(int argc, char **argv) {
 			em_opts_given = 1;
 		}
 		else if (!strcmp(a, "--cigar")) cigar = 1;
+		else if (!strcmp(a, "--cluster")) { NEEDARG("--cluster"); clu_prefix = argv[i]; }
+		else if (!strcmp(a, "--cluster-sizes")) clu_sizes = 1;
 		else if (!strcmp(a, "--variants")) { NEEDARG("--variants"); var_prefix = argv[i]; }
 		else if (!strcmp(a, "--variants-min-depth") || !strcmp(a, "--variants-min-alt")) {
 			const int is_alt = !strcmp(a, "--variants-min-alt");
@@ -522,6 +530,16 @@ int main(int argc, char **argv) {
 	if (var_prefix && (shard_db || n_shards)) { puts("ERROR: --variants traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
 	if (var_prefix && !gather_host) { puts("ERROR: --variants takes the host gather only (drop --gather rccl)"); return 1; }
 	if (var_prefix && mates_FN) { puts("ERROR: --variants of paired output are out of scope: they do not go with --mates"); return 1; }
+	/* (--cluster picks clusters from the lines one query file prints against itself: refused before a device is touched whatever would
+	 * discard those lines, print other files' lines, or leave rank 0 without the whole report) */
+	if (clu_sizes && !clu_prefix) { puts("ERROR: --cluster-sizes goes with --cluster <prefix>"); return 1; }
+	if (clu_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --cluster works from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (clu_prefix && mode != BH_FORAGE) { puts("ERROR: --cluster needs every relationship under the identity cutoff: run it with -m FORAGE (the other modes discard them)"); return 1; }
+	if (clu_prefix && samples_FN) { puts("ERROR: --cluster takes one query file aligned against itself: it does not go with --samples"); return 1; }
+	if (clu_prefix && mates_FN) { puts("ERROR: --cluster takes one query file aligned against itself: it does not go with --mates"); return 1; }
+	if (clu_prefix && (shard_db || n_shards)) { puts("ERROR: --cluster needs the whole report on rank 0: it does not go with --shard db or --shards"); return 1; }
+	if (clu_prefix && !gather_host) { puts("ERROR: --cluster takes the host gather only (drop --gather rccl)"); return 1; }
+	if (clu_prefix && (cov_prefix || em_prefix || var_prefix)) { puts("ERROR: --cluster does not go with --coverage, --abundance or --variants: per-reference tables of a self-alignment are out of scope"); return 1; }
 	if (mates_opts_given && mopts.ins_min > mopts.ins_max) { puts("ERROR: --insert-min is larger than --insert-max"); return 1; }
 	if (mates_opts_given && !mates_FN && !samples_FN) { puts("ERROR: --insert-min, --insert-max, --mates-orientation and --mates-report go with --mates"); return 1; }
 	if (mates_FN) {
@@ -814,7 +832,10 @@ int main(int argc, char **argv) {
 		if ((rc = bh_pile_open(&db, var_prefix, var_min_depth, var_min_alt, var_unique, &pile))) DIE(rc);
 		bh_paths_set_pile(paths, pile, cigar);
 	}
-	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em ? &sink : NULL, paths))) DIEP(rc);
+	BhCluster *clu = NULL;
+	if (clu_prefix && (rc = bh_cluster_open(clu_prefix, clu_sizes, &clu))) DIE(rc);
+	sink.want_re = clu != NULL;
+	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em || clu ? &sink : NULL, paths))) DIEP(rc);
 	if (fclose(output)) { fprintf(stderr, "ERROR: write failed: %s\n", output_FN); return 2; }      /* (the last buffer of the report: a full disk must not end in exit code 0) */
 	printf("Wrote %lu alignments\n", (unsigned long)lines);
 	if (paths && cigar) bh_paths_print_info(paths, hhs[0]);
@@ -838,13 +859,19 @@ int main(int argc, char **argv) {
 		printf("Abundance table written: %sabundance.txt\n", em_prefix);
 		PHASE("abundance");
 	}
+	if (clu) {      /* the reads clustered from the lines just printed (rank 0's handle); a usage error -- two reads of one name -- writes no table */
+		if ((rc = bh_cluster_sample(clu, hhs[0], &db, &Q, &sink)) || (rc = bh_cluster_write(clu))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
+		bh_cluster_print_info(clu);
+		printf("Cluster tables written: %sclusters.txt, %scluster_sizes.txt\n", clu_prefix, clu_prefix);
+		PHASE("clusters");
+	}
 	printf("\nAlignment time: %f seconds\n", wall() - start);
 	fflush(NULL);
 	/* The job is done and its output is on disk.  Unpinning and unmapping tens of gigabytes one table after the other took about a
 	 * second for a 32 M-read job; the operating system releases a finished process's memory (host and device) far faster.
 	 * BURST_HOST_TEARDOWN=1 walks through the orderly release instead (leak checks). */
 	if (!getenv("BURST_HOST_TEARDOWN")) _exit(0);
-	bh_cov_close(cov); bh_em_close(em); free(sink.lines); free(sink.uq); bh_paths_close(paths);
+	bh_cov_close(cov); bh_em_close(em); bh_cluster_close(clu); free(sink.lines); free(sink.uq); free(sink.re); bh_paths_close(paths);
 	if (comm) bhip_comm_destroy(comm);
 	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
 	for (int r = 0; r < n_gpus; ++r) bh_run_free(&ranks[r].run);

@@ -118,6 +118,10 @@ COV_TAP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64
 EM_SOLVER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p)
 
 
+# a solver in place of bhip_cluster_run (bh_cluster_set_solver): ctx, n_nodes, weights, edges, n_edges, centroid, edits, info
+CLUSTER_SOLVER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
 class BhSampleResult(C.Structure):
     _fields_ = [("rc", C.c_int), ("err", C.c_char * 512), ("totQ", C.c_uint64), ("numUniq", C.c_uint64), ("nHits", C.c_uint64), ("nLines", C.c_uint64),
                 ("nBatches", C.c_uint32), ("secIngest", C.c_double), ("secIngestWaited", C.c_double), ("secSearch", C.c_double), ("secReport", C.c_double),
@@ -277,6 +281,27 @@ def lib():
         L.bh_pile_close.restype = None
         L.bh_pile_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                    C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+        L.bh_cluster_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.bh_cluster_set_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_cluster_set_solver.restype = None
+        L.bh_cluster_names.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32]
+        L.bh_cluster_line.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64]
+        L.bh_cluster_add_b6.argtypes = [C.c_void_p, C.c_char_p]
+        L.bh_cluster_solve.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_cluster_reads.argtypes = [C.c_void_p]
+        L.bh_cluster_reads.restype = C.c_uint32
+        L.bh_cluster_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_cluster_last_info.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.bh_cluster_last_info.restype = None
+        L.bh_cluster_write.argtypes = [C.c_void_p]
+        L.bh_cluster_print_info.argtypes = [C.c_void_p]
+        L.bh_cluster_print_info.restype = None
+        L.bh_cluster_abort.argtypes = [C.c_void_p]
+        L.bh_cluster_abort.restype = None
+        L.bh_cluster_close.argtypes = [C.c_void_p]
+        L.bh_cluster_close.restype = None
+        L.bh_cluster_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_session_set_cluster.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_session_set_variants.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_session_set_variants.restype = None
         _lib = L
@@ -291,6 +316,94 @@ def em_host(n_headers, group_w, lines, max_iters=1000, tol=1024):
     counts, info = np.zeros(max(int(n_headers), 1), np.uint64), np.zeros(8, np.uint64)
     _chk(lib().bh_em_host(None, int(n_headers), len(group_w), group_w.ctypes.data, lines.ctypes.data, len(lines), int(max_iters), int(tol), counts.ctypes.data, info.ctypes.data))
     return counts[:int(n_headers)], info
+
+
+def cluster_host(weights, edges):
+    """bh_cluster_host, the clustering definition in plain sequential C (no device): (centroid uint32 [n], edits uint32 [n], info uint64 [8]:
+    0, edges kept, centroids, 0, 0, raw edges, nodes, 0).  weights: uint32 per read; edges: capi.CLUSTER_EDGE_DTYPE or rows (q, r, edits)"""
+    weights = np.ascontiguousarray(weights, dtype=np.uint32)
+    edges = capi.cluster_edges(edges)
+    n = len(weights)
+    centroid, edits, info = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(8, np.uint64)
+    _chk(lib().bh_cluster_host(None, n, weights.ctypes.data, edges.ctypes.data, len(edges), centroid.ctypes.data, edits.ctypes.data, info.ctypes.data))
+    return centroid[:n], edits[:n], info
+
+
+class Clusterer:
+    """bh_cluster.c without a run: the reads' names, lines (or a .b6 file), one solve, the two tables prefix{clusters,cluster_sizes}.txt.
+    device: a capi.Device whose handle resolves the greedy order; None: bh_cluster_host (no device); solver(weights, edges) -> (centroid,
+    edits): a solver of the caller's behind bh_cluster_set_solver (tests)"""
+
+    def __init__(self, prefix, names, sizes=False, device=None, solver=None):
+        self.h, self.device = C.c_void_p(), device
+        _chk(lib().bh_cluster_open(prefix.encode(), int(sizes), C.byref(self.h)))
+        if solver is not None:
+            def _solve(ctx, n, w, e, m, centroid, edits, info):
+                try:
+                    wa = np.frombuffer((C.c_uint8 * (n * 4)).from_address(w), dtype=np.uint32).copy() if n else np.zeros(0, np.uint32)
+                    ea = np.frombuffer((C.c_uint8 * (int(m) * 12)).from_address(e), dtype=capi.CLUSTER_EDGE_DTYPE).copy() if m else np.zeros(0, capi.CLUSTER_EDGE_DTYPE)
+                    c, d = solver(wa, ea)
+                    if n:
+                        np.frombuffer((C.c_uint8 * (n * 4)).from_address(centroid), dtype=np.uint32)[:] = c
+                        np.frombuffer((C.c_uint8 * (n * 4)).from_address(edits), dtype=np.uint32)[:] = d
+                    return 0
+                except Exception:      # (an exception must not cross the C frame)
+                    import traceback
+                    traceback.print_exc()
+                    return E_DEVICE
+            self._cb = CLUSTER_SOLVER_FN(_solve)
+            lib().bh_cluster_set_solver(self.h, C.cast(self._cb, C.c_void_p), None)
+        elif device is None:
+            lib().bh_cluster_set_solver(self.h, C.cast(lib().bh_cluster_host, C.c_void_p), None)
+        try:
+            arr = (C.c_char_p * max(len(names), 1))(*[n.encode() if isinstance(n, str) else n for n in names])
+            _chk(lib().bh_cluster_names(self.h, arr, len(names)))
+        except Exception:
+            self.close()
+            raise
+
+    def line(self, q, ref_name, edits, count=1):
+        ref_name = ref_name.encode() if isinstance(ref_name, str) else ref_name
+        _chk(lib().bh_cluster_line(self.h, int(q), ref_name, len(ref_name), int(edits), int(count)))
+
+    def add_b6(self, path):
+        _chk(lib().bh_cluster_add_b6(self.h, path.encode()))
+
+    def solve(self):
+        _chk(lib().bh_cluster_solve(self.h, self.device._h if self.device is not None else None))
+        return _cluster_result(self.h)
+
+    def info(self):
+        return _cluster_info(self.h)
+
+    def write(self):
+        _chk(lib().bh_cluster_write(self.h))
+
+    def close(self):
+        if self.h:
+            lib().bh_cluster_close(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _cluster_result(h):
+    n = lib().bh_cluster_reads(h)
+    centroid, edits = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    _chk(lib().bh_cluster_result(h, centroid.ctypes.data, edits.ctypes.data, None))
+    return centroid[:n], edits[:n]
+
+
+def _cluster_info(h):
+    info, lines, foreign = np.zeros(8, np.uint64), C.c_uint64(), C.c_uint64()
+    lib().bh_cluster_last_info(h, info.ctypes.data, C.byref(lines), C.byref(foreign))
+    d = dict(zip(capi.CLUSTER_INFO, (int(x) for x in info)))
+    d["lines"], d["foreign"] = lines.value, foreign.value
+    return d
 
 
 def pile_refs(packed, clump_len, tot_refs):
@@ -662,7 +775,8 @@ class Session:
                  coverage=None, coverage_lengths=None, coverage_pad=0, coverage_tap=None, cigar=False,
                  mates_orientation="fr", insert_min=0, insert_max=1000, mates_report="all", mates_join=None,
                  abundance=None, abundance_iters=1000, abundance_tol=1024, abundance_host=False,
-                 variants=None, variants_min_depth=4, variants_min_alt=2, variants_reads="all", variants_host=False):
+                 variants=None, variants_min_depth=4, variants_min_alt=2, variants_reads="all", variants_host=False,
+                 cluster=None, cluster_sizes=False, cluster_host=False):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
         reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
         process only).
@@ -678,10 +792,14 @@ class Session:
         reads differ from the reference, counted from the alignment paths of the printed lines; listed from variants_min_depth reads on the
         position and variants_min_alt that differ; variants_reads "unique" counts only reads printed on one line), counted on rank 0's device
         handle -- or by bh_pile_host with variants_host=True; variants() returns the rows so far, close() writes the table unless the
-        session ended on an error.  Opens the path tracer without adding the cigar columns; same limits as cigar.  Not with mates."""
+        session ended on an error.  Opens the path tracer without adding the cigar columns; same limits as cigar.  Not with mates.
+        cluster = prefix: every reported sample -- meant for ONE, the reads of the database's own FASTA, mode FORAGE -- has its reads clustered
+        from the lines it prints (bh_cluster.c: greedy centroid clusters; cluster_sizes: weights from `;size=N` suffixes), resolved on rank
+        0's device handle -- or by bh_cluster_host with cluster_host=True -- and prefix{clusters,cluster_sizes}.txt written at once;
+        clusters() returns (centroid, edits) per read of the last sample.  FORAGE only; not with shard_db, mates, coverage, abundance, variants."""
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
         self._mates_join = mates_join
-        self.cov, self.em, self.pile = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.cov, self.em, self.pile, self.cluster = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         devs = list(devs) if isinstance(devs, (list, tuple)) else [devs]
         n_local = len(devs)
         world = world or n_local
@@ -748,7 +866,19 @@ class Session:
                 self._pile_refs = BhPileRefs(C.cast(db.c.packed, C.c_void_p), C.cast(db.c.clumpLen, C.c_void_p), db.c.numRclumps, db.c.totR)
                 lib().bh_pile_set_solver(self.pile, C.cast(lib().bh_pile_host, C.c_void_p), C.cast(C.pointer(self._pile_refs), C.c_void_p))
             o.pile = self.pile
+        if cluster is not None:
+            if mode != "FORAGE":
+                raise ValueError("cluster: needs every relationship under the identity cutoff: mode FORAGE")
+            if (shard_db and int(shard_db) > 1) or align is not None or world != n_local:
+                raise ValueError("cluster: needs the whole report and the device handles of one process (no shard_db, no align back end, no job of processes)")
+            if coverage is not None or abundance is not None or variants is not None:
+                raise ValueError("cluster: per-reference tables of a self-alignment are out of scope (no coverage, abundance, variants)")
+            _chk(lib().bh_cluster_open(cluster.encode(), int(bool(cluster_sizes)), C.byref(self.cluster)))
+            if cluster_host:
+                lib().bh_cluster_set_solver(self.cluster, C.cast(lib().bh_cluster_host, C.c_void_p), None)
         _chk(lib().bh_session_open(C.byref(db.c), self.ranks, n_local, world, comm, node.h if node is not None else None, C.byref(o), C.byref(self.h)))
+        if self.cluster:
+            _chk(lib().bh_session_set_cluster(self.h, self.cluster))
 
     def _align_cb(self, align):
         def _align(ctx, q, u0, u1, n, mode, batch, run):
@@ -898,6 +1028,17 @@ class Session:
         d["lines"] = lines.value
         return d
 
+    def clusters(self):
+        """the last sample's clustering: (centroid uint32 [reads], edits uint32 [reads]) per read in file order -- the number of its centroid
+        (its own for a centroid) and the edits of the line that joined it"""
+        if not self.cluster:
+            raise HostError("the session has no clustering")
+        return _cluster_result(self.cluster)
+
+    def clusters_info(self):
+        """the last clustering's figures: rounds, edges_kept, centroids, device_us, device_bytes, edges, nodes, lines, foreign"""
+        return _cluster_info(self.cluster)
+
     def coverage_abort(self):
         """the walk ends on an error that the session itself has not seen (another rank's): close() writes no tables"""
         if self.cov:
@@ -928,6 +1069,9 @@ class Session:
                     err = lib().bh_last_error().decode("utf-8", "replace")
                 lib().bh_pile_close(self.pile)
                 self.pile = C.c_void_p()
+            if self.cluster:      # (its tables were written when the sample was reported)
+                lib().bh_cluster_close(self.cluster)
+                self.cluster = C.c_void_p()
             lib().bh_session_close(self.h)
             self.h = C.c_void_p()
             for i in range(len(self.ranks)):

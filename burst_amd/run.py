@@ -213,7 +213,12 @@ def main(argv=None):
     ap.add_argument("--cigar", action="store_true", help="not available here: the alignment paths are traced by burst_hip --cigar (one process, the host gather)")
     ap.add_argument("--abundance", metavar="PREFIX", help="not available here: the abundance table is written by burst_hip --abundance (one process, the host gather)")
     ap.add_argument("--variants", metavar="PREFIX", help="not available here: the variants table is written by burst_hip --variants (one process, the host gather)")
+    ap.add_argument("--cluster", metavar="PREFIX", help="not available here: reads are clustered by burst_hip --cluster (one process, the host gather)")
+    ap.add_argument("--cluster-sizes", action="store_true", help="not available here: goes with burst_hip --cluster")
     args = ap.parse_args(argv)
+    if args.cluster or args.cluster_sizes:      # (exit code 1, as burst_hip refuses what it cannot do)
+        print("ERROR: --cluster is not available in python -m burst_amd.run: use burst_hip --cluster (one process, --gpus N with the host gather)", flush=True)
+        return 1
     if args.variants:       # (exit code 1, as burst_hip refuses what it cannot do)
         print("ERROR: --variants is not available in python -m burst_amd.run: use burst_hip --variants (one process, --gpus N with the host gather)", flush=True)
         return 1

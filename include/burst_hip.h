@@ -441,6 +441,35 @@ BHIP_API int bhip_pile_run(void *handle, const uint8_t *q_codes, const uint64_t 
                            const BhipPileLine *lines, uint64_t n_lines, const uint32_t *ops, uint64_t n_ops,
                            uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]);
 
+/* Clustering: greedy centroid clusters of the reads of a query file from the lines it prints against itself (burst_hip --cluster; no
+ * reference counterpart: its README lists clustering "as an output mode" as planned and names the recipe -- the queries as their own
+ * references in FORAGE, then clusters picked from that hit graph).  All of it is integer arithmetic, bit-exact on any machine.
+ *   NODES     0 .. n_nodes - 1: the reads of the -q file in file order; a node's name is column 1 as printed.
+ *   WEIGHT    weights[node]: 1, or with --cluster-sizes the N of a trailing `;size=N` or `;size=N;` of the name (1 .. 2^32 - 1; a name
+ *             without that suffix weighs 1).  Two reads with byte-equal names are a usage error that names them.
+ *   EDGE      q -> r with `edits`: a printed line whose column 1 is read q and whose column 2 is byte-equal to the name of a read r != q;
+ *             edits = the smallest column 11 over all such lines (both strands, several placements, several shears).  A line whose
+ *             column 2 names no read is FOREIGN: ignored and counted.  A self line is ignored.  Edges are directed -- the aligner places
+ *             the query end to end inside the reference, so q -> r does not imply r -> q: an edge reads "r can represent q".
+ *   PRIORITY  q is before r when its weight is larger, or the weights are equal and its number is smaller.
+ *   CLUSTERS  the reads in priority order: a read with an edge to a centroid that came before it is a MEMBER of the one with the smallest
+ *             edits among those, the one that came first among equals; any other read is a CENTROID.  Edges towards reads of lower
+ *             priority never matter; a read without lines is a centroid of its own.
+ * bhip_cluster_run takes the edges raw -- duplicates, self edges and edges towards lower priority included; the device cleans them -- and
+ * returns per node centroid_out = its centroid's node (itself for a centroid) and edits_out = the edits of the edge that joined it (0
+ * for a centroid).  Fewer than 2^32 - 1 nodes and fewer than 2^32 edges.  BHIP_E_ARG with a text, before any device memory is touched
+ * and with the handle staying usable, for an edge that names a node >= n_nodes.  n_edges == 0 launches nothing: every read is a centroid.
+ * The greedy order is resolved in rounds over a sorted adjacency (csrc/bhip_cluster.hip): a node decides once
+ * every earlier neighbour it depends on has decided, so a chain i -> i - 1 takes one round per node -- correct and slow, and not capped.
+ * A round that decides nothing is BHIP_E_INTERNAL.  The call leaves nothing resident but scratch buffers of the handle.
+ * bhip_cluster_info, of the last bhip_cluster_run on the handle: [0] rounds, [1] edges kept (distinct, towards higher priority), [2]
+ * centroids, [3] device microseconds (HIP events around everything launched), [4] device bytes of the scratch buffers, [5] raw edges,
+ * [6] nodes, [7] 0. */
+typedef struct BhipClusterEdge { uint32_t q, r, edits; } BhipClusterEdge;
+BHIP_API int bhip_cluster_run(void *handle, uint32_t n_nodes, const uint32_t *weights, const BhipClusterEdge *edges, uint64_t n_edges,
+                              uint32_t *centroid_out, uint32_t *edits_out);
+BHIP_API int bhip_cluster_info(void *handle, uint64_t info[8]);
+
 /* Tuning knobs.  "prefilter_stride": 0 (default) = automatic sparse seeds -- per query the largest stride s <= K for
  * which an alignment within budget still keeps >= 3 of the words starting at 0, s, 2s, ... (one edit destroys at most
  * ceil(K/s) of them), fewest .acx look-ups with the same no-false-negative guarantee; s >= 1 forces every s-th word,
