@@ -49,7 +49,7 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
            "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_pile_run",
-           "bhip_cluster_run", "bhip_cluster_info"]
+           "bhip_cluster_run", "bhip_cluster_info", "bhip_chimera_run", "bhip_chimera_info"]
 
 # BhipMateLine, 20 bytes: pair and header numbers, .b6 columns 9 and 10 (signed), column 11
 MATE_LINE_DTYPE = np.dtype([("pair", "<u4"), ("ref", "<u4"), ("st", "<i4"), ("ed", "<i4"), ("edits", "<u4")])
@@ -102,6 +102,24 @@ def cluster_edges(rows):
     rows = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
     out = np.zeros(len(rows), CLUSTER_EDGE_DTYPE)
     out["q"], out["r"], out["edits"] = rows[:, 0], rows[:, 1], rows[:, 2]
+    return out
+
+
+# BhipChimLine, 24 bytes: read q has a printed line against read r (flags bit 0: reverse strand) with the path ops[op_off : op_off + n_ops];
+# BhipChimera, 32 bytes: a read's row (bhip_chimera_run)
+CHIM_LINE_DTYPE = np.dtype([("q", "<u4"), ("r", "<u4"), ("flags", "<u4"), ("n_ops", "<u4"), ("op_off", "<u8")])
+CHIMERA_DTYPE = np.dtype([("role", "<u4"), ("single", "<u4"), ("model", "<u4"), ("cut", "<u4"), ("a", "<u4"), ("ea", "<u4"), ("b", "<u4"), ("eb", "<u4")])
+assert CHIM_LINE_DTYPE.itemsize == 24 and CHIMERA_DTYPE.itemsize == 32
+CHIMERA_INFO = ("pairs_kept", "evaluated", "chimeric", "device_us", "device_bytes", "lines", "nodes")
+
+
+def chim_lines(rows):
+    """a CHIM_LINE_DTYPE array as it is (contiguous), rows (q, r, flags, n_ops, op_off) as one"""
+    if isinstance(rows, np.ndarray) and rows.dtype == CHIM_LINE_DTYPE:
+        return np.ascontiguousarray(rows)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 5)
+    out = np.zeros(len(rows), CHIM_LINE_DTYPE)
+    out["q"], out["r"], out["flags"], out["n_ops"], out["op_off"] = rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], rows[:, 4]
     return out
 
 
@@ -247,6 +265,10 @@ def _load():
     lib.bhip_cluster_run.restype = i32
     lib.bhip_cluster_info.argtypes = [vp, vp]
     lib.bhip_cluster_info.restype = i32
+    lib.bhip_chimera_run.argtypes = [vp, u32, vp, vp, vp, u64, vp, u64, u32, u32, u32, vp]
+    lib.bhip_chimera_run.restype = i32
+    lib.bhip_chimera_info.argtypes = [vp, vp]
+    lib.bhip_chimera_info.restype = i32
     for f in (lib.bhip_cov_begin, lib.bhip_cov_add, lib.bhip_cov_sample_stats, lib.bhip_cov_dataset_stats, lib.bhip_cov_info, lib.bhip_cov_end, lib.bhip_lane_extents):
         f.restype = i32
     return lib
@@ -539,6 +561,27 @@ class Device:
         info = np.zeros(8, np.uint64)
         _chk(lib().bhip_cluster_info(self._h, _ptr(info)))
         return dict(zip(CLUSTER_INFO, (int(x) for x in info)))
+
+    def chimera_run(self, weights, lens, lines, ops, skew=2, min_seg=16, min_gain=3):
+        """the two-parent chimera check (bhip_chimera_run).  weights, lens: uint32 per node (read); lines: CHIM_LINE_DTYPE array (or rows q, r,
+        flags, n_ops, op_off), raw -- self lines, lines towards non-candidates and repeated (q, r) included; ops: uint32 words length << 4 |
+        code.  Returns a CHIMERA_DTYPE array, one row per node; chimera_info() has the call's figures"""
+        weights = np.ascontiguousarray(weights, dtype=np.uint32)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        lines = chim_lines(lines)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        n = len(weights)
+        if len(lens) != n:
+            raise ValueError("chimera_run: one length per weight")
+        out = np.zeros(max(n, 1), CHIMERA_DTYPE)
+        _chk(lib().bhip_chimera_run(self._h, n, _ptr(weights), _ptr(lens), _ptr(lines), len(lines), _ptr(ops), len(ops), int(skew), int(min_seg), int(min_gain), _ptr(out)))
+        return out[:n]
+
+    def chimera_info(self):
+        """the last chimera_run's figures: pairs_kept, evaluated, chimeric, device_us, device_bytes, lines, nodes"""
+        info = np.zeros(8, np.uint64)
+        _chk(lib().bhip_chimera_info(self._h, _ptr(info)))
+        return dict(zip(CHIMERA_INFO, (int(x) for x in info)))
 
     def pile_info(self):
         """the last pile_run's figures: events, candidates, sites, device_us, peak_bytes"""

@@ -147,7 +147,13 @@ static uint32_t lookup(const BhCluster *cl, const char *s, size_t len) {
 	}
 }
 
-int bh_cluster_names(BhCluster *cl, const char *const *names, uint32_t n) {
+int bh_cluster_names(BhCluster *cl, const char *const *names, uint32_t n) { return bh_cluster_names_as(cl, names, n, "--cluster", "--cluster-sizes"); }
+uint32_t bh_cluster_find(const BhCluster *cl, const char *s, size_t len) { return cl ? lookup(cl, s, len) : NO_NODE; }
+const char *bh_cluster_name(const BhCluster *cl, uint32_t node) { return cl && node < cl->n ? cl->name[node] : NULL; }
+const uint32_t *bh_cluster_weights(const BhCluster *cl) { return cl ? cl->w : NULL; }
+
+/* (the same under another flag's name: bh_chimera.c keeps its reads in such a table) */
+int bh_cluster_names_as(BhCluster *cl, const char *const *names, uint32_t n, const char *flag, const char *sizes_flag) {
 	if (!cl) return bh_set_error(BH_E_USAGE, "bh_cluster_names: no cluster object");
 	if (cl->dead) return bh_set_error(cl->dead, "clustering was ended by an earlier error");
 	if (n && !names) return bh_set_error(BH_E_USAGE, "bh_cluster_names: no names");
@@ -170,7 +176,7 @@ int bh_cluster_names(BhCluster *cl, const char *const *names, uint32_t n) {
 		const uint32_t other = lookup(cl, s, len);
 		if (other != NO_NODE) {
 			cl->dead = BH_E_USAGE;
-			return bh_set_error(BH_E_USAGE, "ERROR: --cluster needs every read named once: reads %u and %u of the query file are both named '%s'", other + 1, i + 1, s);
+			return bh_set_error(BH_E_USAGE, "ERROR: %s needs every read named once: reads %u and %u of the query file are both named '%s'", flag, other + 1, i + 1, s);
 		}
 		uint64_t h = name_hash(s, len) & cl->mask;
 		while (cl->tab[h]) h = (h + 1) & cl->mask;
@@ -178,7 +184,7 @@ int bh_cluster_names(BhCluster *cl, const char *const *names, uint32_t n) {
 		cl->w[i] = 1;
 		if (cl->use_sizes) {
 			const int64_t v = size_suffix(s);
-			if (v < 0) { cl->dead = BH_E_USAGE; return bh_set_error(BH_E_USAGE, "ERROR: --cluster-sizes: the size of read '%s' is not a number 1 .. 4294967295", s); }
+			if (v < 0) { cl->dead = BH_E_USAGE; return bh_set_error(BH_E_USAGE, "ERROR: %s: the size of read '%s' is not a number 1 .. 4294967295", sizes_flag, s); }
 			if (v) cl->w[i] = (uint32_t)v;
 		}
 	}
@@ -259,6 +265,19 @@ static int headat_cmp(const void *a, const void *b) {
 	return (x->j > y->j) - (x->j < y->j);
 }
 
+/* the reads of Q in file order (their names lie in the file's text in that order): names[k] = the k-th read's, node_of[j] = the place of
+ * heads[j]; both with room for totQ + 1 */
+int bh_cluster_file_order(const BhQueries *Q, const char **names, uint32_t *node_of) {
+	const uint64_t n = Q->totQ;
+	HeadAt *at = malloc((n + 1) * sizeof(*at));
+	if (!at) return bh_set_error(BH_E_OOM, "OOM:cluster");
+	for (uint64_t j = 0; j < n; ++j) { at[j].p = Q->heads[j]; at[j].j = j; }
+	qsort(at, n, sizeof(*at), headat_cmp);
+	for (uint64_t k = 0; k < n; ++k) { names[k] = at[k].p; node_of[at[k].j] = (uint32_t)k; }
+	free(at);
+	return BH_OK;
+}
+
 /* a finished run: the reads of Q in file order (their names lie in the file's text in that order), the lines from the report's sink
  * (filled with want_re), solved on `hh` */
 int bh_cluster_sample(BhCluster *cl, void *hh, const BhDb *db, const BhQueries *Q, const BhPlaceSink *sink) {
@@ -267,16 +286,11 @@ int bh_cluster_sample(BhCluster *cl, void *hh, const BhDb *db, const BhQueries *
 	if (sink->n && (!sink->uq || !sink->re)) return bh_set_error(BH_E_USAGE, "bh_cluster_sample: the report's lines came without their references and edits");
 	if (Q->totQ >= NO_NODE) return bh_set_error(BH_E_USAGE, "ERROR: --cluster takes fewer than 2^32 - 1 reads");
 	const uint64_t n = Q->totQ;
-	HeadAt *at = malloc((n + 1) * sizeof(*at));
 	const char **names = malloc((n + 1) * sizeof(*names));
 	uint32_t *node_of = malloc((n + 1) * 4);
-	int rc = at && names && node_of ? BH_OK : bh_set_error(BH_E_OOM, "OOM:cluster");
-	if (!rc) {
-		for (uint64_t j = 0; j < n; ++j) { at[j].p = Q->heads[j]; at[j].j = j; }
-		qsort(at, n, sizeof(*at), headat_cmp);
-		for (uint64_t k = 0; k < n; ++k) { names[k] = at[k].p; node_of[at[k].j] = (uint32_t)k; }
-		rc = bh_cluster_names(cl, names, (uint32_t)n);
-	}
+	int rc = names && node_of ? BH_OK : bh_set_error(BH_E_OOM, "OOM:cluster");
+	if (!rc) rc = bh_cluster_file_order(Q, names, node_of);
+	if (!rc) rc = bh_cluster_names(cl, names, (uint32_t)n);
 	for (uint64_t k = 0; !rc && k < sink->n; ++k) {
 		const uint64_t i = sink->uq[k];
 		if (i >= Q->numUniq) { rc = bh_set_error(BH_E_INTERNAL, "bh_cluster_sample: entry %llu names query %llu of %llu", (unsigned long long)k, (unsigned long long)i, (unsigned long long)Q->numUniq); break; }
@@ -284,7 +298,7 @@ int bh_cluster_sample(BhCluster *cl, void *hh, const BhDb *db, const BhQueries *
 		const size_t rl = strlen(rn);
 		for (uint64_t j = Q->offset[i]; !rc && j < Q->offset[i + 1]; ++j) rc = bh_cluster_line(cl, node_of[j], rn, rl, (uint32_t)sink->re[k], 1);
 	}
-	free(at); free(names); free(node_of);
+	free(names); free(node_of);
 	if (rc) { if (!cl->dead) cl->dead = rc; return rc; }
 	return bh_cluster_solve(cl, hh);
 }

@@ -39,7 +39,8 @@ struct BhSession {
 	BhPlaceSink sink;               /* the report's placements of the current sample (buffer kept across samples) */
 	BhMates *mates;                 /* bh_session_run_mates: the joiner, made on first use */
 	BhCluster *cluster;             /* bh_session_set_cluster: NULL, or the clustering every reported sample is given */
-	BhPaths *paths;                 /* with o.cigar or o.pile: the tracer on the reporting rank's handle, opened by the first sample that reports */
+	BhChimera *chimera;             /* bh_session_set_chimera: NULL, or the chimera check every reported sample is given */
+	BhPaths *paths;                 /* with o.cigar, o.pile or a chimera check: the tracer on the reporting rank's handle, opened by the first sample that reports */
 	int dead, dbg, threads_ok;
 	int alive;                      /* query tables alive (the current sample's and the prefetched one's) */
 	pthread_mutex_t mu;             /* `alive` and its debug line */
@@ -115,6 +116,13 @@ int bh_session_set_cluster(BhSession *s, BhCluster *cl) {
 	if (cl && s->o.mode != BH_FORAGE) return bh_set_error(BH_E_USAGE, "ERROR: clusters need every relationship under the identity cutoff: a session in mode FORAGE");
 	if (cl && (s->o.cov || s->o.em || s->o.pile || s->o.shard_db > 1)) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with coverage, abundance, variants or database shards");
 	s->cluster = cl;
+	return BH_OK;
+}
+int bh_session_set_chimera(BhSession *s, BhChimera *ch) {
+	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_chimera: no session");
+	if (ch && s->o.mode != BH_FORAGE) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check needs every relationship under the identity cutoff: a session in mode FORAGE");
+	if (ch && (s->o.cov || s->o.em || s->o.pile || s->o.shard_db > 1)) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check does not go with coverage, abundance, variants or database shards");
+	s->chimera = ch;
 	return BH_OK;
 }
 const BhQueries *bh_session_sample(const BhSession *s) { return s && s->cur ? &s->cur->Q : NULL; }
@@ -322,8 +330,9 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		const double tr = wall();
 		uint64_t lines = 0;
 		setvbuf(s->out, NULL, _IOFBF, 1 << 22);
-		rc = (o->cigar || o->pile) && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
+		rc = (o->cigar || o->pile || s->chimera) && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
 		if (!rc && s->paths) bh_paths_set_pile(s->paths, o->pile, o->cigar);
+		if (!rc && s->chimera && !(rc = bh_chimera_begin(s->chimera, s->db, Q))) bh_paths_set_chimera(s->paths, s->chimera, o->cigar);
 		s->sink.want_re = s->cluster != NULL;
 		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov || o->em || s->cluster ? &s->sink : NULL, s->paths);
 		if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
@@ -361,6 +370,13 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
 			if (o->verbose) bh_cluster_print_info(s->cluster);
 			PHASE("clusters of the sample");
+		}
+		if (s->chimera) {  /* the sample's reads checked from its own lines and their paths, on rank 0's device as well; the table at once */
+			rc = bh_chimera_solve(s->chimera, R[s->i0].hh);
+			if (!rc) rc = bh_chimera_write(s->chimera);
+			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
+			if (o->verbose) bh_chimera_print_info(s->chimera);
+			PHASE("chimera check of the sample");
 		}
 		free(s->cov_name); s->cov_name = NULL;
 	}
@@ -401,6 +417,7 @@ int bh_session_run_mates(BhSession *s, const char *queries1, const char *queries
 	if (s->o.cov || s->o.cigar) return mates_fail(s, res, BH_E_USAGE, "ERROR: coverage and alignment paths of paired output are out of scope: mates go with neither");
 	if (s->o.em) return mates_fail(s, res, BH_E_USAGE, "ERROR: the abundance of paired output is out of scope: mates do not go with it");
 	if (s->o.pile) return mates_fail(s, res, BH_E_USAGE, "ERROR: variants of paired output are out of scope: mates do not go with them");
+	if (s->chimera) return mates_fail(s, res, BH_E_USAGE, "ERROR: the chimera check works from the lines of one query file against itself: mates do not go with it");
 	if (s->cluster) return mates_fail(s, res, BH_E_USAGE, "ERROR: clusters come from the lines of one query file against itself: mates do not go with them");
 	if (s->o.mates.orientation > BHIP_MATES_FF || s->o.mates.report > BHIP_MATES_BEST || s->o.mates.ins_min > s->o.mates.ins_max)
 		return mates_fail(s, res, BH_E_USAGE, "ERROR: mates: orientation fr|rf|ff, report all|best, insert-min <= insert-max");

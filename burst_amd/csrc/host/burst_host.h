@@ -484,6 +484,59 @@ void bh_cluster_abort(BhCluster *cl);
 void bh_cluster_close(BhCluster *cl);
 int  bh_cluster_host(void *unused, uint32_t n_nodes, const uint32_t *weights, const BhipClusterEdge *edges, uint64_t n_edges, uint32_t *centroid, uint32_t *edits,
                      uint64_t info[8]);
+/* the table of read names on its own (bh_chimera.c keeps its reads in one): bh_cluster_names with the flags its two usage errors name;
+ * the node of a name (0xFFFFFFFF: none), a node's name, the weights (valid until the next names call); the reads of Q in file order */
+int  bh_cluster_names_as(BhCluster *cl, const char *const *names, uint32_t n, const char *flag, const char *sizes_flag);
+uint32_t bh_cluster_find(const BhCluster *cl, const char *s, size_t len);
+const char *bh_cluster_name(const BhCluster *cl, uint32_t node);
+const uint32_t *bh_cluster_weights(const BhCluster *cl);
+int  bh_cluster_file_order(const BhQueries *q, const char **names, uint32_t *node_of);
+
+/* ---- de-novo two-parent chimera check of the reads of a query file aligned against itself (bh_chimera.c; burst_hip --chimeras) ----
+ * The definition is bhip_chimera_run's (include/burst_hip.h): nodes, names and weights as in the clustering (the same name table);
+ * candidate parents weigh at least skew times the read; per (read, parent) the printed line with the fewest edits counts; the edit
+ * positions of its alignment path, in read orientation, give for every cut the edits left and right of it; the best two-parent model
+ * over all cuts is set against the best single parent.  PREFIXchimeras.txt:
+ * `#Read<TAB>Role<TAB>Single<TAB>Model<TAB>Cut<TAB>ParentA<TAB>EditsA<TAB>ParentB<TAB>EditsB<TAB>Weight`, one row per read in file order, Role
+ * Y (chimeric), N, or - (not evaluated: 0 for the numbers, * for the parents); written under a temporary name and renamed, never when the
+ * run ends on an error.
+ *   bh_chimera_open        skew, min_seg, min_gain outside 1 .. 2^31 - 1 are BH_E_USAGE
+ *   bh_chimera_names       the reads and their lengths: resets the object; two byte-equal names are BH_E_USAGE with a text that names them
+ *   bh_chimera_line        one printed line of read q: column 2, strand (reverse: column 9 > column 10), its path's op words
+ *   bh_chimera_add_b6      the lines of a .b6 file written with --cigar (columns 1, 2, 9, 10 and the last)
+ *   bh_chimera_begin       before a run's report: the reads of Q (names, lengths) and the headers of db
+ *   bh_paths_set_chimera   the collector of the path tracer is this object (columns: whether the lines get the --cigar columns): every
+ *                          traced group and the notes of its printed lines become lines here -- the read from the line's unique query
+ *                          (duplicate reads carry its path, one line per read), the parent from the header's name, the strand from the entry
+ *   bh_chimera_solve       one solver call over the lines collected, on `hip_handle`
+ *   bh_chimera_result      per read: its BhipChimera, its weight (either may be NULL)
+ *   bh_chimera_print_info  the `Chimeras:` line on standard output; bh_chimera_last_info: the same figures (bhip_chimera_info's, lines, foreign lines)
+ *   bh_chimera_set_solver  another solver (tests): bhip_chimera_run's arguments and bhip_chimera_info's array behind ctx, return codes in
+ *                          this file's terms; fn = NULL: the device
+ *   bh_chimera_host        the definition in plain sequential C, a solver (its first argument is ignored): it materialises L[c] for every
+ *                          line and cut; the tests without a device and the yardstick.  It checks what bhip_chimera_run checks
+ *                          (BH_E_USAGE) and that a chimeric read has two different parents (BH_E_INTERNAL otherwise)
+ * Any error is final: later calls return it and nothing is written. */
+typedef struct BhChimera BhChimera;
+typedef int (*bh_chimera_solver_fn)(void *ctx, uint32_t n_nodes, const uint32_t *weights, const uint32_t *len, const BhipChimLine *lines, uint64_t n_lines,
+                                    const uint32_t *ops, uint64_t n_ops, uint32_t skew, uint32_t min_seg, uint32_t min_gain, BhipChimera *out, uint64_t info[8]);
+int  bh_chimera_open(const char *prefix, int use_sizes, uint32_t skew, uint32_t min_seg, uint32_t min_gain, BhChimera **ch);
+void bh_chimera_set_solver(BhChimera *ch, bh_chimera_solver_fn fn, void *ctx);
+int  bh_chimera_names(BhChimera *ch, const char *const *names, const uint32_t *lens, uint32_t n);
+int  bh_chimera_line(BhChimera *ch, uint32_t q, const char *ref_name, size_t ref_len, int reverse, const uint32_t *ops, uint32_t n_ops);
+int  bh_chimera_add_b6(BhChimera *ch, const char *path);
+int  bh_chimera_begin(BhChimera *ch, const BhDb *db, const BhQueries *q);
+void bh_paths_set_chimera(BhPaths *paths, BhChimera *ch, int columns);
+int  bh_chimera_solve(BhChimera *ch, void *hip_handle);
+uint32_t bh_chimera_reads(const BhChimera *ch);
+int  bh_chimera_result(const BhChimera *ch, BhipChimera *out, uint32_t *weights);
+void bh_chimera_last_info(const BhChimera *ch, uint64_t info[8], uint64_t *lines, uint64_t *foreign);
+int  bh_chimera_write(BhChimera *ch);
+void bh_chimera_print_info(BhChimera *ch);
+void bh_chimera_abort(BhChimera *ch);
+void bh_chimera_close(BhChimera *ch);
+int  bh_chimera_host(void *unused, uint32_t n_nodes, const uint32_t *weights, const uint32_t *len, const BhipChimLine *lines, uint64_t n_lines,
+                     const uint32_t *ops, uint64_t n_ops, uint32_t skew, uint32_t min_seg, uint32_t min_gain, BhipChimera *out, uint64_t info[8]);
 
 /* ---- a session: the database stays on the devices, a list of query files runs through it (bh_session.c) ---- */
 typedef struct BhSession BhSession;
@@ -543,6 +596,9 @@ void bh_session_set_variants(BhSession *s, BhPile *pile);    /* BhSessionOpts.pi
  * from its own lines on the reporting rank's handle, the two tables written at once (a later sample writes them again).  Needs mode FORAGE
  * (BH_E_USAGE otherwise) and is kept beside the options, not in BhSessionOpts */
 int  bh_session_set_cluster(BhSession *s, BhCluster *cl);
+/* likewise NULL, or the chimera check every reported sample is given: it opens the path tracer (without the --cigar columns unless the
+ * session has them), collects the sample's lines from the traced groups, and writes its table at once.  Mode FORAGE only */
+int  bh_session_set_chimera(BhSession *s, BhChimera *ch);
 int  bh_session_ended(const BhSession *s);      /* 0, or the code of the error that ended the session */
 void bh_session_close(BhSession *s);
 

@@ -9,6 +9,8 @@
  *   ... -q / -o or --samples ... --coverage PREFIX [--coverage-lengths FILE] [--coverage-pad N]      coverage and count tables per reference and sample (bh_cov.c)
  *   ... -q / -o or --samples ... --abundance PREFIX [--abundance-iters N] [--abundance-tol UNITS]   multi-mapped reads split over their references by EM (bh_em.c)
  *   burst_hip -r reads.fa|reads.edx [-a|-ad ...] -q reads.fa -o self.b6 -m FORAGE -i ... [-fr] --cluster PREFIX [--cluster-sizes]      greedy centroid clusters of the reads from their self-hits (bh_cluster.c)
+ *   burst_hip -r reads.fa|reads.edx [-a|-ad ...] -q reads.fa -o self.b6 -m FORAGE -i ... [-fr] --chimeras PREFIX [--chimera-sizes] [--chimera-skew S]
+ *             [--chimera-min-seg G] [--chimera-min-gain D]      de-novo two-parent chimera check of the reads from their self-hits and the hits' paths (bh_chimera.c)
  *   ... -q / -o or --samples ... --variants PREFIX [--variants-min-depth N] [--variants-min-alt N] [--variants-reads all|unique]   variant sites per sample (bh_pile.c)
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
@@ -336,6 +338,13 @@ static void usage(void) {
 	puts("                  lines they print against each other: the reads in the order of their weight (1, or with --cluster-sizes the N of a trailing");
 	puts("                  ;size=N of the name), ties in file order; a read with a line to an earlier centroid joins the one with the fewest edits, any");
 	puts("                  other read is a centroid.  Leaves <prefix>clusters.txt (per read) and <prefix>cluster_sizes.txt (per centroid)");
+	puts("--chimeras <prefix> [--chimera-sizes] [--chimera-skew S] [--chimera-min-seg G] [--chimera-min-gain D]: with -q reads -r the same reads -m FORAGE, a de-novo");
+	puts("                  two-parent chimera check.  Weights and priority as in --cluster (--chimera-sizes: the N of a trailing ;size=N).  A candidate parent");
+	puts("                  of a read weighs at least S (2) times as much; per (read, parent) the line with the fewest edits counts, the first among equals.");
+	puts("                  The edit positions of its alignment path, in read orientation, give for every cut c in [G, length - G] (G = 16) the edits left");
+	puts("                  (positions <= 2c in doubled coordinates) and right of it.  Model = the smallest sum over the cuts of the fewest edits left over all");
+	puts("                  parents and the fewest right (ties: higher priority, smaller cut); Single = the fewest edits of one line.  Role Y when");
+	puts("                  Single - Model >= D (3), else N; - = not evaluated (fewer than two parents with a line, or no cut).  Leaves <prefix>chimeras.txt");
 	puts("--host-acx: build accelerators (-d ... -a, --make-acx) with the host builder instead of the device");
 }
 
@@ -355,6 +364,7 @@ int main(int argc, char **argv) {
 	const char *var_prefix = 0; uint32_t var_min_depth = 4, var_min_alt = 2; int var_unique = 0, var_opts_given = 0;
 	const char *mates_FN = 0; BhMatesOpts mopts = {BHIP_MATES_FR, 0, 1000, BHIP_MATES_ALL}; int mates_opts_given = 0;
 	const char *clu_prefix = 0; int clu_sizes = 0;
+	const char *chi_prefix = 0; int chi_sizes = 0, chi_opts_given = 0; uint32_t chi_skew = 2, chi_min_seg = 16, chi_min_gain = 3;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
 	BhTaxOpts txo; memset(&txo, 0, sizeof txo); txo.taxacut = 10;   /* burst.c:92 */
 	setenv("GPU_MAX_HW_QUEUES", "8", 0);      /* HIP runtime: hardware queues for the library's four streams (read when the runtime starts) */
@@ -418,6 +428,15 @@ int main(int argc, char **argv) {
 		else if (!strcmp(a, "--cigar")) cigar = 1;
 		else if (!strcmp(a, "--cluster")) { NEEDARG("--cluster"); clu_prefix = argv[i]; }
 		else if (!strcmp(a, "--cluster-sizes")) clu_sizes = 1;
+		else if (!strcmp(a, "--chimeras")) { NEEDARG("--chimeras"); chi_prefix = argv[i]; }
+		else if (!strcmp(a, "--chimera-sizes")) { chi_sizes = 1; chi_opts_given = 1; }
+		else if (!strcmp(a, "--chimera-skew") || !strcmp(a, "--chimera-min-seg") || !strcmp(a, "--chimera-min-gain")) {
+			NEEDARG(a);
+			char *end = NULL; const unsigned long long v = strtoull(argv[i], &end, 10);
+			if (!*argv[i] || *argv[i] == '-' || *end || !v || v > 0x7FFFFFFFull) { printf("ERROR: %s takes a number 1 .. 2147483647\n", a); return 1; }
+			if (!strcmp(a, "--chimera-skew")) chi_skew = (uint32_t)v; else if (!strcmp(a, "--chimera-min-seg")) chi_min_seg = (uint32_t)v; else chi_min_gain = (uint32_t)v;
+			chi_opts_given = 1;
+		}
 		else if (!strcmp(a, "--variants")) { NEEDARG("--variants"); var_prefix = argv[i]; }
 		else if (!strcmp(a, "--variants-min-depth") || !strcmp(a, "--variants-min-alt")) {
 			const int is_alt = !strcmp(a, "--variants-min-alt");
@@ -540,6 +559,15 @@ int main(int argc, char **argv) {
 	if (clu_prefix && (shard_db || n_shards)) { puts("ERROR: --cluster needs the whole report on rank 0: it does not go with --shard db or --shards"); return 1; }
 	if (clu_prefix && !gather_host) { puts("ERROR: --cluster takes the host gather only (drop --gather rccl)"); return 1; }
 	if (clu_prefix && (cov_prefix || em_prefix || var_prefix)) { puts("ERROR: --cluster does not go with --coverage, --abundance or --variants: per-reference tables of a self-alignment are out of scope"); return 1; }
+	/* (--chimeras works from the same lines as --cluster, and from their paths: the same refusals, before a device is touched) */
+	if (chi_opts_given && !chi_prefix) { puts("ERROR: --chimera-sizes, --chimera-skew, --chimera-min-seg and --chimera-min-gain go with --chimeras <prefix>"); return 1; }
+	if (chi_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --chimeras works from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (chi_prefix && mode != BH_FORAGE) { puts("ERROR: --chimeras needs every relationship under the identity cutoff: run it with -m FORAGE (the other modes discard them)"); return 1; }
+	if (chi_prefix && samples_FN) { puts("ERROR: --chimeras takes one query file aligned against itself: it does not go with --samples"); return 1; }
+	if (chi_prefix && mates_FN) { puts("ERROR: --chimeras takes one query file aligned against itself: it does not go with --mates"); return 1; }
+	if (chi_prefix && (shard_db || n_shards)) { puts("ERROR: --chimeras needs the whole report on rank 0: it does not go with --shard db or --shards"); return 1; }
+	if (chi_prefix && !gather_host) { puts("ERROR: --chimeras takes the host gather only (drop --gather rccl)"); return 1; }
+	if (chi_prefix && (cov_prefix || em_prefix || var_prefix)) { puts("ERROR: --chimeras does not go with --coverage, --abundance or --variants: per-reference tables of a self-alignment are out of scope"); return 1; }
 	if (mates_opts_given && mopts.ins_min > mopts.ins_max) { puts("ERROR: --insert-min is larger than --insert-max"); return 1; }
 	if (mates_opts_given && !mates_FN && !samples_FN) { puts("ERROR: --insert-min, --insert-max, --mates-orientation and --mates-report go with --mates"); return 1; }
 	if (mates_FN) {
@@ -824,7 +852,7 @@ int main(int argc, char **argv) {
 	setvbuf(output, NULL, _IOFBF, 1 << 22);
 	BhPlaceSink sink; memset(&sink, 0, sizeof sink);
 	BhPaths *paths = NULL;
-	if ((cigar || var_prefix) && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
+	if ((cigar || var_prefix || chi_prefix) && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
 	BhPile *pile = NULL;      /* a study of one sample; opened here: its temporary file exists from now until it is renamed or the object is closed */
 	#define DIEP(rc) do { bh_pile_close(pile); DIE(rc); } while (0)
 	if (var_prefix) {
@@ -835,6 +863,11 @@ int main(int argc, char **argv) {
 	BhCluster *clu = NULL;
 	if (clu_prefix && (rc = bh_cluster_open(clu_prefix, clu_sizes, &clu))) DIE(rc);
 	sink.want_re = clu != NULL;
+	BhChimera *chi = NULL;      /* its lines come from the traced groups of the report: a usage error -- two reads of one name -- ends the run before it */
+	if (chi_prefix) {
+		if ((rc = bh_chimera_open(chi_prefix, chi_sizes, chi_skew, chi_min_seg, chi_min_gain, &chi)) || (rc = bh_chimera_begin(chi, &db, &Q))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
+		bh_paths_set_chimera(paths, chi, cigar);
+	}
 	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em || clu ? &sink : NULL, paths))) DIEP(rc);
 	if (fclose(output)) { fprintf(stderr, "ERROR: write failed: %s\n", output_FN); return 2; }      /* (the last buffer of the report: a full disk must not end in exit code 0) */
 	printf("Wrote %lu alignments\n", (unsigned long)lines);
@@ -865,13 +898,19 @@ int main(int argc, char **argv) {
 		printf("Cluster tables written: %sclusters.txt, %scluster_sizes.txt\n", clu_prefix, clu_prefix);
 		PHASE("clusters");
 	}
+	if (chi) {      /* the reads checked from the lines just printed and their paths (rank 0's handle) */
+		if ((rc = bh_chimera_solve(chi, hhs[0])) || (rc = bh_chimera_write(chi))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
+		bh_chimera_print_info(chi);
+		printf("Chimera table written: %schimeras.txt\n", chi_prefix);
+		PHASE("chimera check");
+	}
 	printf("\nAlignment time: %f seconds\n", wall() - start);
 	fflush(NULL);
 	/* The job is done and its output is on disk.  Unpinning and unmapping tens of gigabytes one table after the other took about a
 	 * second for a 32 M-read job; the operating system releases a finished process's memory (host and device) far faster.
 	 * BURST_HOST_TEARDOWN=1 walks through the orderly release instead (leak checks). */
 	if (!getenv("BURST_HOST_TEARDOWN")) _exit(0);
-	bh_cov_close(cov); bh_em_close(em); bh_cluster_close(clu); free(sink.lines); free(sink.uq); free(sink.re); bh_paths_close(paths);
+	bh_cov_close(cov); bh_em_close(em); bh_cluster_close(clu); bh_chimera_close(chi); free(sink.lines); free(sink.uq); free(sink.re); bh_paths_close(paths);
 	if (comm) bhip_comm_destroy(comm);
 	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
 	for (int r = 0; r < n_gpus; ++r) bh_run_free(&ranks[r].run);

@@ -302,6 +302,28 @@ def lib():
         L.bh_cluster_close.restype = None
         L.bh_cluster_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bh_session_set_cluster.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_chimera_open.argtypes = [C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.bh_chimera_set_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_chimera_set_solver.restype = None
+        L.bh_chimera_names.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32]
+        L.bh_chimera_line.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_uint32]
+        L.bh_chimera_add_b6.argtypes = [C.c_void_p, C.c_char_p]
+        L.bh_chimera_solve.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_chimera_reads.argtypes = [C.c_void_p]
+        L.bh_chimera_reads.restype = C.c_uint32
+        L.bh_chimera_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_chimera_last_info.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.bh_chimera_last_info.restype = None
+        L.bh_chimera_write.argtypes = [C.c_void_p]
+        L.bh_chimera_print_info.argtypes = [C.c_void_p]
+        L.bh_chimera_print_info.restype = None
+        L.bh_chimera_abort.argtypes = [C.c_void_p]
+        L.bh_chimera_abort.restype = None
+        L.bh_chimera_close.argtypes = [C.c_void_p]
+        L.bh_chimera_close.restype = None
+        L.bh_chimera_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_void_p]
+        L.bh_session_set_chimera.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_session_set_variants.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_session_set_variants.restype = None
         _lib = L
@@ -402,6 +424,87 @@ def _cluster_info(h):
     info, lines, foreign = np.zeros(8, np.uint64), C.c_uint64(), C.c_uint64()
     lib().bh_cluster_last_info(h, info.ctypes.data, C.byref(lines), C.byref(foreign))
     d = dict(zip(capi.CLUSTER_INFO, (int(x) for x in info)))
+    d["lines"], d["foreign"] = lines.value, foreign.value
+    return d
+
+
+def chimera_host(weights, lens, lines, ops, skew=2, min_seg=16, min_gain=3):
+    """bh_chimera_host, the chimera check's definition in plain sequential C (no device): (rows capi.CHIMERA_DTYPE [n], info uint64 [8]: pairs
+    kept, evaluated, chimeric, 0, 0, raw lines, nodes, 0).  weights, lens: uint32 per read; lines: capi.CHIM_LINE_DTYPE or rows (q, r, flags,
+    n_ops, op_off); ops: uint32 words length << 4 | code"""
+    weights = np.ascontiguousarray(weights, dtype=np.uint32)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    lines = capi.chim_lines(lines)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    n = len(weights)
+    if len(lens) != n:
+        raise ValueError("chimera_host: one length per weight")
+    out, info = np.zeros(max(n, 1), capi.CHIMERA_DTYPE), np.zeros(8, np.uint64)
+    _chk(lib().bh_chimera_host(None, n, weights.ctypes.data, lens.ctypes.data, lines.ctypes.data, len(lines), ops.ctypes.data, len(ops), int(skew), int(min_seg),
+                               int(min_gain), out.ctypes.data, info.ctypes.data))
+    return out[:n], info
+
+
+class ChimeraChecker:
+    """bh_chimera.c without a run: the reads' names and lengths, lines (or a .b6 file written with --cigar), one solve, the table
+    prefix + chimeras.txt.  device: a capi.Device whose handle computes the profiles; None: bh_chimera_host (no device)"""
+
+    def __init__(self, prefix, names, lens, sizes=False, skew=2, min_seg=16, min_gain=3, device=None):
+        self.h, self.device = C.c_void_p(), device
+        _chk(lib().bh_chimera_open(prefix.encode(), int(sizes), int(skew), int(min_seg), int(min_gain), C.byref(self.h)))
+        if device is None:
+            lib().bh_chimera_set_solver(self.h, C.cast(lib().bh_chimera_host, C.c_void_p), None)
+        try:
+            arr = (C.c_char_p * max(len(names), 1))(*[n.encode() if isinstance(n, str) else n for n in names])
+            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+            if len(lens) != len(names):
+                raise ValueError("ChimeraChecker: one length per name")
+            _chk(lib().bh_chimera_names(self.h, arr, lens.ctypes.data, len(names)))
+        except Exception:
+            self.close()
+            raise
+
+    def line(self, q, ref_name, reverse, ops):
+        ref_name = ref_name.encode() if isinstance(ref_name, str) else ref_name
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        _chk(lib().bh_chimera_line(self.h, int(q), ref_name, len(ref_name), int(bool(reverse)), ops.ctypes.data, len(ops)))
+
+    def add_b6(self, path):
+        _chk(lib().bh_chimera_add_b6(self.h, path.encode()))
+
+    def solve(self):
+        _chk(lib().bh_chimera_solve(self.h, self.device._h if self.device is not None else None))
+        return _chimera_result(self.h)
+
+    def info(self):
+        return _chimera_info(self.h)
+
+    def write(self):
+        _chk(lib().bh_chimera_write(self.h))
+
+    def close(self):
+        if self.h:
+            lib().bh_chimera_close(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _chimera_result(h):
+    n = lib().bh_chimera_reads(h)
+    out = np.zeros(max(n, 1), capi.CHIMERA_DTYPE)
+    _chk(lib().bh_chimera_result(h, out.ctypes.data, None))
+    return out[:n]
+
+
+def _chimera_info(h):
+    info, lines, foreign = np.zeros(8, np.uint64), C.c_uint64(), C.c_uint64()
+    lib().bh_chimera_last_info(h, info.ctypes.data, C.byref(lines), C.byref(foreign))
+    d = dict(zip(capi.CHIMERA_INFO, (int(x) for x in info)))
     d["lines"], d["foreign"] = lines.value, foreign.value
     return d
 
@@ -776,7 +879,8 @@ class Session:
                  mates_orientation="fr", insert_min=0, insert_max=1000, mates_report="all", mates_join=None,
                  abundance=None, abundance_iters=1000, abundance_tol=1024, abundance_host=False,
                  variants=None, variants_min_depth=4, variants_min_alt=2, variants_reads="all", variants_host=False,
-                 cluster=None, cluster_sizes=False, cluster_host=False):
+                 cluster=None, cluster_sizes=False, cluster_host=False,
+                 chimeras=None, chimera_sizes=False, chimera_skew=2, chimera_min_seg=16, chimera_min_gain=3, chimera_host=False):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
         reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
         process only).
@@ -796,10 +900,15 @@ class Session:
         cluster = prefix: every reported sample -- meant for ONE, the reads of the database's own FASTA, mode FORAGE -- has its reads clustered
         from the lines it prints (bh_cluster.c: greedy centroid clusters; cluster_sizes: weights from `;size=N` suffixes), resolved on rank
         0's device handle -- or by bh_cluster_host with cluster_host=True -- and prefix{clusters,cluster_sizes}.txt written at once;
-        clusters() returns (centroid, edits) per read of the last sample.  FORAGE only; not with shard_db, mates, coverage, abundance, variants."""
+        clusters() returns (centroid, edits) per read of the last sample.  FORAGE only; not with shard_db, mates, coverage, abundance, variants.
+        chimeras = prefix: every reported sample -- meant for ONE, the reads of the database's own FASTA, mode FORAGE -- has its reads checked
+        for two-parent chimeras from the lines it prints and their alignment paths (bh_chimera.c; chimera_sizes: weights from `;size=N`
+        suffixes; chimera_skew, chimera_min_seg, chimera_min_gain: S, G and D of the definition), on rank 0's device handle -- or by
+        bh_chimera_host with chimera_host=True -- and prefix + chimeras.txt written at once; chimeras() returns the rows of the last sample.
+        Opens the path tracer without adding the cigar columns.  Same limits as cluster, and it goes with cluster."""
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
         self._mates_join = mates_join
-        self.cov, self.em, self.pile, self.cluster = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.cov, self.em, self.pile, self.cluster, self.chimera = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         devs = list(devs) if isinstance(devs, (list, tuple)) else [devs]
         n_local = len(devs)
         world = world or n_local
@@ -876,9 +985,21 @@ class Session:
             _chk(lib().bh_cluster_open(cluster.encode(), int(bool(cluster_sizes)), C.byref(self.cluster)))
             if cluster_host:
                 lib().bh_cluster_set_solver(self.cluster, C.cast(lib().bh_cluster_host, C.c_void_p), None)
+        if chimeras is not None:
+            if mode != "FORAGE":
+                raise ValueError("chimeras: needs every relationship under the identity cutoff: mode FORAGE")
+            if (shard_db and int(shard_db) > 1) or align is not None or world != n_local:
+                raise ValueError("chimeras: needs the whole report and the device handles of one process (no shard_db, no align back end, no job of processes)")
+            if coverage is not None or abundance is not None or variants is not None:
+                raise ValueError("chimeras: per-reference tables of a self-alignment are out of scope (no coverage, abundance, variants)")
+            _chk(lib().bh_chimera_open(chimeras.encode(), int(bool(chimera_sizes)), int(chimera_skew), int(chimera_min_seg), int(chimera_min_gain), C.byref(self.chimera)))
+            if chimera_host:
+                lib().bh_chimera_set_solver(self.chimera, C.cast(lib().bh_chimera_host, C.c_void_p), None)
         _chk(lib().bh_session_open(C.byref(db.c), self.ranks, n_local, world, comm, node.h if node is not None else None, C.byref(o), C.byref(self.h)))
         if self.cluster:
             _chk(lib().bh_session_set_cluster(self.h, self.cluster))
+        if self.chimera:
+            _chk(lib().bh_session_set_chimera(self.h, self.chimera))
 
     def _align_cb(self, align):
         def _align(ctx, q, u0, u1, n, mode, batch, run):
@@ -1039,6 +1160,17 @@ class Session:
         """the last clustering's figures: rounds, edges_kept, centroids, device_us, device_bytes, edges, nodes, lines, foreign"""
         return _cluster_info(self.cluster)
 
+    def chimeras(self):
+        """the last sample's chimera check: a capi.CHIMERA_DTYPE row per read in file order (role 0 not evaluated, 1 N, 2 Y)"""
+        if not self.chimera:
+            raise HostError("the session has no chimera check")
+        return _chimera_result(self.chimera)
+
+    def chimeras_info(self):
+        """the last chimera check's figures: pairs_kept, evaluated, chimeric, device_us, device_bytes, lines (given to the device), nodes,
+        lines (printed), foreign"""
+        return _chimera_info(self.chimera)
+
     def coverage_abort(self):
         """the walk ends on an error that the session itself has not seen (another rank's): close() writes no tables"""
         if self.cov:
@@ -1072,6 +1204,9 @@ class Session:
             if self.cluster:      # (its tables were written when the sample was reported)
                 lib().bh_cluster_close(self.cluster)
                 self.cluster = C.c_void_p()
+            if self.chimera:      # (likewise)
+                lib().bh_chimera_close(self.chimera)
+                self.chimera = C.c_void_p()
             lib().bh_session_close(self.h)
             self.h = C.c_void_p()
             for i in range(len(self.ranks)):

@@ -215,7 +215,15 @@ def main(argv=None):
     ap.add_argument("--variants", metavar="PREFIX", help="not available here: the variants table is written by burst_hip --variants (one process, the host gather)")
     ap.add_argument("--cluster", metavar="PREFIX", help="not available here: reads are clustered by burst_hip --cluster (one process, the host gather)")
     ap.add_argument("--cluster-sizes", action="store_true", help="not available here: goes with burst_hip --cluster")
+    ap.add_argument("--chimeras", metavar="PREFIX", help="not available here: reads are checked for chimeras by burst_hip --chimeras (one process, the host gather)")
+    ap.add_argument("--chimera-sizes", action="store_true", help="not available here: goes with burst_hip --chimeras")
+    ap.add_argument("--chimera-skew", metavar="S", help="not available here: goes with burst_hip --chimeras")
+    ap.add_argument("--chimera-min-seg", metavar="G", help="not available here: goes with burst_hip --chimeras")
+    ap.add_argument("--chimera-min-gain", metavar="D", help="not available here: goes with burst_hip --chimeras")
     args = ap.parse_args(argv)
+    if args.chimeras or args.chimera_sizes or args.chimera_skew or args.chimera_min_seg or args.chimera_min_gain:      # (exit code 1, as burst_hip refuses what it cannot do)
+        print("ERROR: --chimeras is not available in python -m burst_amd.run: use burst_hip --chimeras (one process, --gpus N with the host gather)", flush=True)
+        return 1
     if args.cluster or args.cluster_sizes:      # (exit code 1, as burst_hip refuses what it cannot do)
         print("ERROR: --cluster is not available in python -m burst_amd.run: use burst_hip --cluster (one process, --gpus N with the host gather)", flush=True)
         return 1

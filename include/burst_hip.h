@@ -470,6 +470,44 @@ BHIP_API int bhip_cluster_run(void *handle, uint32_t n_nodes, const uint32_t *we
                               uint32_t *centroid_out, uint32_t *edits_out);
 BHIP_API int bhip_cluster_info(void *handle, uint64_t info[8]);
 
+/* Chimera check: a de-novo two-parent test of the reads of a query file from the lines it prints against itself and their alignment
+ * paths (burst_hip --chimeras; no reference counterpart: the definition is this project's own).  All of it is integer arithmetic,
+ * bit-exact on any machine.  S, G and D below are policy, not measurements.
+ *   NODES     as in the clustering: the reads of the -q file in file order, weight 1 or (--chimera-sizes) the N of a trailing `;size=N[;]`;
+ *             len[q] = the read's number of symbols.  PRIORITY as there: the larger weight first, then the smaller number; rank[r] = r's place.
+ *   PARENT    r is a CANDIDATE PARENT of q when r != q and weight[r] >= S * weight[q] (64-bit product; S = skew, --chimera-skew, default 2).
+ *   LINE      of q towards r: a printed line whose column 1 is read q and whose column 2 is byte-equal to the name of a candidate parent
+ *             r.  Per (q, r) one line counts: the one with the smallest column 11, the one printed first among equals.  A line whose
+ *             column 2 names no read is FOREIGN (ignored, counted); self lines and lines towards non-candidates are ignored.
+ *   EDITS     of a line, in read orientation and DOUBLED coordinates: walk the line's path (the ops --cigar prints), j = query symbols
+ *             consumed so far: a symbol of an X or I gives position 2j + 1, then j++; a column of a D gives position 2j; '=' advances
+ *             j.  The path of a reverse line (column 9 > column 10) is that of the reverse-complement entry: each position p becomes
+ *             2 len[q] - p.  E = the number of positions = column 11.
+ *   CUT       c splits the read into [0, c) and [c, len): L[c] = the positions <= 2c, R[c] = E - L[c] (a D exactly at the cut is left, in
+ *             both orientations).  The cuts of q are c in [G, len[q] - G] (G = min_seg, --chimera-min-seg, default 16).
+ *   ROLE      q is NOT EVALUATED (role 0, `-`) with fewer than two candidate parents with a line, or without a cut.  Otherwise
+ *             single = the smallest E over its lines; bestL[c], bestR[c] = the smallest packed keys L[c] << 32 | rank[r] and
+ *             R[c] << 32 | rank[r] over its lines; Model[c] = the sum of their two edit parts; cut = the smallest c with the smallest
+ *             Model[c], model = that value; parent a and ea from bestL[cut], parent b and eb from bestR[cut].  Role 2 (`Y`, chimeric)
+ *             when single - model >= D (D = min_gain, --chimera-min-gain, default 3), else role 1 (`N`).  With one line per (q, r) and
+ *             D >= 1 a `Y` always has a != b (a == b would make model = that line's E >= single).
+ * Out of scope: parents that are flagged themselves are not excluded; three-way chimeras; segments are not aligned afresh (the profile is
+ * that of the end-to-end paths printed).
+ * bhip_chimera_run takes the lines raw -- self lines, lines towards non-candidates and repeated (q, r) included; the device drops them --
+ * with their paths as bhip_trace_paths writes them (ops[op_off .. op_off + n_ops), words length << 4 | code).  BHIP_E_ARG with a text, before
+ * any device memory is touched and with the handle staying usable: a line that names a node >= n_nodes, ops that leave `ops`, a word that
+ * is not a run of I/D/=/X of length >= 1, ops that consume ('=' + X + I) another number of symbols than len[q], len[q] of 0 or above
+ * BHIP_MAX_QLEN, more than 254 edits, n_lines >= 2^32, n_nodes = 2^32 - 1, skew, min_seg or min_gain of 0.  n_lines == 0 launches
+ * nothing: every role is 0.  out[q] of a role 0 is all zeros.  The call leaves nothing resident but scratch buffers of the handle
+ * (csrc/bhip_chimera.hip, DESIGN.md section 7f: one wave per read).
+ * bhip_chimera_info, of the last bhip_chimera_run on the handle: [0] (q, r) pairs kept, [1] reads evaluated, [2] chimeric reads, [3]
+ * device microseconds (HIP events around everything launched), [4] device bytes of the scratch buffers, [5] raw lines, [6] nodes, [7] 0. */
+typedef struct BhipChimLine { uint32_t q, r, flags /* bit 0: reverse */, n_ops; uint64_t op_off; } BhipChimLine;
+typedef struct BhipChimera  { uint32_t role /* 0 '-', 1 'N', 2 'Y' */, single, model, cut, a, ea, b, eb; } BhipChimera;
+BHIP_API int bhip_chimera_run(void *handle, uint32_t n_nodes, const uint32_t *weights, const uint32_t *len, const BhipChimLine *lines, uint64_t n_lines,
+                              const uint32_t *ops, uint64_t n_ops, uint32_t skew, uint32_t min_seg, uint32_t min_gain, BhipChimera *out /* [n_nodes] */);
+BHIP_API int bhip_chimera_info(void *handle, uint64_t info[8]);
+
 /* Tuning knobs.  "prefilter_stride": 0 (default) = automatic sparse seeds -- per query the largest stride s <= K for
  * which an alignment within budget still keeps >= 3 of the words starting at 0, s, 2s, ... (one edit destroys at most
  * ceil(K/s) of them), fewest .acx look-ups with the same no-false-negative guarantee; s >= 1 forces every s-th word,
