@@ -49,7 +49,7 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
            "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_pile_run",
-           "bhip_cluster_run", "bhip_cluster_info", "bhip_chimera_run", "bhip_chimera_info"]
+           "bhip_cluster_run", "bhip_cluster_info", "bhip_chimera_run", "bhip_chimera_info", "bhip_md_tags"]
 
 # BhipMateLine, 20 bytes: pair and header numbers, .b6 columns 9 and 10 (signed), column 11
 MATE_LINE_DTYPE = np.dtype([("pair", "<u4"), ("ref", "<u4"), ("st", "<i4"), ("ed", "<i4"), ("edits", "<u4")])
@@ -88,6 +88,7 @@ PILE_LINE_DTYPE = np.dtype({"names": ["q", "refIx", "ref_first", "header", "pos"
 PILE_SITE_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("ref", "<u4"), ("depth", "<u4"), ("n", "<u4", (6,)), ("ins", "<u4")])
 assert PILE_LINE_DTYPE.itemsize == 40 and PILE_SITE_DTYPE.itemsize == 44
 PILE_INFO = ("events", "candidates", "sites", "device_us", "peak_bytes")
+MD_INFO = ("device_us", "requests", "md_bytes", "peak_bytes")
 
 # BhipClusterEdge, 12 bytes: read q has a printed line against read r with this many edits (bhip_cluster_run)
 CLUSTER_EDGE_DTYPE = np.dtype([("q", "<u4"), ("r", "<u4"), ("edits", "<u4")])
@@ -269,6 +270,8 @@ def _load():
     lib.bhip_chimera_run.restype = i32
     lib.bhip_chimera_info.argtypes = [vp, vp]
     lib.bhip_chimera_info.restype = i32
+    lib.bhip_md_tags.argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, vp]
+    lib.bhip_md_tags.restype = i32
     for f in (lib.bhip_cov_begin, lib.bhip_cov_add, lib.bhip_cov_sample_stats, lib.bhip_cov_dataset_stats, lib.bhip_cov_info, lib.bhip_cov_end, lib.bhip_lane_extents):
         f.restype = i32
     return lib
@@ -582,6 +585,37 @@ class Device:
         info = np.zeros(8, np.uint64)
         _chk(lib().bhip_chimera_info(self._h, _ptr(info)))
         return dict(zip(CHIMERA_INFO, (int(x) for x in info)))
+
+    def md_tags(self, requests, ref_first, op_off, ops, cap=None):
+        """MD strings and NM counts of alignment paths (bhip_md_tags).  requests, ref_first, op_off, ops: what trace_paths took and returned
+        (PATH_REQ_DTYPE array or rows q, refIx, finalPos, ed; request i owns ops[op_off[i]:op_off[i + 1]]).  Returns (md uint8 bytes,
+        md_off uint64 [n + 1], nm uint32 [n]): request i owns md[md_off[i]:md_off[i + 1]]; md_info() has the call's figures.  cap: room
+        offered at first (default: 4 bytes per request and op); a capacity answer is retried once with the wanted room"""
+        if not (isinstance(requests, np.ndarray) and requests.dtype == PATH_REQ_DTYPE):
+            rows = np.asarray(requests, dtype=np.uint32).reshape(-1, 4)
+            requests = np.zeros(len(rows), PATH_REQ_DTYPE)
+            for k, name in enumerate(("q", "refIx", "finalPos", "ed")):
+                requests[name] = rows[:, k]
+        requests = np.ascontiguousarray(requests)
+        n = len(requests)
+        ref_first, op_off, ops = _arr(ref_first, np.uint32), _arr(op_off, np.uint64), _arr(ops, np.uint32)
+        if len(ref_first) < n or len(op_off) != n + 1:
+            raise ValueError("md_tags: one ref_first per request, n + 1 offsets")
+        cap = 4 * (n + len(ops)) + 16 if cap is None else int(cap)
+        md_off, nm, info = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint32), np.zeros(8, np.uint64)
+        for _ in range(2):
+            md = np.zeros(max(cap, 1), np.uint8)
+            rc = lib().bhip_md_tags(self._h, _ptr(requests), _ptr(ref_first), _ptr(op_off), _ptr(ops), n, _ptr(md), cap, _ptr(md_off), _ptr(nm), _ptr(info))
+            if rc != BHIP_E_CAPACITY or int(md_off[n]) <= cap:
+                break
+            cap = int(md_off[n])
+        self._md_info = dict(zip(MD_INFO, (int(x) for x in info)))
+        _chk(rc)
+        return md[:int(md_off[n])], md_off, nm[:n]
+
+    def md_info(self):
+        """the last md_tags call's figures: device_us, requests, md_bytes, peak_bytes"""
+        return dict(getattr(self, "_md_info", dict.fromkeys(MD_INFO, 0)))
 
     def pile_info(self):
         """the last pile_run's figures: events, candidates, sites, device_us, peak_bytes"""

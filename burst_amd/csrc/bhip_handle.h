@@ -456,6 +456,7 @@ struct Handle {
 	uint64_t cluster_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // bhip_cluster_info: the figures of the last bhip_cluster_run
 	void *chimera = nullptr;      // scratch buffers and events of bhip_chimera_run (bhip_chimera.hip), made by the first call that launches
 	uint64_t chimera_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // bhip_chimera_info: the figures of the last bhip_chimera_run
+	void *md = nullptr;           // scratch buffers and events of bhip_md_tags (bhip_md.hip), made by the first call that launches
 	int opt_em_weak_hash = 0;     // 1 = candidate sets hashed to two bits: the element-by-element comparison decides which groups merge (tests)
 	int opt_em_thread_max = 0, opt_em_wave_max = 0;   // largest candidate set a thread / a wave takes in the abundance step (0 = EM_THREAD_MAX, EM_WAVE_MAX of bhip_em.hip)
 	long long opt_cov_event_cap = 0;   // bytes the coverage event sets may take before they are compacted (0 = a fifth of the memory free at the first bhip_cov_add)
@@ -479,4 +480,5 @@ void bhip_em_release(Handle *h);                                             // 
 void bhip_pile_release(Handle *h);                                           // bhip_pile.hip
 void bhip_cluster_release(Handle *h);                                        // bhip_cluster.hip
 void bhip_chimera_release(Handle *h);                                        // bhip_chimera.hip
+void bhip_md_release(Handle *h);                                             // bhip_md.hip
 #endif

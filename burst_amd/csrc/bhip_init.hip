@@ -77,6 +77,7 @@ extern "C" void bhip_destroy(void *handle) {
 	bhip_pile_release(h);
 	bhip_cluster_release(h);
 	bhip_chimera_release(h);
+	bhip_md_release(h);
 	if (h->hsc_pinned) (void)hipHostFree(h->hsc_pinned);
 	if (h->nsel_pinned) (void)hipHostFree(h->nsel_pinned);
 	for (Lane *L : h->lanes) lane_destroy(L);

@@ -78,7 +78,9 @@ static int lenrec_cmp(const void *a, const void *b) {
 	const int c = memcmp(x->s, y->s, x->n < y->n ? x->n : y->n);
 	return c ? c : (x->n > y->n) - (x->n < y->n);
 }
-static int read_lengths(BhCov *cv, const char *file) {
+/* the table `name<TAB>length` of `file` looked up for every header: len[h] of heads[h]; `flag` names the option in the texts (--sam-lengths
+ * reads the same table through here) */
+int bh_cov_read_lengths(const char *file, const char *flag, uint32_t n_headers, const char *const *heads, uint32_t *len) {
 	FILE *f = fopen(file, "rb");
 	if (!f) return bh_set_error(BH_E_IO, "ERROR: Cannot open the lengths table: %s", file);
 	fseek(f, 0, SEEK_END);
@@ -109,14 +111,26 @@ static int read_lengths(BhCov *cv, const char *file) {
 	}
 	if (!rc) {
 		qsort(R, n, sizeof(*R), lenrec_cmp);
-		for (uint32_t h = 0; h < cv->nH && !rc; ++h) {
-			const LenRec k = {cv->head[h], strlen(cv->head[h]), 0};
+		for (uint32_t h = 0; h < n_headers && !rc; ++h) {
+			const LenRec k = {heads[h], strlen(heads[h]), 0};
 			const LenRec *m = n ? bsearch(&k, R, n, sizeof(*R), lenrec_cmp) : NULL;
-			if (!m) rc = bh_set_error(BH_E_USAGE, "ERROR: --coverage-lengths %s has no length for reference '%s'", file, cv->head[h]);
-			else cv->len[h] = m->len;
+			if (!m) rc = bh_set_error(BH_E_USAGE, "ERROR: %s %s has no length for reference '%s'", flag, file, heads[h]);
+			else len[h] = m->len;
 		}
 	}
 	free(R); free(txt);
+	return rc;
+}
+
+/* the database's own extent of every header: from the lanes resident behind `hip_handle`, or (NULL) from the packed references in host memory */
+int bh_cov_default_lengths(const BhDb *db, void *hip_handle, uint32_t *len) {
+	uint32_t *ext = calloc((size_t)db->numRclumps * 16 + 1, 4);
+	if (!ext) return bh_set_error(BH_E_OOM, "OOM:coverage");
+	int rc = BH_OK;
+	if (!hip_handle) bh_cov_extents_host(db, ext);
+	else if (bhip_lane_extents(hip_handle, ext)) rc = bh_set_error(BH_E_DEVICE, "coverage: lane extents: %s", bhip_last_error());
+	if (!rc) rc = bh_cov_lengths_from_extents(db, ext, len);
+	free(ext);
 	return rc;
 }
 
@@ -134,7 +148,7 @@ int bh_cov_open(const BhDb *db, const char *prefix, const char *lengths_file, ui
 	for (uint32_t i = 0; i < db->origTotR; ++i) if (db->refMap[i] < cv->nH) cv->head[db->refMap[i]] = db->refHead[i];
 	for (uint32_t h = 0; h < cv->nH; ++h) if (!cv->head[h]) cv->head[h] = "";
 	if (lengths_file) {
-		const int rc = read_lengths(cv, lengths_file);
+		const int rc = bh_cov_read_lengths(lengths_file, "--coverage-lengths", cv->nH, cv->head, cv->len);
 		if (rc) { bh_cov_close(cv); return rc; }
 		cv->have_len = 1;
 	}
@@ -153,11 +167,7 @@ const uint32_t *bh_cov_lengths(const BhCov *cv) { return cv && cv->have_len ? cv
 /* the default lengths without a device: for runs in which no one handle holds the whole database (--shard db) */
 int bh_cov_lengths_host(BhCov *cv) {
 	if (!cv || cv->have_len) return BH_OK;
-	uint32_t *ext = calloc((size_t)cv->db->numRclumps * 16 + 1, 4);
-	if (!ext) return bh_set_error(BH_E_OOM, "OOM:coverage");
-	bh_cov_extents_host(cv->db, ext);
-	const int rc = bh_cov_lengths_from_extents(cv->db, ext, cv->len);
-	free(ext);
+	const int rc = bh_cov_default_lengths(cv->db, NULL, cv->len);
 	if (!rc) cv->have_len = 1;
 	return rc;
 }
@@ -195,11 +205,8 @@ int bh_cov_sample(BhCov *cv, void *hh, const char *out_path, const BhipCovLine *
 	if (!hh) { cv->dead = BH_E_DEVICE; return bh_set_error(BH_E_DEVICE, "coverage: the statistics are computed on the device and rank 0 has no device handle"); }
 	if (!cv->begun) {
 		if (!cv->have_len) {      /* the database's own extents */
-			uint32_t *ext = calloc((size_t)cv->db->numRclumps * 16 + 1, 4);
-			if (!ext) return bh_set_error(BH_E_OOM, "OOM:coverage");
-			if (bhip_lane_extents(hh, ext)) { free(ext); return dev_fail(cv, "lane extents"); }
-			rc = bh_cov_lengths_from_extents(cv->db, ext, cv->len);
-			free(ext);
+			rc = bh_cov_default_lengths(cv->db, hh, cv->len);
+			if (rc == BH_E_DEVICE) cv->dead = BH_E_DEVICE;
 			if (rc) return rc;
 			cv->have_len = 1;
 		}

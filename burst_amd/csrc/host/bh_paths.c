@@ -21,7 +21,10 @@ struct BhPaths {
 	BhipPathReq *req; uint32_t *first, *gapr; uint64_t *off; uint64_t reqCap;
 	uint32_t *ops; uint64_t opsCap;
 	char *text; size_t textCap;
-	bh_paths_collect_fn collect; void *collectCtx; int plain;      /* bh_paths_set_collector: who else gets the traced groups; plain = the lines are written without the two columns */
+	/* who else gets the traced groups (bh_paths_set_collector: an entry with fn, bh_paths_add_collector: one with fn_text), in the order
+	 * they were added; plain = the lines are written without the two columns */
+	struct { bh_paths_collect_fn fn; bh_paths_collect_text_fn fn_text; void *ctx; } col[BH_PATHS_MAX_COLLECTORS];
+	int nCol, plain;
 };
 
 static int trace_device(void *ctx, const BhQueries *Q, const BhipPathReq *req, uint64_t n, uint32_t *ops, uint64_t ops_cap, uint64_t *op_off,
@@ -41,7 +44,26 @@ int bh_paths_open(void *hip_handle, BhPaths **out) {
 	return BH_OK;
 }
 void bh_paths_set_trace(BhPaths *p, bh_paths_trace_fn fn, void *ctx) { p->trace = fn; p->ctx = ctx; }
-void bh_paths_set_collector(BhPaths *p, bh_paths_collect_fn fn, void *ctx, int columns) { if (p) { p->collect = fn; p->collectCtx = ctx; p->plain = !columns; } }
+static void col_remove(BhPaths *p, int k) { for (--p->nCol; k < p->nCol; ++k) p->col[k] = p->col[k + 1]; }
+void bh_paths_set_collector(BhPaths *p, bh_paths_collect_fn fn, void *ctx, int columns) {
+	if (!p) return;
+	p->plain = !columns;
+	int k = 0;
+	while (k < p->nCol && !p->col[k].fn) ++k;
+	if (!fn) { if (k < p->nCol) col_remove(p, k); return; }
+	if (k == p->nCol) { if (p->nCol == BH_PATHS_MAX_COLLECTORS) return; ++p->nCol; }      /* (one entry of this kind: the list cannot fill up through here alone) */
+	p->col[k].fn = fn; p->col[k].fn_text = NULL; p->col[k].ctx = ctx;
+}
+int bh_paths_add_collector(BhPaths *p, bh_paths_collect_text_fn fn, void *ctx, int columns) {
+	if (!p || !fn) return bh_set_error(BH_E_USAGE, "bh_paths_add_collector: no tracer / no collector");
+	p->plain = !columns;
+	int k = 0;
+	while (k < p->nCol && p->col[k].fn_text != fn) ++k;
+	if (!ctx) { if (k < p->nCol) col_remove(p, k); return BH_OK; }
+	if (k == p->nCol) { if (p->nCol == BH_PATHS_MAX_COLLECTORS) return bh_set_error(BH_E_USAGE, "bh_paths_add_collector: %d collectors already", p->nCol); ++p->nCol; }
+	p->col[k].fn = NULL; p->col[k].fn_text = fn; p->col[k].ctx = ctx;
+	return BH_OK;
+}
 void bh_paths_totals(const BhPaths *p, uint64_t *requests, uint64_t *ops, uint64_t *lines) {
 	if (requests) *requests = p->nRequests;
 	if (ops) *ops = p->nOps;
@@ -134,7 +156,11 @@ int bh_paths_emit(BhPaths *p, FILE *out, const BhQueries *Q, const BhipHit *hits
 	}
 	if (rc) return rc;
 	p->nRequests += nr; p->nOps += p->off[nr]; p->nLines += nl; ++p->nCalls;
-	if (p->collect && (rc = p->collect(p->collectCtx, p->idx, p->req, p->first, p->off, p->ops, nr, bufs, n_chunks))) return rc;
+	for (int k = 0; k < p->nCol; ++k) {
+		rc = p->col[k].fn ? p->col[k].fn(p->col[k].ctx, p->idx, p->req, p->first, p->off, p->ops, nr, bufs, n_chunks)
+		                  : p->col[k].fn_text(p->col[k].ctx, p->idx, p->req, p->first, p->off, p->ops, nr, bufs, text, text_len, n_chunks);
+		if (rc) return rc;
+	}
 	if (p->plain) {      /* the lines as they were rendered */
 		for (uint64_t c = 0; c < n_chunks; ++c) if (text_len[c] && fwrite(text[c], 1, text_len[c], out) != text_len[c]) return bh_set_error(BH_E_IO, "short write on the output file");
 		return BH_OK;

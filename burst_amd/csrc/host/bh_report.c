@@ -388,7 +388,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 			for (uint32_t k = 0; k < nb; ++k) {
 				const uint64_t i = bi[k]; const uint32_t qlen = Q->len[i];
 				uint32_t st, ed; coords(db, bb[k], brix[k], qlen, &st, &ed);
-				for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[brix[k]], bb[k], qlen, st, ed, i, 0, NULL); PLINE(bb[k], brix[k]); ++lines; }
+				for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) { print_line_tax(out, Q->heads[j], db->refHead[brix[k]], bb[k], qlen, st, ed, i, 0, NULL); PLINE(bb[k], brix[k]); ++lines; }      /* (bh_sam.c's collector takes the read of a line from this order: per unique query the lines of its reads, read after read, the same number for each) */
 				SINK(bb[k], brix[k], st, ed, Q->offset[i + 1] - Q->offset[i], 1);
 			}
 		}
@@ -447,7 +447,7 @@ int bh_report_view_paths(FILE *out, const BhDb *db, const BhQueries *Q, const Bh
 					if (!dupe_hunt(nodupe, RefCache, StCache, &ddix, MAPPED(rix), st, ql2, 1)) { RPcache[rix_ix] = rp; RIXcache[rix_ix++] = rix; }
 				});
 			}
-			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) for (uint64_t zz = 0; zz < rix_ix; ++zz) {
+			for (uint64_t j = Q->offset[i]; j < Q->offset[i + 1]; ++j) for (uint64_t zz = 0; zz < rix_ix; ++zz) {      /* (bh_sam.c's collector takes the read of a line from this order: per unique query the lines of its reads, read after read, the same number for each) */
 				const BhipHit *rp = RPcache[zz]; const uint32_t rix = RIXcache[zz];
 				uint32_t st, ed; coords(db, rp, rix, qlen, &st, &ed);
 				print_line_tax(out, Q->heads[j], db->refHead[rix], rp, qlen, st, ed, i, wt, wt ? bh_tax_lookup(T, db->refHead[rix], ncbi) : NULL); PLINE_U(rp, rix, rix_ix == 1); ++lines;   /* burst.c:4631-4633, 4685-4687 */

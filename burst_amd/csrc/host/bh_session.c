@@ -40,7 +40,8 @@ struct BhSession {
 	BhMates *mates;                 /* bh_session_run_mates: the joiner, made on first use */
 	BhCluster *cluster;             /* bh_session_set_cluster: NULL, or the clustering every reported sample is given */
 	BhChimera *chimera;             /* bh_session_set_chimera: NULL, or the chimera check every reported sample is given */
-	BhPaths *paths;                 /* with o.cigar, o.pile or a chimera check: the tracer on the reporting rank's handle, opened by the first sample that reports */
+	BhSam *sam;                     /* bh_session_set_sam: NULL, or the SAM writer every reported sample is given */
+	BhPaths *paths;                 /* with o.cigar, o.pile, a chimera check or a SAM writer: the tracer on the reporting rank's handle, opened by the first sample that reports */
 	int dead, dbg, threads_ok;
 	int alive;                      /* query tables alive (the current sample's and the prefetched one's) */
 	pthread_mutex_t mu;             /* `alive` and its debug line */
@@ -125,6 +126,12 @@ int bh_session_set_chimera(BhSession *s, BhChimera *ch) {
 	s->chimera = ch;
 	return BH_OK;
 }
+int bh_session_set_sam(BhSession *s, BhSam *sam) {
+	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_sam: no session");
+	if (sam && s->o.shard_db > 1) return bh_set_error(BH_E_USAGE, "ERROR: --sam traces the paths on rank 0's handle, which must hold the whole database: it does not go with database shards");
+	s->sam = sam;
+	return BH_OK;
+}
 const BhQueries *bh_session_sample(const BhSession *s) { return s && s->cur ? &s->cur->Q : NULL; }
 
 int bh_session_prefetch(BhSession *s, const char *queries) {
@@ -161,6 +168,7 @@ static int sample_fail_ex(BhSession *s, BhSampleResult *res, int rc, const char 
 		if (s->dead) bh_pile_abort(s->o.pile);
 		else if (s->cov_name && !s->pile_col) (void)bh_pile_sample_failed(s->o.pile, s->cov_name);
 	}
+	if (s->sam && s->i0 >= 0) { if (s->dead) bh_sam_abort(s->sam); else bh_sam_discard(s->sam); }      /* (no OUT.sam of a sample that failed) */
 	free(s->cov_name); s->cov_name = NULL;
 	return bh_set_error(rc, "%s", res->err);
 }
@@ -215,6 +223,7 @@ int bh_session_load(BhSession *s, const char *queries, const char *out_path, BhS
 
 static void drop_sample(BhSession *s) {
 	close_output(s, 0);
+	if (s->sam) bh_sam_discard(s->sam);
 	if (s->cur) { ingest_free(s->cur); s->cur = NULL; }
 	free(s->cov_name); s->cov_name = NULL;
 }
@@ -330,9 +339,11 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		const double tr = wall();
 		uint64_t lines = 0;
 		setvbuf(s->out, NULL, _IOFBF, 1 << 22);
-		rc = (o->cigar || o->pile || s->chimera) && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
+		rc = (o->cigar || o->pile || s->chimera || s->sam) && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
 		if (!rc && s->paths) bh_paths_set_pile(s->paths, o->pile, o->cigar);
 		if (!rc && s->chimera && !(rc = bh_chimera_begin(s->chimera, s->db, Q))) bh_paths_set_chimera(s->paths, s->chimera, o->cigar);
+		if (!rc && s->sam) rc = bh_sam_begin(s->sam, R[s->i0].hh, Q, s->out_path);
+		if (!rc && s->paths) rc = bh_paths_set_sam(s->paths, s->sam, o->cigar);
 		s->sink.want_re = s->cluster != NULL;
 		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov || o->em || s->cluster ? &s->sink : NULL, s->paths);
 		if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
@@ -378,6 +389,12 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 			if (o->verbose) bh_chimera_print_info(s->chimera);
 			PHASE("chimera check of the sample");
 		}
+		if (s->sam) {      /* the sample has succeeded: the unmapped records, OUT.sam under its name */
+			rc = bh_sam_end(s->sam);
+			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
+			if (o->verbose) bh_sam_print_info(s->sam);
+			PHASE("SAM records of the sample");
+		}
 		free(s->cov_name); s->cov_name = NULL;
 	}
 	#undef PHASE
@@ -418,6 +435,7 @@ int bh_session_run_mates(BhSession *s, const char *queries1, const char *queries
 	if (s->o.em) return mates_fail(s, res, BH_E_USAGE, "ERROR: the abundance of paired output is out of scope: mates do not go with it");
 	if (s->o.pile) return mates_fail(s, res, BH_E_USAGE, "ERROR: variants of paired output are out of scope: mates do not go with them");
 	if (s->chimera) return mates_fail(s, res, BH_E_USAGE, "ERROR: the chimera check works from the lines of one query file against itself: mates do not go with it");
+	if (s->sam) return mates_fail(s, res, BH_E_USAGE, "ERROR: paired flags, RNEXT and TLEN are out of scope: mates do not go with the SAM output");
 	if (s->cluster) return mates_fail(s, res, BH_E_USAGE, "ERROR: clusters come from the lines of one query file against itself: mates do not go with them");
 	if (s->o.mates.orientation > BHIP_MATES_FF || s->o.mates.report > BHIP_MATES_BEST || s->o.mates.ins_min > s->o.mates.ins_max)
 		return mates_fail(s, res, BH_E_USAGE, "ERROR: mates: orientation fr|rf|ff, report all|best, insert-min <= insert-max");

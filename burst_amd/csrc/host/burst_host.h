@@ -304,6 +304,15 @@ int  bh_paths_push_line(BhPathBuf *b, uint64_t hit, uint32_t ref_off, uint32_t h
 typedef int (*bh_paths_collect_fn)(void *ctx, const uint64_t *idx, const BhipPathReq *req, const uint32_t *first, const uint64_t *off, const uint32_t *ops, uint64_t n_records,
                                    const BhPathBuf *bufs, uint64_t n_chunks);
 void bh_paths_set_collector(BhPaths *paths, bh_paths_collect_fn fn, void *ctx, int columns);
+/* BhPaths keeps a short list of collectors (at most BH_PATHS_MAX_COLLECTORS), called in the order they were added; nothing is traced
+ * twice.  bh_paths_set_collector above sets or (fn = NULL) clears the one entry of the first kind.  bh_paths_add_collector adds an entry
+ * of the second kind, which also gets the rendered text of the group's chunks (text[c], text_len[c]: whole lines, one per note of
+ * bufs[c], without the two path columns): an entry with the same fn is replaced, ctx = NULL removes it; columns as above.  BH_E_USAGE
+ * when the list is full. */
+#define BH_PATHS_MAX_COLLECTORS 4
+typedef int (*bh_paths_collect_text_fn)(void *ctx, const uint64_t *idx, const BhipPathReq *req, const uint32_t *first, const uint64_t *off, const uint32_t *ops, uint64_t n_records,
+                                        const BhPathBuf *bufs, char *const *text, const size_t *text_len, uint64_t n_chunks);
+int  bh_paths_add_collector(BhPaths *paths, bh_paths_collect_text_fn fn, void *ctx, int columns);
 struct BhPile;
 void bh_paths_set_pile(BhPaths *paths, struct BhPile *pile, int columns);
 int  bh_paths_emit(BhPaths *paths, FILE *out, const BhQueries *q, const BhipHit *hits, char *const *text, const size_t *text_len, const BhPathBuf *bufs, uint64_t n_chunks);
@@ -371,6 +380,10 @@ int  bh_cov_lengths_from_extents(const BhDb *db, const uint32_t *extents, uint32
 /* the lane extents from the packed references in host memory (where no one device holds the whole database) */
 void bh_cov_extents_host(const BhDb *db, uint32_t *extents);
 int  bh_cov_lengths_host(BhCov *cov);           /* no lengths table: take them from bh_cov_extents_host now */
+/* the two sources of the lengths on their own (--sam-lengths takes them too): the table `name<TAB>length` looked up for heads[0 .. n_headers)
+ * (`flag` names the option in the error texts), and the database's own extents from `hip_handle`'s lanes (NULL: from host memory) */
+int  bh_cov_read_lengths(const char *file, const char *flag, uint32_t n_headers, const char *const *heads, uint32_t *lengths);
+int  bh_cov_default_lengths(const BhDb *db, void *hip_handle, uint32_t *lengths);
 /* the writer alone: stats = [n_columns][n_headers][4] (tot, cov, sq, lines), column 0 = Dataset, col_names[1 .. n_columns) the samples */
 int  bh_cov_write_tables(const char *prefix, uint32_t n_headers, const char *const *headers, const uint32_t *lengths, uint32_t n_columns,
                          const char *const *col_names, const uint64_t *shared, const uint64_t *unique);
@@ -538,6 +551,46 @@ void bh_chimera_close(BhChimera *ch);
 int  bh_chimera_host(void *unused, uint32_t n_nodes, const uint32_t *weights, const uint32_t *len, const BhipChimLine *lines, uint64_t n_lines,
                      const uint32_t *ops, uint64_t n_ops, uint32_t skew, uint32_t min_seg, uint32_t min_gain, BhipChimera *out, uint64_t info[8]);
 
+/* ---- SAM output beside the .b6, with NM and MD tags (bh_sam.c; burst_hip --sam) ----
+ * For every .b6 output OUT the file OUT.sam: `@HD VN:1.6 SO:unknown GO:query`, one `@SQ SN LN` per database header in the order of the
+ * unique-header numbers (RefMap: the numbers of the placement sink), `@PG ID:burst_hip PN:burst_hip` (no command line, so that a --samples
+ * sample's file equals a separate invocation's), then one record per printed line in .b6 order: QNAME = column 1 up to its first white
+ * space; FLAG = 0x10 when column 9 > column 10, | 0x100 on every line of a read but the first printed for it (a duplicate read is a read of
+ * its own); RNAME = the header's SN (the header up to its first white space); POS and CIGAR = the two --cigar columns; MAPQ 255; RNEXT,
+ * PNEXT, TLEN = * 0 0; SEQ = the codes of the query entry the path belongs to as .ACGTNKMRYSWBVHD (a reverse line: the reverse-complement
+ * entry); QUAL *; NM:i: then MD:Z: (bhip_md_tags, include/burst_hip.h).  With `unmapped`, behind them one record per read without a
+ * line, in query-file order: FLAG 4, * 0 0 * * 0 0, the forward SEQ, QUAL *, no tags.  The file is written under a temporary name and
+ * renamed by bh_sam_end; a sample that failed alone (bh_sam_discard) and a run that ended on an error leave none.
+ *   bh_sam_open        the headers are the database's unique-header numbers; two different headers with one SN are BH_E_USAGE with a text
+ *                      that names both; lengths_file: the table of --coverage-lengths (same format, same errors, bh_cov_read_lengths), or
+ *                      NULL: the database's own extents (bh_cov_default_lengths, taken when the first sample begins)
+ *   bh_sam_open_heads  any headers, with their lengths
+ *   bh_sam_set_md      another MD function (tests): bhip_md_tags' arguments behind ctx, return codes in this file's terms (BH_E_CAPACITY =
+ *                      md_off[n] bytes wanted; the call is repeated once with that room); fn = NULL: the device
+ *   bh_sam_begin       a sample: the handle its paths are traced on, its queries, its .b6 output's name; writes the header
+ *   bh_paths_set_sam   a collector of the path tracer is this object (columns: whether the lines get the --cigar columns): ONE MD call per
+ *                      traced group
+ *   bh_sam_end         the unmapped records, the rename; bh_sam_print_info: the `Sam:` line (records, unmapped records, MD bytes, device
+ *                      milliseconds); bh_sam_last_info: the same figures ([3] in microseconds)
+ *   bh_sam_abort       the run ends on an error: nothing more will be written
+ *   bh_md_host         the MD string and NM of ONE path in plain sequential C over a lane given as an array of codes (lane[0] = column 1):
+ *                      the yardstick.  BH_E_USAGE for what bhip_md_tags refuses, BH_E_CAPACITY with *md_len = the bytes wanted */
+typedef struct BhSam BhSam;
+typedef int (*bh_md_fn)(void *ctx, const BhipPathReq *req, const uint32_t *ref_first, const uint64_t *op_off, const uint32_t *ops, uint64_t n_requests, char *md, uint64_t md_cap,
+                        uint64_t *md_off, uint32_t *nm, uint64_t info[8]);
+int  bh_sam_open(const BhDb *db, const char *lengths_file, int unmapped, BhSam **sam);
+int  bh_sam_open_heads(uint32_t n_headers, const char *const *heads, const uint32_t *lengths, int unmapped, BhSam **sam);
+void bh_sam_set_md(BhSam *sam, bh_md_fn fn, void *ctx);
+int  bh_sam_begin(BhSam *sam, void *hip_handle, const BhQueries *q, const char *out_path);
+int  bh_paths_set_sam(BhPaths *paths, BhSam *sam, int columns);      /* BH_E_USAGE: the tracer's list of collectors is full */
+int  bh_sam_end(BhSam *sam);
+void bh_sam_discard(BhSam *sam);
+void bh_sam_abort(BhSam *sam);
+void bh_sam_print_info(BhSam *sam);
+void bh_sam_last_info(const BhSam *sam, uint64_t info[4]);
+void bh_sam_close(BhSam *sam);
+int  bh_md_host(const uint8_t *lane, uint32_t lane_len, uint32_t ref_first, const uint32_t *ops, uint64_t n_ops, char *md, uint64_t md_cap, uint64_t *md_len, uint32_t *nm);
+
 /* ---- a session: the database stays on the devices, a list of query files runs through it (bh_session.c) ---- */
 typedef struct BhSession BhSession;
 typedef struct BhSessionOpts {            /* fixed for the whole session */
@@ -599,6 +652,10 @@ int  bh_session_set_cluster(BhSession *s, BhCluster *cl);
 /* likewise NULL, or the chimera check every reported sample is given: it opens the path tracer (without the --cigar columns unless the
  * session has them), collects the sample's lines from the traced groups, and writes its table at once.  Mode FORAGE only */
 int  bh_session_set_chimera(BhSession *s, BhChimera *ch);
+/* likewise NULL, or the SAM writer every reported sample is given (rank 0's process; the caller opens and closes it): OUT.sam beside every
+ * output OUT.  It opens the path tracer (without the --cigar columns unless the session has them) and goes with variants and the chimera
+ * check.  Not with database shards, not with bh_session_run_mates */
+int  bh_session_set_sam(BhSession *s, BhSam *sam);
 int  bh_session_ended(const BhSession *s);      /* 0, or the code of the error that ended the session */
 void bh_session_close(BhSession *s);
 

@@ -12,6 +12,7 @@
  *   burst_hip -r reads.fa|reads.edx [-a|-ad ...] -q reads.fa -o self.b6 -m FORAGE -i ... [-fr] --chimeras PREFIX [--chimera-sizes] [--chimera-skew S]
  *             [--chimera-min-seg G] [--chimera-min-gain D]      de-novo two-parent chimera check of the reads from their self-hits and the hits' paths (bh_chimera.c)
  *   ... -q / -o or --samples ... --variants PREFIX [--variants-min-depth N] [--variants-min-alt N] [--variants-reads all|unique]   variant sites per sample (bh_pile.c)
+ *   ... -q / -o or --samples ... --sam [--sam-unmapped] [--sam-lengths FILE]      OUT.sam beside every .b6 output OUT, with NM and MD tags (bh_sam.c)
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
  * reference's exit code 1.  Extra flags: --device N, --batch N (unique queries per device call), -k {12|15}.
@@ -127,6 +128,7 @@ typedef struct {
 	BhMatesOpts mates; int mates_opts_given;
 	const char *em_prefix; uint32_t em_iters; uint64_t em_tol;
 	const char *var_prefix; uint32_t var_min_depth, var_min_alt; int var_unique;
+	int sam, sam_unmapped; const char *sam_lengths;
 } SamplesArgs;
 typedef struct { char *q, *o, *m; int line; } Sample;      /* m: the mates file of a three-field line, or NULL */
 
@@ -180,6 +182,7 @@ static int samples_main(SamplesArgs *a) {
 	if (any_mates && (a->cigar || a->cov_prefix)) { puts("ERROR: --cigar and --coverage of paired output are out of scope: neither goes with mates"); return 1; }
 	if (any_mates && a->em_prefix) { puts("ERROR: --abundance of paired output is out of scope: it does not go with mates"); return 1; }
 	if (any_mates && a->var_prefix) { puts("ERROR: --variants of paired output are out of scope: they do not go with mates"); return 1; }
+	if (any_mates && a->sam) { puts("ERROR: --sam of paired output (paired flags, RNEXT, TLEN) is out of scope: it does not go with mates"); return 1; }
 	const int usedb = bh_is_edx(a->ref_FN);
 	if (usedb < 0) DIE(usedb);
 	/* direct FASTA references: their clumps depend on the longest query (burst.c:5151) -- there is nothing to keep resident */
@@ -241,6 +244,10 @@ static int samples_main(SamplesArgs *a) {
 		if ((rc = bh_em_open(&db, a->em_prefix, a->em_iters, a->em_tol, &em))) DIES(rc);
 		bh_session_set_abundance(ses, em);
 	}
+	BhSam *sam = NULL;
+	if (a->sam) {      /* (the names and the lengths table are checked against the database's headers before a device is touched) */
+		if ((rc = bh_sam_open(&db, a->sam_lengths, a->sam_unmapped, &sam)) || (rc = bh_session_set_sam(ses, sam))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); bh_session_close(ses); return 1; } DIES(rc); }
+	}
 	if (shard_db && (uint32_t)n_shards > db.numRclumps) { bh_session_close(ses); puts("ERROR: more database shards than clumps"); return 1; }
 	{ const int e = open_devices(&db, n_gpus, dev_list, shard_db, n_shards, a->accel_dev, K, a->z, hhs, ranks, slices); if (e) { bh_session_close(ses); return e; } }
 	for (int r = 0; r < n_gpus; ++r) ranks[r].hh = hhs[r];
@@ -281,6 +288,7 @@ static int samples_main(SamplesArgs *a) {
 		else printf("Variants table written: %svariants.txt\n", a->var_prefix);
 	} else if (pile) puts("No variants table is written: the run ended on an error");
 	bh_pile_close(pile); pile = NULL;      /* (a table that was not written leaves no temporary file) */
+	bh_sam_close(sam); sam = NULL;         /* (every sample's file was renamed or removed when the sample ended) */
 	printf("\nSamples: %d done, %d failed. Alignment time: %f seconds\n", n_done, n_failed, wall() - start);
 	fflush(NULL);
 	#undef PHASE
@@ -294,6 +302,10 @@ static int samples_main(SamplesArgs *a) {
 	free(S);
 	return first_fail;
 }
+
+/* the single-sample path's SAM writer: closed on every way out of the run, so that a run that ends on an error leaves no file */
+static BhSam *g_sam;
+static void sam_atexit(void) { bh_sam_close(g_sam); g_sam = NULL; }
 
 static void usage(void) {
 	puts("\nburst_hip: BURST-compatible optimal aligner, MI355X (gfx950) device path");
@@ -345,6 +357,14 @@ static void usage(void) {
 	puts("                  (positions <= 2c in doubled coordinates) and right of it.  Model = the smallest sum over the cuts of the fewest edits left over all");
 	puts("                  parents and the fewest right (ties: higher priority, smaller cut); Single = the fewest edits of one line.  Role Y when");
 	puts("                  Single - Model >= D (3), else N; - = not evaluated (fewer than two parents with a line, or no cut).  Leaves <prefix>chimeras.txt");
+	puts("--sam [--sam-unmapped] [--sam-lengths <file>]: with -q / -o or --samples, leave OUT.sam beside every output OUT: @HD, one @SQ per reference");
+	puts("                  header (SN = the header up to its first white space; LN from a 'name<TAB>length' table as --coverage-lengths takes, else");
+	puts("                  the database's own extent), @PG, and one record per printed line in the order of the lines: FLAG 0x10 for a reverse line,");
+	puts("                  0x100 on every line of a read but its first; POS and CIGAR (=XID) as --cigar prints them; MAPQ 255; SEQ of the strand");
+	puts("                  that was aligned; QUAL *; NM:i: = column 11; MD:Z: = samtools calmd's string over the path, a match being an '=' op: the");
+	puts("                  count of matches, then the reference base under every X, ^ and the reference bases under every D, the count again, also");
+	puts("                  when it is 0 (3=2D1X4= gives 3^AC0T4; I adds nothing).  --sam-unmapped: behind them one FLAG 4 record per read without a");
+	puts("                  line, in query-file order.  Refuses what --cigar refuses, and --mates");
 	puts("--host-acx: build accelerators (-d ... -a, --make-acx) with the host builder instead of the device");
 }
 
@@ -364,6 +384,7 @@ int main(int argc, char **argv) {
 	const char *var_prefix = 0; uint32_t var_min_depth = 4, var_min_alt = 2; int var_unique = 0, var_opts_given = 0;
 	const char *mates_FN = 0; BhMatesOpts mopts = {BHIP_MATES_FR, 0, 1000, BHIP_MATES_ALL}; int mates_opts_given = 0;
 	const char *clu_prefix = 0; int clu_sizes = 0;
+	int sam = 0, sam_unmapped = 0; const char *sam_lengths = 0;
 	const char *chi_prefix = 0; int chi_sizes = 0, chi_opts_given = 0; uint32_t chi_skew = 2, chi_min_seg = 16, chi_min_gain = 3;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
 	BhTaxOpts txo; memset(&txo, 0, sizeof txo); txo.taxacut = 10;   /* burst.c:92 */
@@ -426,6 +447,9 @@ int main(int argc, char **argv) {
 			em_opts_given = 1;
 		}
 		else if (!strcmp(a, "--cigar")) cigar = 1;
+		else if (!strcmp(a, "--sam")) sam = 1;
+		else if (!strcmp(a, "--sam-unmapped")) sam_unmapped = 1;
+		else if (!strcmp(a, "--sam-lengths")) { NEEDARG("--sam-lengths"); sam_lengths = argv[i]; }
 		else if (!strcmp(a, "--cluster")) { NEEDARG("--cluster"); clu_prefix = argv[i]; }
 		else if (!strcmp(a, "--cluster-sizes")) clu_sizes = 1;
 		else if (!strcmp(a, "--chimeras")) { NEEDARG("--chimeras"); chi_prefix = argv[i]; }
@@ -543,6 +567,12 @@ int main(int argc, char **argv) {
 	if (cigar && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --cigar adds the alignment paths to the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
 	if (cigar && (shard_db || n_shards)) { puts("ERROR: --cigar traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
 	if (cigar && !gather_host) { puts("ERROR: --cigar takes the host gather only (drop --gather rccl)"); return 1; }
+	/* (--sam writes its records from the same paths, traced on the same handle: it refuses what --cigar refuses, and paired output) */
+	if ((sam_unmapped || sam_lengths) && !sam) { puts("ERROR: --sam-unmapped and --sam-lengths go with --sam"); return 1; }
+	if (sam && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --sam writes the records of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (sam && (shard_db || n_shards)) { puts("ERROR: --sam traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
+	if (sam && !gather_host) { puts("ERROR: --sam takes the host gather only (drop --gather rccl)"); return 1; }
+	if (sam && mates_FN) { puts("ERROR: --sam of paired output (paired flags, RNEXT, TLEN) is out of scope: it does not go with --mates"); return 1; }
 	/* (--variants counts from the same paths, traced on the same handle: it refuses what --cigar refuses) */
 	if (var_opts_given && !var_prefix) { puts("ERROR: --variants-min-depth, --variants-min-alt and --variants-reads go with --variants <prefix>"); return 1; }
 	if (var_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --variants counts from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
@@ -592,7 +622,7 @@ int main(int argc, char **argv) {
 		SamplesArgs sa = {ref_FN, xcel_FN, tax_FN, samples_FN, mode, thres, z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device,
 		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo, cov_prefix, cov_lengths, cov_pad, cigar,
 		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given, em_prefix, em_iters, em_tol,
-		                  var_prefix, var_min_depth, var_min_alt, var_unique};
+		                  var_prefix, var_min_depth, var_min_alt, var_unique, sam, sam_unmapped, sam_lengths};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
@@ -726,6 +756,10 @@ int main(int argc, char **argv) {
 	if (cov_prefix && (rc = bh_cov_open(&db, cov_prefix, cov_lengths, cov_pad, &cov))) DIEJ(rc);      /* (before a device is touched) */
 	BhEm *em = NULL;
 	if (em_prefix && (rc = bh_em_open(&db, em_prefix, em_iters, em_tol, &em))) DIEJ(rc);
+	if (sam) {      /* (before a device is touched: two headers of one name, a lengths table without a header) */
+		if ((rc = bh_sam_open(&db, sam_lengths, sam_unmapped, &g_sam))) { JOIN_INGEST(); if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
+		atexit(sam_atexit);      /* (whichever way the run ends before bh_sam_end: no file, no temporary file) */
+	}
 	if (shard_db && n_gpus == 1 && n_shards > 1 && !use_rccl) {
 		/* more shards than devices: the shards take turns on the one device (bh_search_serial_shards) -- a database larger than the
 		 * device's memory, at the price of one upload per shard */
@@ -852,7 +886,7 @@ int main(int argc, char **argv) {
 	setvbuf(output, NULL, _IOFBF, 1 << 22);
 	BhPlaceSink sink; memset(&sink, 0, sizeof sink);
 	BhPaths *paths = NULL;
-	if ((cigar || var_prefix || chi_prefix) && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
+	if ((cigar || var_prefix || chi_prefix || sam) && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
 	BhPile *pile = NULL;      /* a study of one sample; opened here: its temporary file exists from now until it is renamed or the object is closed */
 	#define DIEP(rc) do { bh_pile_close(pile); DIE(rc); } while (0)
 	if (var_prefix) {
@@ -867,6 +901,10 @@ int main(int argc, char **argv) {
 	if (chi_prefix) {
 		if ((rc = bh_chimera_open(chi_prefix, chi_sizes, chi_skew, chi_min_seg, chi_min_gain, &chi)) || (rc = bh_chimera_begin(chi, &db, &Q))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
 		bh_paths_set_chimera(paths, chi, cigar);
+	}
+	if (sam) {
+		if ((rc = bh_sam_begin(g_sam, hhs[0], &Q, output_FN))) DIEP(rc);
+		if ((rc = bh_paths_set_sam(paths, g_sam, cigar))) DIEP(rc);
 	}
 	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em || clu ? &sink : NULL, paths))) DIEP(rc);
 	if (fclose(output)) { fprintf(stderr, "ERROR: write failed: %s\n", output_FN); return 2; }      /* (the last buffer of the report: a full disk must not end in exit code 0) */
@@ -903,6 +941,13 @@ int main(int argc, char **argv) {
 		bh_chimera_print_info(chi);
 		printf("Chimera table written: %schimeras.txt\n", chi_prefix);
 		PHASE("chimera check");
+	}
+	if (sam) {      /* last: the run has succeeded, OUT.sam gets its name */
+		if ((rc = bh_sam_end(g_sam))) DIE(rc);
+		bh_sam_print_info(g_sam);
+		printf("SAM records written: %s.sam\n", output_FN);
+		PHASE("SAM records");
+		bh_sam_close(g_sam); g_sam = NULL;
 	}
 	printf("\nAlignment time: %f seconds\n", wall() - start);
 	fflush(NULL);

@@ -326,6 +326,23 @@ def lib():
         L.bh_session_set_chimera.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_session_set_variants.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_session_set_variants.restype = None
+        L.bh_sam_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.bh_sam_open_heads.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.bh_sam_set_md.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_sam_set_md.restype = None
+        L.bh_sam_begin.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BhQueries), C.c_char_p]
+        L.bh_paths_set_sam.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.bh_sam_end.argtypes = [C.c_void_p]
+        L.bh_sam_discard.argtypes = [C.c_void_p]
+        L.bh_sam_discard.restype = None
+        L.bh_sam_abort.argtypes = [C.c_void_p]
+        L.bh_sam_abort.restype = None
+        L.bh_sam_last_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_sam_last_info.restype = None
+        L.bh_sam_close.argtypes = [C.c_void_p]
+        L.bh_sam_close.restype = None
+        L.bh_md_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        L.bh_session_set_sam.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -507,6 +524,27 @@ def _chimera_info(h):
     d = dict(zip(capi.CHIMERA_INFO, (int(x) for x in info)))
     d["lines"], d["foreign"] = lines.value, foreign.value
     return d
+
+
+# an MD function in place of bhip_md_tags (bh_sam_set_md): ctx, requests, ref_first, op_off, ops, n_requests, md, md_cap, md_off, nm, info
+MD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+def md_host(lane, ref_first, ops):
+    """bh_md_host, the MD definition in plain sequential C (no device): the MD string (bytes) and NM of ONE path over a lane given as an
+    array of codes, lane[0] = column 1; ref_first 1-based; ops: uint32 words length << 4 | code"""
+    lane = np.ascontiguousarray(lane, dtype=np.uint8)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    n, nm = C.c_uint64(0), C.c_uint32(0)
+    cap = 16
+    for _ in range(2):
+        md = np.zeros(cap, np.uint8)
+        rc = lib().bh_md_host(lane.ctypes.data, len(lane), int(ref_first), ops.ctypes.data, len(ops), md.ctypes.data, cap, C.byref(n), C.byref(nm))
+        if rc != E_CAPACITY:
+            break
+        cap = int(n.value)
+    _chk(rc)
+    return md[:n.value].tobytes(), int(nm.value)
 
 
 def pile_refs(packed, clump_len, tot_refs):
@@ -880,7 +918,8 @@ class Session:
                  abundance=None, abundance_iters=1000, abundance_tol=1024, abundance_host=False,
                  variants=None, variants_min_depth=4, variants_min_alt=2, variants_reads="all", variants_host=False,
                  cluster=None, cluster_sizes=False, cluster_host=False,
-                 chimeras=None, chimera_sizes=False, chimera_skew=2, chimera_min_seg=16, chimera_min_gain=3, chimera_host=False):
+                 chimeras=None, chimera_sizes=False, chimera_skew=2, chimera_min_seg=16, chimera_min_gain=3, chimera_host=False,
+                 sam=False, sam_unmapped=False, sam_lengths=None, sam_md=None):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
         reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
         process only).
@@ -905,10 +944,16 @@ class Session:
         for two-parent chimeras from the lines it prints and their alignment paths (bh_chimera.c; chimera_sizes: weights from `;size=N`
         suffixes; chimera_skew, chimera_min_seg, chimera_min_gain: S, G and D of the definition), on rank 0's device handle -- or by
         bh_chimera_host with chimera_host=True -- and prefix + chimeras.txt written at once; chimeras() returns the rows of the last sample.
-        Opens the path tracer without adding the cigar columns.  Same limits as cluster, and it goes with cluster."""
+        Opens the path tracer without adding the cigar columns.  Same limits as cluster, and it goes with cluster.
+        sam: every output OUT gets OUT.sam beside it (bh_sam.c: @HD, @SQ per reference header, @PG, one record per printed line with NM and
+        MD tags -- bhip_md_tags on rank 0's device handle, one call per traced group); sam_unmapped: behind them a FLAG 4 record per read
+        without a line, in query-file order; sam_lengths: a `name<TAB>length` table for the @SQ lines (default: the database's own extents).
+        sam_md: an MD_FN in place of the device's function (tests).  Opens the path tracer without adding the cigar columns; same limits as
+        cigar; goes with variants and chimeras, not with mates.  sam_info() has the last sample's figures."""
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
         self._mates_join = mates_join
         self.cov, self.em, self.pile, self.cluster, self.chimera = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.sam = C.c_void_p()
         devs = list(devs) if isinstance(devs, (list, tuple)) else [devs]
         n_local = len(devs)
         world = world or n_local
@@ -995,11 +1040,34 @@ class Session:
             _chk(lib().bh_chimera_open(chimeras.encode(), int(bool(chimera_sizes)), int(chimera_skew), int(chimera_min_seg), int(chimera_min_gain), C.byref(self.chimera)))
             if chimera_host:
                 lib().bh_chimera_set_solver(self.chimera, C.cast(lib().bh_chimera_host, C.c_void_p), None)
-        _chk(lib().bh_session_open(C.byref(db.c), self.ranks, n_local, world, comm, node.h if node is not None else None, C.byref(o), C.byref(self.h)))
-        if self.cluster:
-            _chk(lib().bh_session_set_cluster(self.h, self.cluster))
-        if self.chimera:
-            _chk(lib().bh_session_set_chimera(self.h, self.chimera))
+        if (sam_unmapped or sam_lengths) and not sam:
+            raise ValueError("sam_unmapped and sam_lengths go with sam=True")
+        if sam:
+            if shard_db and int(shard_db) > 1:
+                raise ValueError("sam: the paths are traced on one handle, which must hold the whole database (no shard_db)")
+            if align is not None or world != n_local:
+                raise ValueError("sam: needs the device handles of one process (no align back end, no job of processes)")
+            _chk(lib().bh_sam_open(C.byref(db.c), sam_lengths.encode() if sam_lengths else None, int(bool(sam_unmapped)), C.byref(self.sam)))
+            if sam_md is not None:
+                self._cb.append(sam_md)
+                lib().bh_sam_set_md(self.sam, C.cast(sam_md, C.c_void_p), None)
+        try:
+            _chk(lib().bh_session_open(C.byref(db.c), self.ranks, n_local, world, comm, node.h if node is not None else None, C.byref(o), C.byref(self.h)))
+            if self.sam:
+                _chk(lib().bh_session_set_sam(self.h, self.sam))
+            if self.cluster:
+                _chk(lib().bh_session_set_cluster(self.h, self.cluster))
+            if self.chimera:
+                _chk(lib().bh_session_set_chimera(self.h, self.chimera))
+        except Exception:      # (the objects opened above belong to a session that will never be closed: release them here)
+            if self.h:
+                lib().bh_session_close(self.h)
+                self.h = C.c_void_p()
+            for name, close in (("sam", lib().bh_sam_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
+                if getattr(self, name):
+                    close(getattr(self, name))
+                    setattr(self, name, C.c_void_p())
+            raise
 
     def _align_cb(self, align):
         def _align(ctx, q, u0, u1, n, mode, batch, run):
@@ -1171,6 +1239,12 @@ class Session:
         lines (printed), foreign"""
         return _chimera_info(self.chimera)
 
+    def sam_info(self):
+        """the last written sample's figures: records, unmapped, md_bytes, device_us"""
+        info = np.zeros(4, np.uint64)
+        lib().bh_sam_last_info(self.sam, info.ctypes.data)
+        return dict(zip(("records", "unmapped", "md_bytes", "device_us"), (int(x) for x in info)))
+
     def coverage_abort(self):
         """the walk ends on an error that the session itself has not seen (another rank's): close() writes no tables"""
         if self.cov:
@@ -1209,6 +1283,9 @@ class Session:
                 self.chimera = C.c_void_p()
             lib().bh_session_close(self.h)
             self.h = C.c_void_p()
+            if self.sam:      # (every sample's file was renamed or removed when the sample ended)
+                lib().bh_sam_close(self.sam)
+                self.sam = C.c_void_p()
             for i in range(len(self.ranks)):
                 lib().bh_run_free(C.byref(self.ranks[i].run))
             if self.tax.n or self.tax.blob:

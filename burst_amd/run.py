@@ -220,7 +220,13 @@ def main(argv=None):
     ap.add_argument("--chimera-skew", metavar="S", help="not available here: goes with burst_hip --chimeras")
     ap.add_argument("--chimera-min-seg", metavar="G", help="not available here: goes with burst_hip --chimeras")
     ap.add_argument("--chimera-min-gain", metavar="D", help="not available here: goes with burst_hip --chimeras")
+    ap.add_argument("--sam", action="store_true", help="not available here: SAM records are written by burst_hip --sam (one process, the host gather)")
+    ap.add_argument("--sam-unmapped", action="store_true", help="not available here: goes with burst_hip --sam")
+    ap.add_argument("--sam-lengths", metavar="FILE", help="not available here: goes with burst_hip --sam")
     args = ap.parse_args(argv)
+    if args.sam or args.sam_unmapped or args.sam_lengths:      # (exit code 1, as burst_hip refuses what it cannot do)
+        print("ERROR: --sam is not available in python -m burst_amd.run: use burst_hip --sam (one process, --gpus N with the host gather)", flush=True)
+        return 1
     if args.chimeras or args.chimera_sizes or args.chimera_skew or args.chimera_min_seg or args.chimera_min_gain:      # (exit code 1, as burst_hip refuses what it cannot do)
         print("ERROR: --chimeras is not available in python -m burst_amd.run: use burst_hip --chimeras (one process, --gpus N with the host gather)", flush=True)
         return 1

@@ -508,6 +508,30 @@ BHIP_API int bhip_chimera_run(void *handle, uint32_t n_nodes, const uint32_t *we
                               const uint32_t *ops, uint64_t n_ops, uint32_t skew, uint32_t min_seg, uint32_t min_gain, BhipChimera *out /* [n_nodes] */);
 BHIP_API int bhip_chimera_info(void *handle, uint64_t info[8]);
 
+/* MD tags: the SAM `MD:Z:` string and the `NM:i:` count of alignment paths (burst_hip --sam; no reference counterpart).  The inputs are
+ * exactly what bhip_trace_paths returns for the same requests -- the lane refIx of the request, its first lane column ref_first (1-based,
+ * as the tracer writes it) and its op words length << 4 | code, request i owning ops[op_off[i] .. op_off[i + 1]); the query symbols are
+ * not needed.  The string is what `samtools calmd` computes, over these ops, where a MATCH is an '=' op: cost 0 under the run's scoring,
+ * so an ambiguity code the matrix scores 0 is a match.  With a counter u = 0 and the lane column col = ref_first - 1 (0-based):
+ *   '=' of length n   u += n; col += n
+ *   X of length n     per column: u in decimal, then the reference letter at col; u = 0; col++
+ *   D of length n     u in decimal, then '^', then the n reference letters; u = 0; col += n
+ *   I                 nothing: the counter runs on across it
+ *   at the end        u in decimal, also when it is 0
+ * Letters are "NACGTNKMRYSWBVHD"[code]: the pad code 0 prints N (a valid path never consumes a pad column).  nm[i] = the X + I + D symbols.
+ * Examples: 100= gives `100`; 1X gives `0A0`; 2X gives `0A0C0`; 3=2D1X4= gives `3^AC0T4`; 5=2I5= gives `10`; 1X1D gives `0A0^C0`.
+ * The strings are not terminated: request i owns md[md_off[i] .. md_off[i + 1]), md_off has n_requests + 1 entries.
+ * BHIP_E_CAPACITY when md_off[n_requests] exceeds md_cap: md_off and nm are complete, md is not valid, the handle stays usable.  BHIP_E_ARG
+ * with a text, before any device memory is touched and with the handle staying usable, for null arguments, a word that is not a run of
+ * I / D / '=' / X of length >= 1, op_off that is not ascending, a refIx >= 16 n_clumps or >= tot_refs, and a path whose '=' + X + D columns
+ * leave the columns 1 .. ClumpLen of its lane.  n_requests == 0 launches nothing (md_off[0] = 0).
+ * info (may be NULL): [0] device microseconds of the call (HIP events around its kernels and scan), [1] requests, [2] MD bytes, [3] peak
+ * bytes of the call's scratch buffers (the handle keeps them; bhip_destroy frees them), [4..7] 0.
+ * One thread per request: a counting walk, a 64-bit exclusive sum, the writing walk; an '=' run costs one addition and the lane is read
+ * under X and D only (csrc/bhip_md.hip). */
+BHIP_API int bhip_md_tags(void *handle, const BhipPathReq *requests, const uint32_t *ref_first, const uint64_t *op_off, const uint32_t *ops, uint64_t n_requests,
+                          char *md, uint64_t md_cap, uint64_t *md_off /* [n_requests + 1] */, uint32_t *nm /* [n_requests] */, uint64_t info[8]);
+
 /* Tuning knobs.  "prefilter_stride": 0 (default) = automatic sparse seeds -- per query the largest stride s <= K for
  * which an alignment within budget still keeps >= 3 of the words starting at 0, s, 2s, ... (one edit destroys at most
  * ceil(K/s) of them), fewest .acx look-ups with the same no-false-negative guarantee; s >= 1 forces every s-th word,
