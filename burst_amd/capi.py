@@ -48,7 +48,7 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_comm_create", "bhip_comm_unique_id", "bhip_comm_create_rank", "bhip_comm_allreduce_min", "bhip_comm_fetch_gathered", "bhip_comm_gather_hits", "bhip_comm_stage_device", "bhip_comm_gather_staged", "bhip_comm_stage_reset", "bhip_comm_destroy", "bhip_acx_export", "bhip_reserve", "bhip_reserve_symbols", "bhip_sort_queries", "bhip_stage_spans", "bhip_alloc_host", "bhip_free_host", "bhip_host_register", "bhip_host_unregister", "bhip_set_enqueued_hook", "bhip_acx_export_entries",
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
-           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_pile_run",
+           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_pile_run", "bhip_consensus_run", "bhip_consensus_info",
            "bhip_cluster_run", "bhip_cluster_info", "bhip_chimera_run", "bhip_chimera_info", "bhip_md_tags"]
 
 # BhipMateLine, 20 bytes: pair and header numbers, .b6 columns 9 and 10 (signed), column 11
@@ -88,6 +88,11 @@ PILE_LINE_DTYPE = np.dtype({"names": ["q", "refIx", "ref_first", "header", "pos"
 PILE_SITE_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("ref", "<u4"), ("depth", "<u4"), ("n", "<u4", (6,)), ("ins", "<u4")])
 assert PILE_LINE_DTYPE.itemsize == 40 and PILE_SITE_DTYPE.itemsize == 44
 PILE_INFO = ("events", "candidates", "sites", "device_us", "peak_bytes")
+# BhipConsSeg, 48 bytes: a maximal run of covered positions of a header, its figures, and where its letters start (bhip_consensus_run)
+CONS_SEG_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("len", "<u4"), ("called", "<u4"), ("same", "<u4"), ("subst", "<u4"), ("del", "<u4"), ("ambig", "<u4"),
+                           ("ins_major", "<u4"), ("pad", "<u4"), ("off", "<u8")])
+assert CONS_SEG_DTYPE.itemsize == 48
+CONS_INFO = ("events", "candidates", "segments", "covered", "device_us", "peak_bytes")
 MD_INFO = ("device_us", "requests", "md_bytes", "peak_bytes")
 
 # BhipClusterEdge, 12 bytes: read q has a printed line against read r with this many edits (bhip_cluster_run)
@@ -262,6 +267,10 @@ def _load():
     lib.bhip_em_run.restype = i32
     lib.bhip_pile_run.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, C.POINTER(u64), vp]
     lib.bhip_pile_run.restype = i32
+    lib.bhip_consensus_run.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), vp]
+    lib.bhip_consensus_run.restype = i32
+    lib.bhip_consensus_info.argtypes = [vp, vp]
+    lib.bhip_consensus_info.restype = i32
     lib.bhip_cluster_run.argtypes = [vp, u32, vp, vp, u64, vp, vp]
     lib.bhip_cluster_run.restype = i32
     lib.bhip_cluster_info.argtypes = [vp, vp]
@@ -547,6 +556,32 @@ class Device:
         self._pile_info = dict(zip(PILE_INFO, (int(x) for x in info)))
         _chk(rc)
         return sites[:n.value]
+
+    def consensus_run(self, q, lines, ops, min_depth=4, seg_cap=None, letter_cap=None):
+        """the consensus of one sample on every position its lines cover (bhip_consensus_run).  q, lines, ops: as pile_run takes them.  Returns
+        (segments CONS_SEG_DTYPE in ascending header, position order, letters bytes): segment s owns letters[off : off + len];
+        consensus_info() has the call's figures.  seg_cap / letter_cap: room offered at first; a capacity answer is retried once with
+        the wanted room"""
+        lines = pile_lines(lines)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        seg_cap = max(len(lines), 16) if seg_cap is None else int(seg_cap)
+        letter_cap = 1 << 16 if letter_cap is None else int(letter_cap)
+        ns, nl, info = C.c_uint64(0), C.c_uint64(0), np.zeros(8, np.uint64)
+        for _ in range(2):
+            segs, letters = np.zeros(max(seg_cap, 1), CONS_SEG_DTYPE), np.zeros(max(letter_cap, 1), np.uint8)
+            rc = lib().bhip_consensus_run(self._h, _ptr(q.codes), _ptr(q.off), q.n, _ptr(lines), len(lines), _ptr(ops), len(ops), int(min_depth),
+                                          _ptr(segs), seg_cap, C.byref(ns), _ptr(letters), letter_cap, C.byref(nl), _ptr(info))
+            if rc != BHIP_E_CAPACITY or (ns.value <= seg_cap and nl.value <= letter_cap):
+                break
+            seg_cap, letter_cap = max(seg_cap, ns.value), max(letter_cap, nl.value)
+        _chk(rc)
+        return segs[:ns.value], letters[:nl.value].tobytes()
+
+    def consensus_info(self):
+        """the last consensus_run's figures (bhip_consensus_info): events, candidates, segments, covered, device_us, peak_bytes"""
+        info = np.zeros(8, np.uint64)
+        _chk(lib().bhip_consensus_info(self._h, _ptr(info)))
+        return dict(zip(CONS_INFO, (int(x) for x in info)))
 
     def cluster_run(self, weights, edges):
         """greedy centroid clusters (bhip_cluster_run).  weights: uint32 per node (read), edges: CLUSTER_EDGE_DTYPE array (or rows q, r, edits), raw

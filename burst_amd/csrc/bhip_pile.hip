@@ -31,27 +31,10 @@
 //   select, copy        hipcub flagged selection keeps the order of the candidates, which is ascending (header, position)
 // Lanes that share header positions are taken to agree there (they are cuts of one original sequence): Ref is the smallest ref code among
 // the events of a site, and plain observations count as Ref.
-#include "bhip_handle.h"
-
-#define PILE_BLOCK 256
-#define PILE_MAX_GRID 65536u
-#define PILE_CLS_DEL 4u
-#define PILE_CLS_OTHER 5u
-#define PILE_CLS_INS 6u
-
-struct PileLine { unsigned long long qbase, op_off; uint32_t refIx, ref_first, header, pos, w, n_ops; };      // qbase: offset of the query entry in the uploaded symbols
-struct PileCand { unsigned long long key; uint32_t n[6], ins, ref; };
+#include "bhip_pile.h"
 
 __device__ __forceinline__ uint32_t pile_class(uint32_t code) { return code >= 1u && code <= 4u ? code - 1u : PILE_CLS_OTHER; }
-// code of 0-based column `col` of a lane whose first dword is refw[base]
-__device__ __forceinline__ uint32_t pile_ref(const uint32_t *__restrict__ refw, uint64_t base, uint32_t col) { return (refw[base + (col >> 3)] >> (4u * (col & 7u))) & 15u; }
 __device__ __forceinline__ unsigned long long pile_value(uint32_t w, uint32_t cls, uint32_t ref) { return (unsigned long long)w | (unsigned long long)cls << 32 | (unsigned long long)ref << 36; }
-// number of sorted keys that are <= key
-__device__ __forceinline__ uint64_t pile_upper_bound(const unsigned long long *__restrict__ keys, uint64_t n, unsigned long long key) {
-	uint64_t lo = 0, hi = n;
-	while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (keys[mid] <= key) lo = mid + 1; else hi = mid; }
-	return lo;
-}
 
 // EMIT = false: cnt[i] = events of line i.  EMIT = true: off = the exclusive scan of cnt; the events at their offsets
 template <bool EMIT>
@@ -158,19 +141,6 @@ __global__ __launch_bounds__(PILE_BLOCK) void k_pile_finish(const PileCand *__re
 	}
 }
 
-struct PileState {
-	DBuf lines, span, ops, codes, cnt, off, ev_key, ev_val, ev_key_s, ev_val_s, head, idx, cand, k_start, k_end, w_start, w_end, k_start_s, k_end_s, w_start_s, w_end_s,
-	     cs, ce, site, keep, out, n_sel, tmp;
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	uint64_t bytes() const {
-		const DBuf *all[] = {&lines, &span, &ops, &codes, &cnt, &off, &ev_key, &ev_val, &ev_key_s, &ev_val_s, &head, &idx, &cand, &k_start, &k_end, &w_start, &w_end,
-			&k_start_s, &k_end_s, &w_start_s, &w_end_s, &cs, &ce, &site, &keep, &out, &n_sel, &tmp};
-		uint64_t b = 0;
-		for (const DBuf *x : all) b += x->cap;
-		return b;
-	}
-};
-
 // (bhip_handle.h: Handle::pile)
 void bhip_pile_release(Handle *h) {
 	PileState *st = (PileState *)h->pile;
@@ -184,78 +154,74 @@ void bhip_pile_release(Handle *h) {
 	h->pile = nullptr;
 }
 
-static inline uint32_t pile_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + PILE_BLOCK - 1) / PILE_BLOCK, PILE_MAX_GRID); }
-static inline int pile_bits(uint32_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
-
-typedef unsigned long long pile_u64;
-
-extern "C" int bhip_pile_run(void *handle, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
-		const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]) {
-	Handle *h = (Handle *)handle;
-	uint64_t local[8];
-	if (!info) info = local;
-	memset(info, 0, 8 * sizeof(uint64_t));
-	if (!h || !n_sites || (n_lines && (!lines || !q_codes || !q_off)) || (n_ops && !ops) || (cap && !sites)) return fail(BHIP_E_ARG, "bhip_pile_run: null argument");
-	*n_sites = 0;
-	if (!min_depth || !min_alt) return fail(BHIP_E_ARG, "bhip_pile_run: min_depth %u, min_alt %u (1 .. 2^31 - 1 each)", min_depth, min_alt);
-	if (n_lines >= (1ull << 32)) return fail(BHIP_E_ARG, "bhip_pile_run: %llu lines (fewer than 2^32)", (pile_u64)n_lines);
-	// every line is checked on the host before the device is touched: the kernels index by these values alone
-	std::vector<PileLine> dl((size_t)n_lines);
-	std::vector<uint32_t> span((size_t)n_lines);
+// ---- the stages bhip_pile_run and bhip_consensus_run share (bhip_pile.h) ----
+// every line is checked on the host before the device is touched: the kernels index by these values alone
+int pile_check_lines(const char *who, Handle *h, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
+		const uint32_t *ops, uint64_t n_ops, PileInput &in) {
+	if (n_lines >= (1ull << 32)) return fail(BHIP_E_ARG, "%s: %llu lines (fewer than 2^32)", who, (pile_u64)n_lines);
+	in.dl.assign((size_t)n_lines, PileLine());
+	in.span.assign((size_t)n_lines, 0u);
+	in.codes.clear();
+	in.max_header = 0;
 	std::vector<uint64_t> qpos;
-	std::vector<uint8_t> codes;
 	if (n_lines) qpos.assign(n_queries, ~0ull);
 	uint64_t wsum = 0;
-	uint32_t max_header = 0;
 	for (uint64_t i = 0; i < n_lines; ++i) {
 		const BhipPileLine &u = lines[i];
-		if (u.q >= n_queries) return fail(BHIP_E_ARG, "bhip_pile_run: line %llu names query %u of %u", (pile_u64)i, u.q, n_queries);
-		if (q_off[u.q + 1] < q_off[u.q]) return fail(BHIP_E_ARG, "bhip_pile_run: line %llu: query %u has descending offsets", (pile_u64)i, u.q);
-		if (u.refIx >= 16ull * h->n_clumps || u.refIx >= h->tot_refs) return fail(BHIP_E_ARG, "bhip_pile_run: line %llu names reference %u of %u", (pile_u64)i, u.refIx, h->tot_refs);
-		if (u.op_off > n_ops || u.n_ops > n_ops - u.op_off) return fail(BHIP_E_ARG, "bhip_pile_run: line %llu owns ops %llu + %u of %llu", (pile_u64)i, (pile_u64)u.op_off, u.n_ops, (pile_u64)n_ops);
+		if (u.q >= n_queries) return fail(BHIP_E_ARG, "%s: line %llu names query %u of %u", who, (pile_u64)i, u.q, n_queries);
+		if (q_off[u.q + 1] < q_off[u.q]) return fail(BHIP_E_ARG, "%s: line %llu: query %u has descending offsets", who, (pile_u64)i, u.q);
+		if (u.refIx >= 16ull * h->n_clumps || u.refIx >= h->tot_refs) return fail(BHIP_E_ARG, "%s: line %llu names reference %u of %u", who, (pile_u64)i, u.refIx, h->tot_refs);
+		if (u.op_off > n_ops || u.n_ops > n_ops - u.op_off) return fail(BHIP_E_ARG, "%s: line %llu owns ops %llu + %u of %llu", who, (pile_u64)i, (pile_u64)u.op_off, u.n_ops, (pile_u64)n_ops);
 		uint64_t on_q = 0, on_r = 0;
 		uint32_t last_code = 0;
 		for (uint32_t k = 0; k < u.n_ops; ++k) {
 			const uint32_t word = ops[u.op_off + k], len = word >> 4, code = word & 15u;
 			if (!len || code == last_code || (code != BHIP_OP_I && code != BHIP_OP_D && code != BHIP_OP_EQ && code != BHIP_OP_X))      // (merged runs: an I that is not the first op follows a column)
-				return fail(BHIP_E_ARG, "bhip_pile_run: line %llu, op %u: word 0x%x is not a run of I, D, = or X, or repeats the op before it", (pile_u64)i, k, word);
+				return fail(BHIP_E_ARG, "%s: line %llu, op %u: word 0x%x is not a run of I, D, = or X, or repeats the op before it", who, (pile_u64)i, k, word);
 			last_code = code;
 			if (code != BHIP_OP_D) on_q += len;
 			if (code != BHIP_OP_I) on_r += len;
 		}
 		if (on_q != q_off[u.q + 1] - q_off[u.q])
-			return fail(BHIP_E_ARG, "bhip_pile_run: line %llu: its ops consume %llu query symbols, query %u has %llu", (pile_u64)i, (pile_u64)on_q, u.q, (pile_u64)(q_off[u.q + 1] - q_off[u.q]));
+			return fail(BHIP_E_ARG, "%s: line %llu: its ops consume %llu query symbols, query %u has %llu", who, (pile_u64)i, (pile_u64)on_q, u.q, (pile_u64)(q_off[u.q + 1] - q_off[u.q]));
 		if (u.ref_first < 1 || (uint64_t)u.ref_first - 1 + on_r > h->h_clump_len[u.refIx >> 4])
-			return fail(BHIP_E_ARG, "bhip_pile_run: line %llu: columns %u + %llu leave a clump of %u", (pile_u64)i, u.ref_first, (pile_u64)on_r, h->h_clump_len[u.refIx >> 4]);
-		if (u.pos < 1 || (uint64_t)u.pos + on_r > 0xFFFFFFFFull) return fail(BHIP_E_ARG, "bhip_pile_run: line %llu: position %u + %llu columns (1 .. 2^32 - 1)", (pile_u64)i, u.pos, (pile_u64)on_r);
-		if (!u.w) return fail(BHIP_E_ARG, "bhip_pile_run: line %llu has weight 0", (pile_u64)i);
+			return fail(BHIP_E_ARG, "%s: line %llu: columns %u + %llu leave a clump of %u", who, (pile_u64)i, u.ref_first, (pile_u64)on_r, h->h_clump_len[u.refIx >> 4]);
+		if (u.pos < 1 || (uint64_t)u.pos + on_r > 0xFFFFFFFFull) return fail(BHIP_E_ARG, "%s: line %llu: position %u + %llu columns (1 .. 2^32 - 1)", who, (pile_u64)i, u.pos, (pile_u64)on_r);
+		if (!u.w) return fail(BHIP_E_ARG, "%s: line %llu has weight 0", who, (pile_u64)i);
 		wsum += u.w;
-		if (wsum > 0x7FFFFFFFull) return fail(BHIP_E_ARG, "bhip_pile_run: the lines stand for more than 2^31 - 1 reads (line %llu)", (pile_u64)i);
+		if (wsum > 0x7FFFFFFFull) return fail(BHIP_E_ARG, "%s: the lines stand for more than 2^31 - 1 reads (line %llu)", who, (pile_u64)i);
 		if (qpos[u.q] == ~0ull) {      // (a query entry is uploaded once, word-aligned, however many lines it has)
-			codes.resize((codes.size() + 3) & ~(size_t)3);
-			qpos[u.q] = codes.size();
-			codes.insert(codes.end(), q_codes + q_off[u.q], q_codes + q_off[u.q + 1]);
+			in.codes.resize((in.codes.size() + 3) & ~(size_t)3);
+			qpos[u.q] = in.codes.size();
+			in.codes.insert(in.codes.end(), q_codes + q_off[u.q], q_codes + q_off[u.q + 1]);
 		}
-		PileLine &d = dl[i];
+		PileLine &d = in.dl[i];
 		d.qbase = qpos[u.q]; d.op_off = u.op_off; d.refIx = u.refIx; d.ref_first = u.ref_first; d.header = u.header; d.pos = u.pos; d.w = u.w; d.n_ops = u.n_ops;
-		span[i] = (uint32_t)on_r;
-		max_header = std::max(max_header, u.header);
+		in.span[i] = (uint32_t)on_r;
+		in.max_header = std::max(in.max_header, u.header);
 	}
-	if (!n_lines) return BHIP_OK;      // (no sites, no launch)
-	HIPCHK(hipSetDevice(h->device));
+	return BHIP_OK;
+}
+
+int pile_state(Handle *h, PileState **out) {
 	PileState *st = (PileState *)h->pile;
 	if (!st) {
 		st = new PileState();
 		h->pile = st;
 		if (hipEventCreate(&st->ev0) != hipSuccess || hipEventCreate(&st->ev1) != hipSuccess) { bhip_pile_release(h); return fail(BHIP_E_DEVICE, "hipEventCreate failed"); }
 	}
+	*out = st;
+	return BHIP_OK;
+}
+
+int pile_stage_lines(Handle *h, PileState *st, const PileInput &in, const uint32_t *ops, uint64_t n_ops, pile_u64 *n_events, uint64_t *us) {
 	hipStream_t S = h->stream;
-	const uint64_t nl = n_lines;
-	const int end_bit = 32 + std::max(1, pile_bits(max_header));
+	const uint64_t nl = in.dl.size();
+	const int end_bit = in.end_bit();
 	int rc = st->lines.reserve(nl * sizeof(PileLine)); if (rc) return rc;
 	rc = st->span.reserve(nl * 4); if (rc) return rc;
 	rc = st->ops.reserve(n_ops * 4 + 16); if (rc) return rc;
-	rc = st->codes.reserve(codes.size() + 16); if (rc) return rc;
+	rc = st->codes.reserve(in.codes.size() + 16); if (rc) return rc;
 	rc = st->cnt.reserve((nl + 1) * 8); if (rc) return rc;
 	rc = st->off.reserve((nl + 1) * 8); if (rc) return rc;
 	DBuf *per_line[] = {&st->k_start, &st->k_end, &st->w_start, &st->w_end, &st->k_start_s, &st->k_end_s, &st->w_start_s, &st->w_end_s, &st->cs, &st->ce};
@@ -267,12 +233,12 @@ extern "C" int bhip_pile_run(void *handle, const uint8_t *q_codes, const uint64_
 	rc = st->tmp.reserve(std::max(tb_scan, std::max(tb_sort, tb_sum)) + 16); if (rc) return rc;
 
 	const PileLine *d_lines = st->lines.as<PileLine>();
-	HIPCHK(hipMemcpyAsync(st->lines.p, dl.data(), nl * sizeof(PileLine), hipMemcpyHostToDevice, S));
-	HIPCHK(hipMemcpyAsync(st->span.p, span.data(), nl * 4, hipMemcpyHostToDevice, S));
+	HIPCHK(hipMemcpyAsync(st->lines.p, in.dl.data(), nl * sizeof(PileLine), hipMemcpyHostToDevice, S));
+	HIPCHK(hipMemcpyAsync(st->span.p, in.span.data(), nl * 4, hipMemcpyHostToDevice, S));
 	if (n_ops) HIPCHK(hipMemcpyAsync(st->ops.p, ops, n_ops * 4, hipMemcpyHostToDevice, S));
-	if (!codes.empty()) HIPCHK(hipMemcpyAsync(st->codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice, S));
+	if (!in.codes.empty()) HIPCHK(hipMemcpyAsync(st->codes.p, in.codes.data(), in.codes.size(), hipMemcpyHostToDevice, S));
 	HIPCHK(hipEventRecord(st->ev0, S));
-	// 1. the events of every line: count, scan, and (below) emit
+	// 1. the events of every line: count, scan, and (pile_stage_cands) emit
 	HIPCHK(hipMemsetAsync((char *)st->cnt.p + nl * 8, 0, 8, S));      // (the scan's extra element: off[n_lines] = the total)
 	hipLaunchKernelGGL(k_pile_walk<false>, dim3(pile_grid(nl)), dim3(PILE_BLOCK), 0, S, d_lines, nl, st->ops.as<uint32_t>(), st->codes.as<uint8_t>(), h->ref_lane.as<uint32_t>(),
 		h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), st->cnt.as<pile_u64>(), (const pile_u64 *)nullptr, (uint64_t)0, (pile_u64 *)nullptr, (pile_u64 *)nullptr);
@@ -292,40 +258,79 @@ extern "C" int bhip_pile_run(void *handle, const uint8_t *q_codes, const uint64_
 	tb = st->tmp.cap;
 	HIPCHK(hipcub::DeviceScan::InclusiveSum(st->tmp.p, tb, st->w_end_s.as<pile_u64>(), st->ce.as<pile_u64>(), (size_t)nl, S));
 	HIPCHK(hipEventRecord(st->ev1, S));
-	pile_u64 n_events = 0;
-	HIPCHK(hipMemcpyAsync(&n_events, (char *)st->off.p + nl * 8, 8, hipMemcpyDeviceToHost, S));
+	*n_events = 0;
+	HIPCHK(hipMemcpyAsync(n_events, (char *)st->off.p + nl * 8, 8, hipMemcpyDeviceToHost, S));
 	HIPCHK(hipStreamSynchronize(S));
-	uint64_t us = (uint64_t)(ev_ms(st->ev0, st->ev1) * 1000.0f);
+	*us += (uint64_t)(ev_ms(st->ev0, st->ev1) * 1000.0f);
+	return BHIP_OK;
+}
+
+int pile_stage_cands(Handle *h, PileState *st, const PileInput &in, uint64_t ne, const char *who, pile_u64 *n_cand, uint64_t *us) {
+	hipStream_t S = h->stream;
+	const uint64_t nl = in.dl.size();
+	const int end_bit = in.end_bit();
+	int rc;
+	DBuf *per_event[] = {&st->ev_key, &st->ev_val, &st->ev_key_s, &st->ev_val_s};
+	for (DBuf *x : per_event) { rc = x->reserve(ne * 8); if (rc) return rc; }
+	rc = st->head.reserve((ne + 1) * 8); if (rc) return rc;
+	rc = st->idx.reserve((ne + 1) * 8); if (rc) return rc;
+	size_t tb_sort = 0, tb_scan = 0;
+	HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, st->ev_key.as<pile_u64>(), st->ev_key_s.as<pile_u64>(), st->ev_val.as<pile_u64>(), st->ev_val_s.as<pile_u64>(), (size_t)ne, 0, end_bit, S));
+	HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, st->head.as<pile_u64>(), st->idx.as<pile_u64>(), (size_t)(ne + 1), S));
+	rc = st->tmp.reserve(std::max(tb_sort, tb_scan) + 16); if (rc) return rc;
+	HIPCHK(hipEventRecord(st->ev0, S));
+	hipLaunchKernelGGL(k_pile_walk<true>, dim3(pile_grid(nl)), dim3(PILE_BLOCK), 0, S, st->lines.as<PileLine>(), nl, st->ops.as<uint32_t>(), st->codes.as<uint8_t>(), h->ref_lane.as<uint32_t>(),
+		h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), (pile_u64 *)nullptr, st->off.as<pile_u64>(), ne, st->ev_key.as<pile_u64>(), st->ev_val.as<pile_u64>());
+	HIPCHK(hipGetLastError());
+	// 2. sort, open a candidate at every new key, reduce the runs (pile_launch_reduce)
+	size_t tb = st->tmp.cap;
+	HIPCHK(hipcub::DeviceRadixSort::SortPairs(st->tmp.p, tb, st->ev_key.as<pile_u64>(), st->ev_key_s.as<pile_u64>(), st->ev_val.as<pile_u64>(), st->ev_val_s.as<pile_u64>(), (size_t)ne, 0, end_bit, S));
+	hipLaunchKernelGGL(k_pile_heads, dim3(pile_grid(ne + 1)), dim3(PILE_BLOCK), 0, S, st->ev_key_s.as<pile_u64>(), ne, st->head.as<pile_u64>());
+	HIPCHK(hipGetLastError());
+	tb = st->tmp.cap;
+	HIPCHK(hipcub::DeviceScan::ExclusiveSum(st->tmp.p, tb, st->head.as<pile_u64>(), st->idx.as<pile_u64>(), (size_t)(ne + 1), S));
+	HIPCHK(hipEventRecord(st->ev1, S));
+	*n_cand = 0;
+	HIPCHK(hipMemcpyAsync(n_cand, (char *)st->idx.p + ne * 8, 8, hipMemcpyDeviceToHost, S));
+	HIPCHK(hipStreamSynchronize(S));
+	*us += (uint64_t)(ev_ms(st->ev0, st->ev1) * 1000.0f);
+	if (*n_cand > 0x7FFFFFFFull) return fail(BHIP_E_INTERNAL, "%s: %llu candidate sites (at most 2^31 - 1 in one call)", who, *n_cand);      // (>= 1: there are events)
+	return st->cand.reserve(*n_cand * sizeof(PileCand));
+}
+
+int pile_launch_reduce(Handle *h, PileState *st, uint64_t ne, uint64_t nc) {
+	hipLaunchKernelGGL(k_pile_reduce, dim3(pile_grid(ne)), dim3(PILE_BLOCK), 0, h->stream, st->ev_key_s.as<pile_u64>(), st->ev_val_s.as<pile_u64>(), ne, st->head.as<pile_u64>(),
+		st->idx.as<pile_u64>(), nc, st->cand.as<PileCand>());
+	HIPCHK(hipGetLastError());
+	return BHIP_OK;
+}
+
+extern "C" int bhip_pile_run(void *handle, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
+		const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]) {
+	Handle *h = (Handle *)handle;
+	uint64_t local[8];
+	if (!info) info = local;
+	memset(info, 0, 8 * sizeof(uint64_t));
+	if (!h || !n_sites || (n_lines && (!lines || !q_codes || !q_off)) || (n_ops && !ops) || (cap && !sites)) return fail(BHIP_E_ARG, "bhip_pile_run: null argument");
+	*n_sites = 0;
+	if (!min_depth || !min_alt) return fail(BHIP_E_ARG, "bhip_pile_run: min_depth %u, min_alt %u (1 .. 2^31 - 1 each)", min_depth, min_alt);
+	PileInput in;
+	int rc = pile_check_lines("bhip_pile_run", h, q_codes, q_off, n_queries, lines, n_lines, ops, n_ops, in);
+	if (rc) return rc;
+	if (!n_lines) return BHIP_OK;      // (no sites, no launch)
+	HIPCHK(hipSetDevice(h->device));
+	PileState *st = nullptr;
+	rc = pile_state(h, &st); if (rc) return rc;
+	hipStream_t S = h->stream;
+	const uint64_t nl = n_lines;
+	uint64_t us = 0;
+	pile_u64 n_events = 0, n_cand = 0, n_keep = 0;
+	rc = pile_stage_lines(h, st, in, ops, n_ops, &n_events, &us); if (rc) return rc;
 	info[0] = n_events;
-	pile_u64 n_cand = 0, n_keep = 0;
 	if (n_events) {
 		const uint64_t ne = n_events;
-		DBuf *per_event[] = {&st->ev_key, &st->ev_val, &st->ev_key_s, &st->ev_val_s};
-		for (DBuf *x : per_event) { rc = x->reserve(ne * 8); if (rc) return rc; }
-		rc = st->head.reserve((ne + 1) * 8); if (rc) return rc;
-		rc = st->idx.reserve((ne + 1) * 8); if (rc) return rc;
-		tb_sort = tb_scan = 0;
-		HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, st->ev_key.as<pile_u64>(), st->ev_key_s.as<pile_u64>(), st->ev_val.as<pile_u64>(), st->ev_val_s.as<pile_u64>(), (size_t)ne, 0, end_bit, S));
-		HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, st->head.as<pile_u64>(), st->idx.as<pile_u64>(), (size_t)(ne + 1), S));
-		rc = st->tmp.reserve(std::max(tb_sort, tb_scan) + 16); if (rc) return rc;
-		HIPCHK(hipEventRecord(st->ev0, S));
-		hipLaunchKernelGGL(k_pile_walk<true>, dim3(pile_grid(nl)), dim3(PILE_BLOCK), 0, S, d_lines, nl, st->ops.as<uint32_t>(), st->codes.as<uint8_t>(), h->ref_lane.as<uint32_t>(),
-			h->ref_off.as<uint64_t>(), h->clump_len.as<uint32_t>(), (pile_u64 *)nullptr, st->off.as<pile_u64>(), ne, st->ev_key.as<pile_u64>(), st->ev_val.as<pile_u64>());
-		HIPCHK(hipGetLastError());
-		// 2. sort, open a candidate at every new key, reduce the runs
-		tb = st->tmp.cap;
-		HIPCHK(hipcub::DeviceRadixSort::SortPairs(st->tmp.p, tb, st->ev_key.as<pile_u64>(), st->ev_key_s.as<pile_u64>(), st->ev_val.as<pile_u64>(), st->ev_val_s.as<pile_u64>(), (size_t)ne, 0, end_bit, S));
-		hipLaunchKernelGGL(k_pile_heads, dim3(pile_grid(ne + 1)), dim3(PILE_BLOCK), 0, S, st->ev_key_s.as<pile_u64>(), ne, st->head.as<pile_u64>());
-		HIPCHK(hipGetLastError());
-		tb = st->tmp.cap;
-		HIPCHK(hipcub::DeviceScan::ExclusiveSum(st->tmp.p, tb, st->head.as<pile_u64>(), st->idx.as<pile_u64>(), (size_t)(ne + 1), S));
-		HIPCHK(hipEventRecord(st->ev1, S));
-		HIPCHK(hipMemcpyAsync(&n_cand, (char *)st->idx.p + ne * 8, 8, hipMemcpyDeviceToHost, S));
-		HIPCHK(hipStreamSynchronize(S));
-		us += (uint64_t)(ev_ms(st->ev0, st->ev1) * 1000.0f);
-		const uint64_t nc = n_cand;      // (>= 1: there are events)
-		if (nc > 0x7FFFFFFFull) return fail(BHIP_E_INTERNAL, "bhip_pile_run: %llu candidate sites (at most 2^31 - 1 in one call)", n_cand);
-		rc = st->cand.reserve(nc * sizeof(PileCand)); if (rc) return rc;
+		rc = pile_stage_cands(h, st, in, ne, "bhip_pile_run", &n_cand, &us); if (rc) return rc;
+		const uint64_t nc = n_cand;
 		rc = st->site.reserve(nc * sizeof(BhipPileSite)); if (rc) return rc;
 		rc = st->out.reserve(nc * sizeof(BhipPileSite)); if (rc) return rc;
 		rc = st->keep.reserve(nc + 16); if (rc) return rc;
@@ -334,14 +339,12 @@ extern "C" int bhip_pile_run(void *handle, const uint8_t *q_codes, const uint64_
 		HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tb_sel, st->site.as<BhipPileSite>(), st->keep.as<uint8_t>(), st->out.as<BhipPileSite>(), st->n_sel.as<pile_u64>(), (int)nc, S));
 		rc = st->tmp.reserve(tb_sel + 16); if (rc) return rc;
 		HIPCHK(hipEventRecord(st->ev0, S));
-		hipLaunchKernelGGL(k_pile_reduce, dim3(pile_grid(ne)), dim3(PILE_BLOCK), 0, S, st->ev_key_s.as<pile_u64>(), st->ev_val_s.as<pile_u64>(), ne, st->head.as<pile_u64>(),
-			st->idx.as<pile_u64>(), nc, st->cand.as<PileCand>());
-		HIPCHK(hipGetLastError());
+		rc = pile_launch_reduce(h, st, ne, nc); if (rc) return rc;
 		// 3b. the stabbing count per candidate, the plain observations to count[Ref];  4. the thresholds, the selection in order
 		hipLaunchKernelGGL(k_pile_finish, dim3(pile_grid(nc)), dim3(PILE_BLOCK), 0, S, st->cand.as<PileCand>(), nc, st->k_start_s.as<pile_u64>(), st->cs.as<pile_u64>(),
 			st->k_end_s.as<pile_u64>(), st->ce.as<pile_u64>(), nl, min_depth, min_alt, st->site.as<BhipPileSite>(), st->keep.as<uint8_t>());
 		HIPCHK(hipGetLastError());
-		tb = st->tmp.cap;
+		size_t tb = st->tmp.cap;
 		HIPCHK(hipcub::DeviceSelect::Flagged(st->tmp.p, tb, st->site.as<BhipPileSite>(), st->keep.as<uint8_t>(), st->out.as<BhipPileSite>(), st->n_sel.as<pile_u64>(), (int)nc, S));
 		HIPCHK(hipEventRecord(st->ev1, S));
 		HIPCHK(hipMemcpyAsync(&n_keep, st->n_sel.p, 8, hipMemcpyDeviceToHost, S));
@@ -358,3 +361,4 @@ extern "C" int bhip_pile_run(void *handle, const uint8_t *q_codes, const uint64_
 	info[2] = n_keep;
 	return BHIP_OK;
 }
+

@@ -35,13 +35,14 @@ struct BhSession {
 	SessIngest *cur, *ahead; pthread_t th; char *pending;
 	FILE *out; char *out_path;
 	char *cov_name;                 /* with a coverage or an abundance: the output the loaded sample was given (names its column, also when the sample fails) */
-	int cov_col, em_col, pile_col;  /* the loaded sample has its column in the coverage / the abundance, its block in the variants already */
+	int cov_col, em_col, pile_col, cons_col;  /* the loaded sample has its column in the coverage / the abundance, its block in the variants / the consensus already */
 	BhPlaceSink sink;               /* the report's placements of the current sample (buffer kept across samples) */
 	BhMates *mates;                 /* bh_session_run_mates: the joiner, made on first use */
 	BhCluster *cluster;             /* bh_session_set_cluster: NULL, or the clustering every reported sample is given */
 	BhChimera *chimera;             /* bh_session_set_chimera: NULL, or the chimera check every reported sample is given */
 	BhSam *sam;                     /* bh_session_set_sam: NULL, or the SAM writer every reported sample is given */
-	BhPaths *paths;                 /* with o.cigar, o.pile, a chimera check or a SAM writer: the tracer on the reporting rank's handle, opened by the first sample that reports */
+	BhCons *cons;                   /* bh_session_set_consensus: NULL, or the consensus every reported sample feeds */
+	BhPaths *paths;                 /* with o.cigar, o.pile, a consensus, a chimera check or a SAM writer: the tracer on the reporting rank's handle, opened by the first sample that reports */
 	int dead, dbg, threads_ok;
 	int alive;                      /* query tables alive (the current sample's and the prefetched one's) */
 	pthread_mutex_t mu;             /* `alive` and its debug line */
@@ -115,6 +116,7 @@ void bh_session_set_variants(BhSession *s, BhPile *pile) { if (s) s->o.pile = pi
 int bh_session_set_cluster(BhSession *s, BhCluster *cl) {
 	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_cluster: no session");
 	if (cl && s->o.mode != BH_FORAGE) return bh_set_error(BH_E_USAGE, "ERROR: clusters need every relationship under the identity cutoff: a session in mode FORAGE");
+	if (cl && s->cons) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with the consensus");
 	if (cl && (s->o.cov || s->o.em || s->o.pile || s->o.shard_db > 1)) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with coverage, abundance, variants or database shards");
 	s->cluster = cl;
 	return BH_OK;
@@ -122,6 +124,7 @@ int bh_session_set_cluster(BhSession *s, BhCluster *cl) {
 int bh_session_set_chimera(BhSession *s, BhChimera *ch) {
 	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_chimera: no session");
 	if (ch && s->o.mode != BH_FORAGE) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check needs every relationship under the identity cutoff: a session in mode FORAGE");
+	if (ch && s->cons) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check does not go with the consensus");
 	if (ch && (s->o.cov || s->o.em || s->o.pile || s->o.shard_db > 1)) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check does not go with coverage, abundance, variants or database shards");
 	s->chimera = ch;
 	return BH_OK;
@@ -130,6 +133,13 @@ int bh_session_set_sam(BhSession *s, BhSam *sam) {
 	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_sam: no session");
 	if (sam && s->o.shard_db > 1) return bh_set_error(BH_E_USAGE, "ERROR: --sam traces the paths on rank 0's handle, which must hold the whole database: it does not go with database shards");
 	s->sam = sam;
+	return BH_OK;
+}
+int bh_session_set_consensus(BhSession *s, BhCons *cons) {
+	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_consensus: no session");
+	if (cons && s->o.shard_db > 1) return bh_set_error(BH_E_USAGE, "ERROR: --consensus traces the paths on rank 0's handle, which must hold the whole database: it does not go with database shards");
+	if (cons && (s->cluster || s->chimera)) return bh_set_error(BH_E_USAGE, "ERROR: the consensus does not go with clusters or the chimera check");
+	s->cons = cons;
 	return BH_OK;
 }
 const BhQueries *bh_session_sample(const BhSession *s) { return s && s->cur ? &s->cur->Q : NULL; }
@@ -168,6 +178,10 @@ static int sample_fail_ex(BhSession *s, BhSampleResult *res, int rc, const char 
 		if (s->dead) bh_pile_abort(s->o.pile);
 		else if (s->cov_name && !s->pile_col) (void)bh_pile_sample_failed(s->o.pile, s->cov_name);
 	}
+	if (s->cons && s->i0 >= 0) {
+		if (s->dead) bh_consensus_abort(s->cons);
+		else if (s->cov_name && !s->cons_col) (void)bh_consensus_sample_failed(s->cons, s->cov_name);
+	}
 	if (s->sam && s->i0 >= 0) { if (s->dead) bh_sam_abort(s->sam); else bh_sam_discard(s->sam); }      /* (no OUT.sam of a sample that failed) */
 	free(s->cov_name); s->cov_name = NULL;
 	return bh_set_error(rc, "%s", res->err);
@@ -182,8 +196,8 @@ int bh_session_load(BhSession *s, const char *queries, const char *out_path, BhS
 	if (s->dead) { res->rc = s->dead; snprintf(res->err, sizeof res->err, "the session was ended by an earlier error (code %d)", s->dead); return bh_set_error(s->dead, "%s", res->err); }
 	if (s->cur) return bh_set_error(BH_E_USAGE, "bh_session_load: the previous sample has not been finished or dropped");
 	s->tLoad = wall();
-	free(s->cov_name); s->cov_name = NULL; s->cov_col = s->em_col = s->pile_col = 0;
-	if ((s->o.cov || s->o.em || s->o.pile) && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
+	free(s->cov_name); s->cov_name = NULL; s->cov_col = s->em_col = s->pile_col = s->cons_col = 0;
+	if ((s->o.cov || s->o.em || s->o.pile || s->cons) && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
 	SessIngest *g = NULL;
 	/* the outstanding ingest is this sample's: take it.  If it is another one's (prefetched before this sample was named) it stays
 	 * outstanding and this sample is read here */
@@ -234,6 +248,7 @@ int bh_session_drop(BhSession *s) {
 	if (s->o.cov && s->cur && s->cov_name && !s->dead) (void)bh_cov_sample_failed(s->o.cov, s->cov_name);
 	if (s->o.em && s->cur && s->cov_name && !s->dead) (void)bh_em_sample_failed(s->o.em, s->cov_name);
 	if (s->o.pile && s->cur && s->cov_name && !s->dead) (void)bh_pile_sample_failed(s->o.pile, s->cov_name);
+	if (s->cons && s->cur && s->cov_name && !s->dead) (void)bh_consensus_sample_failed(s->cons, s->cov_name);
 	drop_sample(s);
 	return BH_OK;
 }
@@ -339,11 +354,12 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		const double tr = wall();
 		uint64_t lines = 0;
 		setvbuf(s->out, NULL, _IOFBF, 1 << 22);
-		rc = (o->cigar || o->pile || s->chimera || s->sam) && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
+		rc = (o->cigar || o->pile || s->cons || s->chimera || s->sam) && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
 		if (!rc && s->paths) bh_paths_set_pile(s->paths, o->pile, o->cigar);
 		if (!rc && s->chimera && !(rc = bh_chimera_begin(s->chimera, s->db, Q))) bh_paths_set_chimera(s->paths, s->chimera, o->cigar);
 		if (!rc && s->sam) rc = bh_sam_begin(s->sam, R[s->i0].hh, Q, s->out_path);
 		if (!rc && s->paths) rc = bh_paths_set_sam(s->paths, s->sam, o->cigar);
+		if (!rc && s->paths) rc = bh_paths_set_consensus(s->paths, s->cons, o->cigar);
 		s->sink.want_re = s->cluster != NULL;
 		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov || o->em || s->cluster ? &s->sink : NULL, s->paths);
 		if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
@@ -374,6 +390,13 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
 			if (o->verbose) bh_pile_print_info(o->pile);
 			PHASE("variant sites of the sample");
+		}
+		if (s->cons) {     /* the sample's consensus: one call over the lines the tracer handed over, on rank 0's device as well */
+			rc = bh_consensus_sample(s->cons, R[s->i0].hh, s->cov_name, Q->codes, Q->qoff, Q->numEntries);
+			s->cons_col = 1;
+			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
+			if (o->verbose) bh_consensus_print_info(s->cons);
+			PHASE("consensus of the sample");
 		}
 		if (s->cluster) {  /* the sample's reads clustered from its own lines, on rank 0's device as well; the tables at once */
 			rc = bh_cluster_sample(s->cluster, R[s->i0].hh, s->db, Q, &s->sink);
@@ -434,6 +457,7 @@ int bh_session_run_mates(BhSession *s, const char *queries1, const char *queries
 	if (s->o.cov || s->o.cigar) return mates_fail(s, res, BH_E_USAGE, "ERROR: coverage and alignment paths of paired output are out of scope: mates go with neither");
 	if (s->o.em) return mates_fail(s, res, BH_E_USAGE, "ERROR: the abundance of paired output is out of scope: mates do not go with it");
 	if (s->o.pile) return mates_fail(s, res, BH_E_USAGE, "ERROR: variants of paired output are out of scope: mates do not go with them");
+	if (s->cons) return mates_fail(s, res, BH_E_USAGE, "ERROR: the consensus of paired output is out of scope: mates do not go with it");
 	if (s->chimera) return mates_fail(s, res, BH_E_USAGE, "ERROR: the chimera check works from the lines of one query file against itself: mates do not go with it");
 	if (s->sam) return mates_fail(s, res, BH_E_USAGE, "ERROR: paired flags, RNEXT and TLEN are out of scope: mates do not go with the SAM output");
 	if (s->cluster) return mates_fail(s, res, BH_E_USAGE, "ERROR: clusters come from the lines of one query file against itself: mates do not go with them");

@@ -460,6 +460,50 @@ void bh_pile_close(BhPile *pile);
 int  bh_pile_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
                   const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]);
 
+/* ---- consensus sequences per reference and sample from the alignment paths (bh_consensus.c; burst_hip --consensus) ----
+ * The definition is bhip_consensus_run's (include/burst_hip.h): per sample, every printed line is a line of the pile-up, as for the variant
+ * sites; every covered position gets a letter, and the segments of a header become one record in REFERENCE coordinates -- the header's
+ * length L letters, N outside the segments, '-' for a deletion -- so that the records of one reference from all samples are the rows of
+ * one alignment.  L: the table of --consensus-lengths (format and errors of --coverage-lengths) or the database's own extents; a segment
+ * that ends beyond L is BH_E_USAGE that names the header.  Two files, written under temporary names (opened by bh_consensus_open, a block
+ * per sample in study order, headers in strcmp order) and renamed together by bh_consensus_write; bh_consensus_close removes temporary
+ * files that were not renamed:
+ *   PREFIXconsensus.fa    `>SAMPLE|HEADER` and L letters, for every (sample, header) with Called >= 1 and 1000 * Called >= min_breadth * L
+ *   PREFIXconsensus.txt   #Reference Sample Length Covered Called Same Subst Del Ambig InsMajor Record, a row per (sample, header) with Covered >= 1
+ *   bh_consensus_open          the headers are the database's unique-header numbers (RefMap); bh_consensus_open_heads: any headers and lengths
+ *   bh_consensus_collect       the tracer's hand-over of a traced group; bh_paths_set_consensus registers it beside the other collectors
+ *   bh_consensus_sample        the end of a sample: ONE solver call over its lines (the room grows once), its block appended to both files
+ *   bh_consensus_sample_failed the sample has no rows (it failed alone); named on standard output
+ *   bh_consensus_abort         the run ends on an error: nothing will be written
+ *   bh_consensus_rows          the rows of the table so far (headers as unique-header numbers); returns their number
+ *   bh_consensus_print_info    the `Consensus:` line of the last sample on standard output; bh_consensus_last_info: the same figures
+ *   bh_consensus_set_solver    another solver (tests): bhip_consensus_run's arguments behind ctx, return codes in this file's terms
+ *   bh_consensus_host          the definition in plain C, a solver: ctx = a BhPileRefs; one record per observed base, sorted and counted */
+typedef struct BhCons BhCons;
+typedef struct BhConsRow { uint32_t header, sample, length, covered, called, same, subst, del, ambig, ins_major, record, pad; } BhConsRow;
+typedef int (*bh_cons_solver_fn)(void *ctx, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
+                                 const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, BhipConsSeg *segs, uint64_t seg_cap, uint64_t *n_segs,
+                                 char *letters, uint64_t letter_cap, uint64_t *n_letters, uint64_t info[8]);
+int  bh_consensus_check_opts(uint32_t min_depth, uint32_t min_breadth);      /* BH_E_USAGE with the command line's text for a value outside its range */
+int  bh_consensus_open(const BhDb *db, const char *prefix, const char *lengths_file, uint32_t min_depth, uint32_t min_breadth, int unique_only, BhCons **cons);
+int  bh_consensus_open_heads(const char *prefix, uint32_t n_headers, const char *const *heads, const uint32_t *lengths, uint32_t min_depth, uint32_t min_breadth,
+                             int unique_only, BhCons **cons);
+void bh_consensus_set_solver(BhCons *cons, bh_cons_solver_fn fn, void *ctx);
+int  bh_consensus_collect(BhCons *cons, const uint64_t *idx, const BhipPathReq *req, const uint32_t *first, const uint64_t *off, const uint32_t *ops, uint64_t n_records,
+                          const BhPathBuf *bufs, uint64_t n_chunks);
+int  bh_paths_set_consensus(BhPaths *paths, BhCons *cons, int columns);      /* BH_E_USAGE: the tracer's list of collectors is full */
+int  bh_consensus_sample(BhCons *cons, void *hip_handle, const char *out_path, const uint8_t *q_codes, const uint64_t *q_off, uint64_t n_queries);
+int  bh_consensus_sample_failed(BhCons *cons, const char *out_path);
+void bh_consensus_abort(BhCons *cons);
+uint64_t bh_consensus_rows(const BhCons *cons, BhConsRow *rows, uint64_t cap);
+int  bh_consensus_write(BhCons *cons);
+void bh_consensus_print_info(BhCons *cons);
+void bh_consensus_last_info(const BhCons *cons, uint64_t info[8], uint64_t *lines, uint64_t *records);
+void bh_consensus_close(BhCons *cons);
+int  bh_consensus_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
+                       const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, BhipConsSeg *segs, uint64_t seg_cap, uint64_t *n_segs,
+                       char *letters, uint64_t letter_cap, uint64_t *n_letters, uint64_t info[8]);
+
 /* ---- greedy centroid clusters of the reads of a query file aligned against itself (bh_cluster.c; burst_hip --cluster) ----
  * The definition is bhip_cluster_run's (include/burst_hip.h): nodes = the reads in file order, named by column 1; weight 1, or with
  * use_sizes the N of a trailing `;size=N[;]`; an edge per printed line whose column 2 is the name of another read, its edits the smallest
@@ -656,6 +700,10 @@ int  bh_session_set_chimera(BhSession *s, BhChimera *ch);
  * output OUT.  It opens the path tracer (without the --cigar columns unless the session has them) and goes with variants and the chimera
  * check.  Not with database shards, not with bh_session_run_mates */
 int  bh_session_set_sam(BhSession *s, BhSam *sam);
+/* likewise NULL, or the consensus every reported sample feeds (rank 0's process; the caller opens it, writes the files and closes it): it
+ * opens the path tracer (without the --cigar columns unless the session has them) and goes with coverage, abundance, variants and the SAM
+ * writer.  Not with database shards, clusters, the chimera check or bh_session_run_mates */
+int  bh_session_set_consensus(BhSession *s, BhCons *cons);
 int  bh_session_ended(const BhSession *s);      /* 0, or the code of the error that ended the session */
 void bh_session_close(BhSession *s);
 

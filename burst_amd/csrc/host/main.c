@@ -12,6 +12,7 @@
  *   burst_hip -r reads.fa|reads.edx [-a|-ad ...] -q reads.fa -o self.b6 -m FORAGE -i ... [-fr] --chimeras PREFIX [--chimera-sizes] [--chimera-skew S]
  *             [--chimera-min-seg G] [--chimera-min-gain D]      de-novo two-parent chimera check of the reads from their self-hits and the hits' paths (bh_chimera.c)
  *   ... -q / -o or --samples ... --variants PREFIX [--variants-min-depth N] [--variants-min-alt N] [--variants-reads all|unique]   variant sites per sample (bh_pile.c)
+ *   ... -q / -o or --samples ... --consensus PREFIX [--consensus-min-depth N] [--consensus-min-breadth PERMILLE] [--consensus-reads all|unique] [--consensus-lengths FILE]   consensus per reference and sample (bh_consensus.c)
  *   ... -q / -o or --samples ... --sam [--sam-unmapped] [--sam-lengths FILE]      OUT.sam beside every .b6 output OUT, with NM and MD tags (bh_sam.c)
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
@@ -129,6 +130,7 @@ typedef struct {
 	const char *em_prefix; uint32_t em_iters; uint64_t em_tol;
 	const char *var_prefix; uint32_t var_min_depth, var_min_alt; int var_unique;
 	int sam, sam_unmapped; const char *sam_lengths;
+	const char *cons_prefix; uint32_t cons_min_depth, cons_min_breadth; int cons_unique; const char *cons_lengths;
 } SamplesArgs;
 typedef struct { char *q, *o, *m; int line; } Sample;      /* m: the mates file of a three-field line, or NULL */
 
@@ -166,6 +168,18 @@ static int read_sample_list(const SamplesArgs *a, Sample **out, int *n_out) {
 	return 0;
 }
 
+/* the consensus of a run: closed on every way out, so that a run that ends on an error leaves neither file nor temporary file */
+static BhCons *g_cons;
+static void cons_atexit(void) { bh_consensus_close(g_cons); g_cons = NULL; }
+/* opened before a device is touched: the lengths table is checked against the database's headers */
+static int open_consensus(const BhDb *db, const char *prefix, const char *lengths, uint32_t min_depth, uint32_t min_breadth, int unique) {
+	if (!db->refMap || !db->numRefHeads) { puts("ERROR: --consensus needs the reference headers of the database"); return 1; }
+	const int rc = bh_consensus_open(db, prefix, lengths, min_depth, min_breadth, unique, &g_cons);
+	if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; }
+	if (rc) { fprintf(stderr, "%s\n", bh_last_error()); return code_to_exit(rc); }
+	atexit(cons_atexit);
+	return 0;
+}
 static int samples_main(SamplesArgs *a) {
 	Sample *S = NULL; int nS = 0, rc;
 	if (a->list_FN) { const int e = read_sample_list(a, &S, &nS); if (e) return e; }
@@ -182,6 +196,7 @@ static int samples_main(SamplesArgs *a) {
 	if (any_mates && (a->cigar || a->cov_prefix)) { puts("ERROR: --cigar and --coverage of paired output are out of scope: neither goes with mates"); return 1; }
 	if (any_mates && a->em_prefix) { puts("ERROR: --abundance of paired output is out of scope: it does not go with mates"); return 1; }
 	if (any_mates && a->var_prefix) { puts("ERROR: --variants of paired output are out of scope: they do not go with mates"); return 1; }
+	if (any_mates && a->cons_prefix) { puts("ERROR: --consensus of paired output is out of scope: it does not go with mates"); return 1; }
 	if (any_mates && a->sam) { puts("ERROR: --sam of paired output (paired flags, RNEXT, TLEN) is out of scope: it does not go with mates"); return 1; }
 	const int usedb = bh_is_edx(a->ref_FN);
 	if (usedb < 0) DIE(usedb);
@@ -248,6 +263,11 @@ static int samples_main(SamplesArgs *a) {
 	if (a->sam) {      /* (the names and the lengths table are checked against the database's headers before a device is touched) */
 		if ((rc = bh_sam_open(&db, a->sam_lengths, a->sam_unmapped, &sam)) || (rc = bh_session_set_sam(ses, sam))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); bh_session_close(ses); return 1; } DIES(rc); }
 	}
+	if (a->cons_prefix) {
+		const int e = open_consensus(&db, a->cons_prefix, a->cons_lengths, a->cons_min_depth, a->cons_min_breadth, a->cons_unique);
+		if (e) { bh_session_close(ses); return e; }
+		if ((rc = bh_session_set_consensus(ses, g_cons))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); bh_session_close(ses); return 1; } DIES(rc); }
+	}
 	if (shard_db && (uint32_t)n_shards > db.numRclumps) { bh_session_close(ses); puts("ERROR: more database shards than clumps"); return 1; }
 	{ const int e = open_devices(&db, n_gpus, dev_list, shard_db, n_shards, a->accel_dev, K, a->z, hhs, ranks, slices); if (e) { bh_session_close(ses); return e; } }
 	for (int r = 0; r < n_gpus; ++r) ranks[r].hh = hhs[r];
@@ -288,6 +308,11 @@ static int samples_main(SamplesArgs *a) {
 		else printf("Variants table written: %svariants.txt\n", a->var_prefix);
 	} else if (pile) puts("No variants table is written: the run ended on an error");
 	bh_pile_close(pile); pile = NULL;      /* (a table that was not written leaves no temporary file) */
+	if (g_cons && !bh_session_ended(ses)) {
+		if ((rc = bh_consensus_write(g_cons))) { if (rc == BH_E_USAGE) puts(bh_last_error()); else fprintf(stderr, "%s\n", bh_last_error()); if (!first_fail) first_fail = code_to_exit(rc); }
+		else printf("Consensus written: %sconsensus.fa, %sconsensus.txt\n", a->cons_prefix, a->cons_prefix);
+	} else if (g_cons) puts("No consensus is written: the run ended on an error");
+	bh_consensus_close(g_cons); g_cons = NULL;
 	bh_sam_close(sam); sam = NULL;         /* (every sample's file was renamed or removed when the sample ended) */
 	printf("\nSamples: %d done, %d failed. Alignment time: %f seconds\n", n_done, n_failed, wall() - start);
 	fflush(NULL);
@@ -346,6 +371,14 @@ static void usage(void) {
 	puts("                  (Depth, A, C, G, T, Del, Other) and the insertions behind the position (Ins), counted from the alignment paths of the");
 	puts("                  printed lines; a position is listed when its reference base is A/C/G/T, Depth >= --variants-min-depth (4) and the reads");
 	puts("                  that differ, or Ins, are >= --variants-min-alt (2); --variants-reads unique counts only reads printed on one line");
+	puts("--consensus <prefix> [--consensus-min-depth <int>] [--consensus-min-breadth <permille>] [--consensus-reads all|unique] [--consensus-lengths <file>]:");
+	puts("                  with -q / -o or --samples, leave <prefix>consensus.fa and <prefix>consensus.txt: per sample and reference header the sequence the");
+	puts("                  sample's reads show, in REFERENCE coordinates (every record has the reference's length, from a 'name<TAB>length' table as");
+	puts("                  --coverage-lengths takes, else the database's own extent): at a position with Depth >= --consensus-min-depth (4) the largest of");
+	puts("                  the counts A, C, G, T, Del of --variants (the reference's base among equals, then that order; - for Del; the reference's own");
+	puts("                  letter where it is an ambiguity code), N elsewhere.  Insertions are counted (InsMajor), not written.  A record is written when");
+	puts("                  a position was called and 1000 * Called >= --consensus-min-breadth (0) * length; the table has a row per covered (sample,");
+	puts("                  header).  --consensus-reads unique counts only reads printed on one line.  Refuses what --variants refuses");
 	puts("--cluster <prefix> [--cluster-sizes]: with -q reads -r the same reads (FASTA or .edx) -m FORAGE, greedy centroid clusters of the reads from the");
 	puts("                  lines they print against each other: the reads in the order of their weight (1, or with --cluster-sizes the N of a trailing");
 	puts("                  ;size=N of the name), ties in file order; a read with a line to an earlier centroid joins the one with the fewest edits, any");
@@ -385,6 +418,7 @@ int main(int argc, char **argv) {
 	const char *mates_FN = 0; BhMatesOpts mopts = {BHIP_MATES_FR, 0, 1000, BHIP_MATES_ALL}; int mates_opts_given = 0;
 	const char *clu_prefix = 0; int clu_sizes = 0;
 	int sam = 0, sam_unmapped = 0; const char *sam_lengths = 0;
+	const char *cons_prefix = 0, *cons_lengths = 0; uint32_t cons_min_depth = 4, cons_min_breadth = 0; int cons_unique = 0, cons_opts_given = 0;
 	const char *chi_prefix = 0; int chi_sizes = 0, chi_opts_given = 0; uint32_t chi_skew = 2, chi_min_seg = 16, chi_min_gain = 3;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
 	BhTaxOpts txo; memset(&txo, 0, sizeof txo); txo.taxacut = 10;   /* burst.c:92 */
@@ -474,6 +508,20 @@ int main(int argc, char **argv) {
 			NEEDARG("--variants-reads"); var_opts_given = 1;
 			if (!strcmp(argv[i], "all")) var_unique = 0; else if (!strcmp(argv[i], "unique")) var_unique = 1; else { puts("ERROR: --variants-reads all|unique"); return 1; }
 		}
+		else if (!strcmp(a, "--consensus")) { NEEDARG("--consensus"); cons_prefix = argv[i]; }
+		else if (!strcmp(a, "--consensus-min-depth") || !strcmp(a, "--consensus-min-breadth")) {
+			const int is_breadth = !strcmp(a, "--consensus-min-breadth");
+			NEEDARG(a);
+			char *end = NULL; const unsigned long long v = strtoull(argv[i], &end, 10);
+			if (!*argv[i] || *end || (is_breadth ? v > 1000 : !v || v > 0x7FFFFFFFull)) { puts(is_breadth ? "ERROR: --consensus-min-breadth takes 0 .. 1000 (permille of the reference's length)" : "ERROR: --consensus-min-depth takes 1 .. 2147483647"); return 1; }
+			if (is_breadth) cons_min_breadth = (uint32_t)v; else cons_min_depth = (uint32_t)v;
+			cons_opts_given = 1;
+		}
+		else if (!strcmp(a, "--consensus-reads")) {
+			NEEDARG("--consensus-reads"); cons_opts_given = 1;
+			if (!strcmp(argv[i], "all")) cons_unique = 0; else if (!strcmp(argv[i], "unique")) cons_unique = 1; else { puts("ERROR: --consensus-reads all|unique"); return 1; }
+		}
+		else if (!strcmp(a, "--consensus-lengths")) { NEEDARG("--consensus-lengths"); cons_lengths = argv[i]; cons_opts_given = 1; }
 		else if (!strcmp(a, "--mates")) { NEEDARG("--mates"); mates_FN = argv[i]; }
 		else if (!strcmp(a, "--insert-min") || !strcmp(a, "--insert-max")) {
 			const int is_max = !strcmp(a, "--insert-max");
@@ -579,6 +627,14 @@ int main(int argc, char **argv) {
 	if (var_prefix && (shard_db || n_shards)) { puts("ERROR: --variants traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
 	if (var_prefix && !gather_host) { puts("ERROR: --variants takes the host gather only (drop --gather rccl)"); return 1; }
 	if (var_prefix && mates_FN) { puts("ERROR: --variants of paired output are out of scope: they do not go with --mates"); return 1; }
+	/* (--consensus calls from the same paths, traced on the same handle: it refuses what --variants refuses, and the self-alignment outputs) */
+	if (cons_opts_given && !cons_prefix) { puts("ERROR: --consensus-min-depth, --consensus-min-breadth, --consensus-reads and --consensus-lengths go with --consensus <prefix>"); return 1; }
+	if (cons_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --consensus calls from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (cons_prefix && (shard_db || n_shards)) { puts("ERROR: --consensus traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
+	if (cons_prefix && !gather_host) { puts("ERROR: --consensus takes the host gather only (drop --gather rccl)"); return 1; }
+	if (cons_prefix && mates_FN) { puts("ERROR: --consensus of paired output is out of scope: it does not go with --mates"); return 1; }
+	if (cons_prefix && (clu_prefix || chi_prefix)) { puts("ERROR: --consensus does not go with --cluster or --chimeras: per-reference outputs of a self-alignment are out of scope"); return 1; }
+	if (cons_prefix && !samples_FN && !(ref_FN && query_FN && output_FN)) { puts("ERROR: --consensus goes with an alignment run: -r, -q and -o, or --samples"); return 1; }
 	/* (--cluster picks clusters from the lines one query file prints against itself: refused before a device is touched whatever would
 	 * discard those lines, print other files' lines, or leave rank 0 without the whole report) */
 	if (clu_sizes && !clu_prefix) { puts("ERROR: --cluster-sizes goes with --cluster <prefix>"); return 1; }
@@ -622,7 +678,8 @@ int main(int argc, char **argv) {
 		SamplesArgs sa = {ref_FN, xcel_FN, tax_FN, samples_FN, mode, thres, z, do_rc, incl_ws, do_accel, accel_dev, K, skip_ambig, rep_flags, threads, device,
 		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo, cov_prefix, cov_lengths, cov_pad, cigar,
 		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given, em_prefix, em_iters, em_tol,
-		                  var_prefix, var_min_depth, var_min_alt, var_unique, sam, sam_unmapped, sam_lengths};
+		                  var_prefix, var_min_depth, var_min_alt, var_unique, sam, sam_unmapped, sam_lengths,
+		                  cons_prefix, cons_min_depth, cons_min_breadth, cons_unique, cons_lengths};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
@@ -756,6 +813,7 @@ int main(int argc, char **argv) {
 	if (cov_prefix && (rc = bh_cov_open(&db, cov_prefix, cov_lengths, cov_pad, &cov))) DIEJ(rc);      /* (before a device is touched) */
 	BhEm *em = NULL;
 	if (em_prefix && (rc = bh_em_open(&db, em_prefix, em_iters, em_tol, &em))) DIEJ(rc);
+	if (cons_prefix) { const int e = open_consensus(&db, cons_prefix, cons_lengths, cons_min_depth, cons_min_breadth, cons_unique); if (e) { JOIN_INGEST(); return e; } }
 	if (sam) {      /* (before a device is touched: two headers of one name, a lengths table without a header) */
 		if ((rc = bh_sam_open(&db, sam_lengths, sam_unmapped, &g_sam))) { JOIN_INGEST(); if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
 		atexit(sam_atexit);      /* (whichever way the run ends before bh_sam_end: no file, no temporary file) */
@@ -886,7 +944,7 @@ int main(int argc, char **argv) {
 	setvbuf(output, NULL, _IOFBF, 1 << 22);
 	BhPlaceSink sink; memset(&sink, 0, sizeof sink);
 	BhPaths *paths = NULL;
-	if ((cigar || var_prefix || chi_prefix || sam) && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
+	if ((cigar || var_prefix || cons_prefix || chi_prefix || sam) && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
 	BhPile *pile = NULL;      /* a study of one sample; opened here: its temporary file exists from now until it is renamed or the object is closed */
 	#define DIEP(rc) do { bh_pile_close(pile); DIE(rc); } while (0)
 	if (var_prefix) {
@@ -906,6 +964,7 @@ int main(int argc, char **argv) {
 		if ((rc = bh_sam_begin(g_sam, hhs[0], &Q, output_FN))) DIEP(rc);
 		if ((rc = bh_paths_set_sam(paths, g_sam, cigar))) DIEP(rc);
 	}
+	if (g_cons && (rc = bh_paths_set_consensus(paths, g_cons, cigar))) DIEP(rc);
 	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em || clu ? &sink : NULL, paths))) DIEP(rc);
 	if (fclose(output)) { fprintf(stderr, "ERROR: write failed: %s\n", output_FN); return 2; }      /* (the last buffer of the report: a full disk must not end in exit code 0) */
 	printf("Wrote %lu alignments\n", (unsigned long)lines);
@@ -917,6 +976,13 @@ int main(int argc, char **argv) {
 		printf("Variants table written: %svariants.txt\n", var_prefix);
 		PHASE("variants");
 		bh_pile_close(pile); pile = NULL;
+	}
+	if (g_cons) {   /* a study of one sample: its block, then both files get their names (a failure: the exit handler removes the temporary files) */
+		if ((rc = bh_consensus_sample(g_cons, hhs[0], output_FN, Q.codes, Q.qoff, Q.numEntries)) || (rc = bh_consensus_write(g_cons))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
+		bh_consensus_print_info(g_cons);
+		printf("Consensus written: %sconsensus.fa, %sconsensus.txt\n", cons_prefix, cons_prefix);
+		PHASE("consensus");
+		bh_consensus_close(g_cons); g_cons = NULL;
 	}
 	if (cov) {      /* a study of one sample: the Dataset column and the sample's (rank 0's handle; the lines exist only here) */
 		if ((shard_db && (rc = bh_cov_lengths_host(cov))) || (rc = bh_cov_sample(cov, hhs[0], output_FN, sink.lines, sink.n)) || (rc = bh_cov_write(cov))) DIE(rc);

@@ -326,6 +326,27 @@ def lib():
         L.bh_session_set_chimera.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_session_set_variants.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_session_set_variants.restype = None
+        L.bh_consensus_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        L.bh_consensus_open_heads.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        L.bh_consensus_set_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_consensus_set_solver.restype = None
+        L.bh_consensus_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BhPathBuf), C.c_uint64]
+        L.bh_consensus_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.bh_consensus_sample_failed.argtypes = [C.c_void_p, C.c_char_p]
+        L.bh_consensus_abort.argtypes = [C.c_void_p]
+        L.bh_consensus_abort.restype = None
+        L.bh_consensus_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.bh_consensus_rows.restype = C.c_uint64
+        L.bh_consensus_write.argtypes = [C.c_void_p]
+        L.bh_consensus_print_info.argtypes = [C.c_void_p]
+        L.bh_consensus_print_info.restype = None
+        L.bh_consensus_last_info.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.bh_consensus_last_info.restype = None
+        L.bh_consensus_close.argtypes = [C.c_void_p]
+        L.bh_consensus_close.restype = None
+        L.bh_consensus_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                        C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+        L.bh_session_set_consensus.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_sam_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
         L.bh_sam_open_heads.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.bh_sam_set_md.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -553,6 +574,31 @@ def pile_refs(packed, clump_len, tot_refs):
     r._keep = (np.ascontiguousarray(packed, dtype=np.uint8), np.ascontiguousarray(clump_len, dtype=np.uint32))
     r.packed, r.clump_len, r.n_clumps, r.tot_refs = r._keep[0].ctypes.data, r._keep[1].ctypes.data, len(r._keep[1]), int(tot_refs)
     return r
+
+
+# BhConsRow, 48 bytes: a row of PREFIXconsensus.txt (header = the database's unique-header number, sample = its place in the study)
+CONS_ROW_DTYPE = np.dtype([(n, "<u4") for n in ("header", "sample", "length", "covered", "called", "same", "subst", "del", "ambig", "ins_major", "record", "pad")])
+
+
+def consensus_host(refs, q_codes, q_off, lines, ops, min_depth=4, seg_cap=None, letter_cap=None):
+    """bh_consensus_host, the consensus definition in plain C (no device; one record per observed base): (segments capi.CONS_SEG_DTYPE,
+    letters bytes, info uint64 [8]: events, candidate sites, segments, covered positions).  refs: pile_refs(...); the rest as pile_host"""
+    q_codes, q_off = np.ascontiguousarray(q_codes, dtype=np.uint8), np.ascontiguousarray(q_off, dtype=np.uint64)
+    lines, ops = capi.pile_lines(lines), np.ascontiguousarray(ops, dtype=np.uint32)
+    seg_cap = max(len(lines), 16) if seg_cap is None else int(seg_cap)
+    letter_cap = 1 << 16 if letter_cap is None else int(letter_cap)
+    ns, nl, info = C.c_uint64(0), C.c_uint64(0), np.zeros(8, np.uint64)
+    for _ in range(2):
+        segs, letters = np.zeros(max(seg_cap, 1), capi.CONS_SEG_DTYPE), np.zeros(max(letter_cap, 1), np.uint8)
+        rc = lib().bh_consensus_host(C.byref(refs), q_codes.ctypes.data, q_off.ctypes.data, len(q_off) - 1, lines.ctypes.data, len(lines), ops.ctypes.data, len(ops),
+                                     int(min_depth), segs.ctypes.data, seg_cap, C.byref(ns), letters.ctypes.data, letter_cap, C.byref(nl), info.ctypes.data)
+        if rc != E_CAPACITY or (ns.value <= seg_cap and nl.value <= letter_cap):
+            break
+        seg_cap, letter_cap = max(seg_cap, ns.value), max(letter_cap, nl.value)
+    if rc == E_CAPACITY:
+        raise HostError("bh_consensus_host: %d segments and %d letters, room for %d and %d" % (ns.value, nl.value, seg_cap, letter_cap))
+    _chk(rc)
+    return segs[:ns.value], letters[:nl.value].tobytes(), info
 
 
 def pile_host(refs, q_codes, q_off, lines, ops, min_depth=4, min_alt=2, cap=None):
@@ -919,7 +965,8 @@ class Session:
                  variants=None, variants_min_depth=4, variants_min_alt=2, variants_reads="all", variants_host=False,
                  cluster=None, cluster_sizes=False, cluster_host=False,
                  chimeras=None, chimera_sizes=False, chimera_skew=2, chimera_min_seg=16, chimera_min_gain=3, chimera_host=False,
-                 sam=False, sam_unmapped=False, sam_lengths=None, sam_md=None):
+                 sam=False, sam_unmapped=False, sam_lengths=None, sam_md=None,
+                 consensus=None, consensus_min_depth=4, consensus_min_breadth=0, consensus_reads="all", consensus_lengths=None, consensus_host=False):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
         reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
         process only).
@@ -949,7 +996,13 @@ class Session:
         MD tags -- bhip_md_tags on rank 0's device handle, one call per traced group); sam_unmapped: behind them a FLAG 4 record per read
         without a line, in query-file order; sam_lengths: a `name<TAB>length` table for the @SQ lines (default: the database's own extents).
         sam_md: an MD_FN in place of the device's function (tests).  Opens the path tracer without adding the cigar columns; same limits as
-        cigar; goes with variants and chimeras, not with mates.  sam_info() has the last sample's figures."""
+        cigar; goes with variants and chimeras, not with mates.  sam_info() has the last sample's figures.
+        consensus = prefix: every reported sample gets a block of prefix + "consensus.fa" and prefix + "consensus.txt" (bh_consensus.c: per
+        reference header the letters the sample's reads show, in reference coordinates; a position is called at consensus_min_depth reads, a
+        record written at consensus_min_breadth permille of the header's length; consensus_reads "unique": only reads printed on one line;
+        consensus_lengths: a `name<TAB>length` table, default the database's own extents), from ONE bhip_consensus_run per sample on rank
+        0's device handle -- or bh_consensus_host with consensus_host=True; consensus() returns the table's rows so far, close() writes both
+        files unless the session ended on an error.  Same limits as variants; goes with them, coverage, abundance, cigar and sam."""
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
         self._mates_join = mates_join
         self.cov, self.em, self.pile, self.cluster, self.chimera = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -989,6 +1042,7 @@ class Session:
             o.tax = C.pointer(self.taxo)
         self.ended = False
         self.cov_aborted = False
+        self.cons = C.c_void_p()
         if coverage is not None and (rank == 0 or len(devs) > 1):      # (in a job of processes the lines exist only where rank 0 reports)
             _chk(lib().bh_cov_open(C.byref(db.c), coverage.encode(), coverage_lengths.encode() if coverage_lengths else None, int(coverage_pad), C.byref(self.cov)))
             if coverage_tap is not None:
@@ -1040,6 +1094,20 @@ class Session:
             _chk(lib().bh_chimera_open(chimeras.encode(), int(bool(chimera_sizes)), int(chimera_skew), int(chimera_min_seg), int(chimera_min_gain), C.byref(self.chimera)))
             if chimera_host:
                 lib().bh_chimera_set_solver(self.chimera, C.cast(lib().bh_chimera_host, C.c_void_p), None)
+        if consensus is not None:
+            if consensus_reads not in ("all", "unique") or not 1 <= int(consensus_min_depth) < 1 << 31 or not 0 <= int(consensus_min_breadth) <= 1000:
+                raise ValueError("consensus: reads all|unique, 1 <= min_depth < 2^31, 0 <= min_breadth <= 1000")
+            if shard_db and int(shard_db) > 1:
+                raise ValueError("consensus: the paths are traced on one handle, which must hold the whole database (no shard_db)")
+            if align is not None or world != n_local:
+                raise ValueError("consensus: needs the device handles of one process (no align back end, no job of processes)")
+            if cluster is not None or chimeras is not None:
+                raise ValueError("consensus: per-reference outputs of a self-alignment are out of scope (no cluster, no chimeras)")
+            _chk(lib().bh_consensus_open(C.byref(db.c), consensus.encode(), consensus_lengths.encode() if consensus_lengths else None, int(consensus_min_depth),
+                                         int(consensus_min_breadth), int(consensus_reads == "unique"), C.byref(self.cons)))
+            if consensus_host:
+                self._cons_refs = BhPileRefs(C.cast(db.c.packed, C.c_void_p), C.cast(db.c.clumpLen, C.c_void_p), db.c.numRclumps, db.c.totR)
+                lib().bh_consensus_set_solver(self.cons, C.cast(lib().bh_consensus_host, C.c_void_p), C.cast(C.pointer(self._cons_refs), C.c_void_p))
         if (sam_unmapped or sam_lengths) and not sam:
             raise ValueError("sam_unmapped and sam_lengths go with sam=True")
         if sam:
@@ -1055,6 +1123,8 @@ class Session:
             _chk(lib().bh_session_open(C.byref(db.c), self.ranks, n_local, world, comm, node.h if node is not None else None, C.byref(o), C.byref(self.h)))
             if self.sam:
                 _chk(lib().bh_session_set_sam(self.h, self.sam))
+            if self.cons:
+                _chk(lib().bh_session_set_consensus(self.h, self.cons))
             if self.cluster:
                 _chk(lib().bh_session_set_cluster(self.h, self.cluster))
             if self.chimera:
@@ -1063,7 +1133,7 @@ class Session:
             if self.h:
                 lib().bh_session_close(self.h)
                 self.h = C.c_void_p()
-            for name, close in (("sam", lib().bh_sam_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
+            for name, close in (("sam", lib().bh_sam_close), ("cons", lib().bh_consensus_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
                 if getattr(self, name):
                     close(getattr(self, name))
                     setattr(self, name, C.c_void_p())
@@ -1217,6 +1287,24 @@ class Session:
         d["lines"] = lines.value
         return d
 
+    def consensus(self):
+        """the rows of the consensus table so far (CONS_ROW_DTYPE: header = the database's unique-header number, sample = its place in the study,
+        length, covered, called, same, subst, del, ambig, ins_major, record), in the table's order"""
+        if not self.cons:
+            raise HostError("the session has no consensus")
+        n = lib().bh_consensus_rows(self.cons, None, 0)
+        rows = np.zeros(max(n, 1), CONS_ROW_DTYPE)
+        lib().bh_consensus_rows(self.cons, rows.ctypes.data, n)
+        return rows[:n]
+
+    def consensus_info(self):
+        """the last called sample's figures: events, candidates, segments, covered, device_us, peak_bytes, lines, records"""
+        info, lines, records = np.zeros(8, np.uint64), C.c_uint64(), C.c_uint64()
+        lib().bh_consensus_last_info(self.cons, info.ctypes.data, C.byref(lines), C.byref(records))
+        d = dict(zip(capi.CONS_INFO, (int(x) for x in info)))
+        d["lines"], d["records"] = lines.value, records.value
+        return d
+
     def clusters(self):
         """the last sample's clustering: (centroid uint32 [reads], edits uint32 [reads]) per read in file order -- the number of its centroid
         (its own for a centroid) and the edits of the line that joined it"""
@@ -1275,6 +1363,11 @@ class Session:
                     err = lib().bh_last_error().decode("utf-8", "replace")
                 lib().bh_pile_close(self.pile)
                 self.pile = C.c_void_p()
+            if self.cons:
+                if not lib().bh_session_ended(self.h) and not self.cov_aborted and lib().bh_consensus_write(self.cons):
+                    err = lib().bh_last_error().decode("utf-8", "replace")
+                lib().bh_consensus_close(self.cons)
+                self.cons = C.c_void_p()
             if self.cluster:      # (its tables were written when the sample was reported)
                 lib().bh_cluster_close(self.cluster)
                 self.cluster = C.c_void_p()

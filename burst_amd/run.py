@@ -223,7 +223,15 @@ def main(argv=None):
     ap.add_argument("--sam", action="store_true", help="not available here: SAM records are written by burst_hip --sam (one process, the host gather)")
     ap.add_argument("--sam-unmapped", action="store_true", help="not available here: goes with burst_hip --sam")
     ap.add_argument("--sam-lengths", metavar="FILE", help="not available here: goes with burst_hip --sam")
+    ap.add_argument("--consensus", metavar="PREFIX", help="not available here: consensus sequences are written by burst_hip --consensus (one process, the host gather)")
+    ap.add_argument("--consensus-min-depth", metavar="N", help="not available here: goes with burst_hip --consensus")
+    ap.add_argument("--consensus-min-breadth", metavar="PERMILLE", help="not available here: goes with burst_hip --consensus")
+    ap.add_argument("--consensus-reads", metavar="all|unique", help="not available here: goes with burst_hip --consensus")
+    ap.add_argument("--consensus-lengths", metavar="FILE", help="not available here: goes with burst_hip --consensus")
     args = ap.parse_args(argv)
+    if args.consensus or args.consensus_min_depth or args.consensus_min_breadth or args.consensus_reads or args.consensus_lengths:      # (exit code 1, as burst_hip refuses what it cannot do)
+        print("ERROR: --consensus is not available in python -m burst_amd.run: use burst_hip --consensus (one process, --gpus N with the host gather)", flush=True)
+        return 1
     if args.sam or args.sam_unmapped or args.sam_lengths:      # (exit code 1, as burst_hip refuses what it cannot do)
         print("ERROR: --sam is not available in python -m burst_amd.run: use burst_hip --sam (one process, --gpus N with the host gather)", flush=True)
         return 1

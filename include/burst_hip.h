@@ -441,6 +441,41 @@ BHIP_API int bhip_pile_run(void *handle, const uint8_t *q_codes, const uint64_t 
                            const BhipPileLine *lines, uint64_t n_lines, const uint32_t *ops, uint64_t n_ops,
                            uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]);
 
+/* Consensus: the sequence one sample's reads show on every reference position they cover (burst_hip --consensus; no reference counterpart:
+ * the definition is this project's own).  A function of the sample's printed lines, all integer arithmetic, bit-exact on any machine.
+ * Lines, observations, classes, Depth, the counts A C G T Del Other, Ins and Ref are exactly those of "Variant sites" above (a reverse line
+ * carries the path of its reverse-complement entry, so letters are forward-strand; a duplicate read is a line of its own).
+ *   COVERED   a position of a header with Depth >= 1.  A SEGMENT is a maximal run of consecutive covered positions of one header: a line
+ *             that ends at p and one that starts at p + 1 are one segment, a gap of one position makes two.
+ *   CALL      at a covered position, m = min_depth (policy, not a measurement):
+ *             1. Depth < m: the letter is N (not called).
+ *             2. else, Ref not A/C/G/T: the reference's own letter, "NACGTNKMRYSWBVHD"[Ref] (AMBIGUOUS; plain observations on such a
+ *                column carry no class the device keeps, and the variants never report these sites either).
+ *             3. else the largest of the five counts A, C, G, T, Del; among equal largest counts the class of Ref if it is one of them,
+ *                otherwise the first in that order.  Other is part of Depth and never wins.  The letter is A/C/G/T, or '-' for Del.
+ *   FIGURES   per segment: called = positions with Depth >= m; same, subst, del = rule-3 positions whose letter equals Ref, is another base,
+ *             is '-'; ambig = rule-2 positions; ins_major = called positions with 2 * Ins > Depth (most reads insert behind the column,
+ *             which a record in reference coordinates cannot show).  called = same + subst + del + ambig.
+ * Segments come back in ascending (header, pos) order; segment s owns letters[off .. off + len), and the offsets are the running sum of
+ * the lengths.  The cost follows lines + events + covered positions (csrc/bhip_consensus.hip): events and candidate
+ * sites as the variants take them; the segments from a max-scan of the one-past-ends in start order; the depth of every covered position
+ * as the stabbing count of two sorted arrays, with cursors that move forwards along a thread's run of positions; the reference code from
+ * the lane column of one covering line (lanes that share a position agree there; the definition says the smallest code, the device takes
+ * any covering lane's); the candidate sites then replace their letters.  The figures are integer sums: no order of threads matters.
+ * The inputs and the BHIP_E_ARG checks are those of bhip_pile_run, before any device memory is touched and with the handle staying usable;
+ * also for min_depth == 0 or > 2^31 - 1, and for more than 2^31 - 1 covered positions in one call (never a truncated result).
+ * BHIP_E_CAPACITY when seg_cap or letter_cap is too small: *n_segs and *n_letters are the numbers wanted, nothing is written, the handle
+ * stays usable.  n_lines == 0: no segments, nothing is launched.
+ * info (may be NULL; bhip_consensus_info returns that of the last call on the handle): [0] events, [1] candidate sites, [2] segments, [3]
+ * covered positions, [4] device microseconds (HIP events around everything launched), [5] peak device bytes of the scratch buffers (shared
+ * with bhip_pile_run; the handle keeps them, bhip_destroy frees them), [6..7] 0. */
+typedef struct BhipConsSeg { uint32_t header, pos, len, called, same, subst, del, ambig, ins_major, pad; uint64_t off; } BhipConsSeg;
+BHIP_API int bhip_consensus_run(void *handle, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries,
+                                const BhipPileLine *lines, uint64_t n_lines, const uint32_t *ops, uint64_t n_ops, uint32_t min_depth,
+                                BhipConsSeg *segs, uint64_t seg_cap, uint64_t *n_segs, char *letters, uint64_t letter_cap, uint64_t *n_letters,
+                                uint64_t info[8]);
+BHIP_API int bhip_consensus_info(void *handle, uint64_t info[8]);
+
 /* Clustering: greedy centroid clusters of the reads of a query file from the lines it prints against itself (burst_hip --cluster; no
  * reference counterpart: its README lists clustering "as an output mode" as planned and names the recipe -- the queries as their own
  * references in FORAGE, then clusters picked from that hit graph).  All of it is integer arithmetic, bit-exact on any machine.
