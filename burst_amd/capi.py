@@ -49,6 +49,7 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
            "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_pile_run", "bhip_consensus_run", "bhip_consensus_info",
+           "bhip_alleles_run", "bhip_alleles_info",
            "bhip_cluster_run", "bhip_cluster_info", "bhip_chimera_run", "bhip_chimera_info", "bhip_md_tags"]
 
 # BhipMateLine, 20 bytes: pair and header numbers, .b6 columns 9 and 10 (signed), column 11
@@ -93,6 +94,10 @@ CONS_SEG_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("len", "<u4"), ("
                            ("ins_major", "<u4"), ("pad", "<u4"), ("off", "<u8")])
 assert CONS_SEG_DTYPE.itemsize == 48
 CONS_INFO = ("events", "candidates", "segments", "covered", "device_us", "peak_bytes")
+# BhipAllele, 40 bytes: an indel allele behind the anchor (header, pos) (bhip_alleles_run).  allele: Del(n) = n; Ins = n << 60 | c1 << 56 | ...
+ALLELE_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("allele", "<u8"), ("ref", "<u4"), ("depth", "<u4"), ("count", "<u4"), ("pad", "<u4"), ("code_off", "<u8")])
+assert ALLELE_DTYPE.itemsize == 40
+ALLELES_INFO = ("events", "distinct", "alleles", "skipped_end", "skipped_adjacent", "skipped_long", "device_us", "peak_bytes")
 MD_INFO = ("device_us", "requests", "md_bytes", "peak_bytes")
 
 # BhipClusterEdge, 12 bytes: read q has a printed line against read r with this many edits (bhip_cluster_run)
@@ -271,6 +276,10 @@ def _load():
     lib.bhip_consensus_run.restype = i32
     lib.bhip_consensus_info.argtypes = [vp, vp]
     lib.bhip_consensus_info.restype = i32
+    lib.bhip_alleles_run.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), vp]
+    lib.bhip_alleles_run.restype = i32
+    lib.bhip_alleles_info.argtypes = [vp, vp]
+    lib.bhip_alleles_info.restype = i32
     lib.bhip_cluster_run.argtypes = [vp, u32, vp, vp, u64, vp, vp]
     lib.bhip_cluster_run.restype = i32
     lib.bhip_cluster_info.argtypes = [vp, vp]
@@ -582,6 +591,32 @@ class Device:
         info = np.zeros(8, np.uint64)
         _chk(lib().bhip_consensus_info(self._h, _ptr(info)))
         return dict(zip(CONS_INFO, (int(x) for x in info)))
+
+    def alleles_run(self, q, lines, ops, min_depth=4, min_alt=2, cap=None, code_cap=None):
+        """the indel alleles of one sample (bhip_alleles_run).  q, lines, ops: as pile_run takes them.  Returns (alleles ALLELE_DTYPE in the
+        defined order, codes uint8: a Del(n) owns codes[code_off : code_off + n], the reference codes it deletes); alleles_info() has the
+        call's figures.  cap / code_cap: room offered at first; a capacity answer is retried once with the wanted room"""
+        lines = pile_lines(lines)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        cap = max(len(lines), 16) if cap is None else int(cap)
+        code_cap = 1 << 12 if code_cap is None else int(code_cap)
+        na, nc, info = C.c_uint64(0), C.c_uint64(0), np.zeros(8, np.uint64)
+        for _ in range(2):
+            out, codes = np.zeros(max(cap, 1), ALLELE_DTYPE), np.zeros(max(code_cap, 1), np.uint8)
+            rc = lib().bhip_alleles_run(self._h, _ptr(q.codes), _ptr(q.off), q.n, _ptr(lines), len(lines), _ptr(ops), len(ops), int(min_depth), int(min_alt),
+                                        _ptr(out), cap, C.byref(na), _ptr(codes), code_cap, C.byref(nc), _ptr(info))
+            if rc != BHIP_E_CAPACITY or (na.value <= cap and nc.value <= code_cap):
+                break
+            cap, code_cap = max(cap, na.value), max(code_cap, nc.value)
+        _chk(rc)
+        return out[:na.value], codes[:nc.value]
+
+    def alleles_info(self):
+        """the last alleles_run's figures (bhip_alleles_info): events, distinct, alleles, skipped_end, skipped_adjacent, skipped_long, device_us,
+        peak_bytes"""
+        info = np.zeros(8, np.uint64)
+        _chk(lib().bhip_alleles_info(self._h, _ptr(info)))
+        return dict(zip(ALLELES_INFO, (int(x) for x in info)))
 
     def cluster_run(self, weights, edges):
         """greedy centroid clusters (bhip_cluster_run).  weights: uint32 per node (read), edges: CLUSTER_EDGE_DTYPE array (or rows q, r, edits), raw

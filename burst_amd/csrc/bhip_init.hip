@@ -75,6 +75,7 @@ extern "C" void bhip_destroy(void *handle) {
 	bhip_mates_release(h);
 	bhip_em_release(h);
 	bhip_consensus_release(h);
+	bhip_alleles_release(h);
 	bhip_pile_release(h);
 	bhip_cluster_release(h);
 	bhip_chimera_release(h);

@@ -37,6 +37,39 @@ static uint8_t ref_code(const BhPileRefs *R, const uint64_t *clump_off, uint32_t
 	return (col0 & 1u) ? b >> 4 : b & 15u;
 }
 
+/* the checks of a solver's lines in plain C (bhip_pile_run's, `who` opens the texts); *n_obs: an upper bound of the records a walk writes */
+int bh_pile_check_lines(const char *who, const BhPileRefs *R, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
+                        const uint32_t *ops, uint64_t n_ops, uint64_t *n_obs_out) {
+	uint64_t n_obs = 0, wsum = 0;
+	if (n_lines && (!R || !R->clump_len || !lines || !q_off || (n_ops && !ops))) return bh_set_error(BH_E_USAGE, "%s: null argument", who);
+	for (uint64_t i = 0; i < n_lines; ++i) {
+		const BhipPileLine *u = &lines[i];
+		if (u->q >= n_queries || q_off[u->q + 1] < q_off[u->q]) return bh_set_error(BH_E_USAGE, "%s: line %llu names query %u of %u", who, (unsigned long long)i, u->q, n_queries);
+		if (u->refIx >= 16ull * R->n_clumps || u->refIx >= R->tot_refs) return bh_set_error(BH_E_USAGE, "%s: line %llu names reference %u of %u", who, (unsigned long long)i, u->refIx, R->tot_refs);
+		if (u->op_off > n_ops || u->n_ops > n_ops - u->op_off) return bh_set_error(BH_E_USAGE, "%s: line %llu owns ops %llu + %u of %llu", who, (unsigned long long)i, (unsigned long long)u->op_off, u->n_ops, (unsigned long long)n_ops);
+		uint64_t on_q = 0, on_r = 0; uint32_t last = 0;
+		for (uint32_t k = 0; k < u->n_ops; ++k) {
+			const uint32_t word = ops[u->op_off + k], len = word >> 4, code = word & 15u;
+			if (!len || code == last || (code != BHIP_OP_I && code != BHIP_OP_D && code != BHIP_OP_EQ && code != BHIP_OP_X))
+				return bh_set_error(BH_E_USAGE, "%s: line %llu, op %u: word 0x%x is not a run of I, D, = or X, or repeats the op before it", who, (unsigned long long)i, k, word);
+			last = code;
+			if (code != BHIP_OP_D) on_q += len;
+			if (code != BHIP_OP_I) on_r += len;
+		}
+		if (on_q != q_off[u->q + 1] - q_off[u->q]) return bh_set_error(BH_E_USAGE, "%s: line %llu: its ops consume %llu query symbols, query %u has %llu", who, (unsigned long long)i,
+			(unsigned long long)on_q, u->q, (unsigned long long)(q_off[u->q + 1] - q_off[u->q]));
+		if (u->ref_first < 1 || (uint64_t)u->ref_first - 1 + on_r > R->clump_len[u->refIx >> 4])
+			return bh_set_error(BH_E_USAGE, "%s: line %llu: columns %u + %llu leave a clump of %u", who, (unsigned long long)i, u->ref_first, (unsigned long long)on_r, R->clump_len[u->refIx >> 4]);
+		if (u->pos < 1 || (uint64_t)u->pos + on_r > 0xFFFFFFFFull) return bh_set_error(BH_E_USAGE, "%s: line %llu: position %u + %llu columns (1 .. 2^32 - 1)", who, (unsigned long long)i, u->pos, (unsigned long long)on_r);
+		if (!u->w) return bh_set_error(BH_E_USAGE, "%s: line %llu has weight 0", who, (unsigned long long)i);
+		wsum += u->w;
+		if (wsum > 0x7FFFFFFFull) return bh_set_error(BH_E_USAGE, "%s: the lines stand for more than 2^31 - 1 reads (line %llu)", who, (unsigned long long)i);
+		n_obs += on_r + u->n_ops;
+	}
+	if (n_obs_out) *n_obs_out = n_obs;
+	return BH_OK;
+}
+
 int bh_pile_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
                  const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]) {
 	const BhPileRefs *R = refs;
@@ -47,31 +80,8 @@ int bh_pile_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off, uint
 		return bh_set_error(BH_E_USAGE, "bh_pile_host: null argument");
 	*n_sites = 0;
 	if (!min_depth || !min_alt) return bh_set_error(BH_E_USAGE, "bh_pile_host: min_depth %u, min_alt %u (1 .. 2^31 - 1 each)", min_depth, min_alt);
-	uint64_t n_obs = 0, wsum = 0;
-	for (uint64_t i = 0; i < n_lines; ++i) {
-		const BhipPileLine *u = &lines[i];
-		if (u->q >= n_queries || q_off[u->q + 1] < q_off[u->q]) return bh_set_error(BH_E_USAGE, "bh_pile_host: line %llu names query %u of %u", (unsigned long long)i, u->q, n_queries);
-		if (u->refIx >= 16ull * R->n_clumps || u->refIx >= R->tot_refs) return bh_set_error(BH_E_USAGE, "bh_pile_host: line %llu names reference %u of %u", (unsigned long long)i, u->refIx, R->tot_refs);
-		if (u->op_off > n_ops || u->n_ops > n_ops - u->op_off) return bh_set_error(BH_E_USAGE, "bh_pile_host: line %llu owns ops %llu + %u of %llu", (unsigned long long)i, (unsigned long long)u->op_off, u->n_ops, (unsigned long long)n_ops);
-		uint64_t on_q = 0, on_r = 0; uint32_t last = 0;
-		for (uint32_t k = 0; k < u->n_ops; ++k) {
-			const uint32_t word = ops[u->op_off + k], len = word >> 4, code = word & 15u;
-			if (!len || code == last || (code != BHIP_OP_I && code != BHIP_OP_D && code != BHIP_OP_EQ && code != BHIP_OP_X))
-				return bh_set_error(BH_E_USAGE, "bh_pile_host: line %llu, op %u: word 0x%x is not a run of I, D, = or X, or repeats the op before it", (unsigned long long)i, k, word);
-			last = code;
-			if (code != BHIP_OP_D) on_q += len;
-			if (code != BHIP_OP_I) on_r += len;
-		}
-		if (on_q != q_off[u->q + 1] - q_off[u->q]) return bh_set_error(BH_E_USAGE, "bh_pile_host: line %llu: its ops consume %llu query symbols, query %u has %llu", (unsigned long long)i,
-			(unsigned long long)on_q, u->q, (unsigned long long)(q_off[u->q + 1] - q_off[u->q]));
-		if (u->ref_first < 1 || (uint64_t)u->ref_first - 1 + on_r > R->clump_len[u->refIx >> 4])
-			return bh_set_error(BH_E_USAGE, "bh_pile_host: line %llu: columns %u + %llu leave a clump of %u", (unsigned long long)i, u->ref_first, (unsigned long long)on_r, R->clump_len[u->refIx >> 4]);
-		if (u->pos < 1 || (uint64_t)u->pos + on_r > 0xFFFFFFFFull) return bh_set_error(BH_E_USAGE, "bh_pile_host: line %llu: position %u + %llu columns (1 .. 2^32 - 1)", (unsigned long long)i, u->pos, (unsigned long long)on_r);
-		if (!u->w) return bh_set_error(BH_E_USAGE, "bh_pile_host: line %llu has weight 0", (unsigned long long)i);
-		wsum += u->w;
-		if (wsum > 0x7FFFFFFFull) return bh_set_error(BH_E_USAGE, "bh_pile_host: the lines stand for more than 2^31 - 1 reads (line %llu)", (unsigned long long)i);
-		n_obs += on_r + u->n_ops;
-	}
+	uint64_t n_obs = 0;
+	{ const int rc = bh_pile_check_lines("bh_pile_host", R, q_off, n_queries, lines, n_lines, ops, n_ops, &n_obs); if (rc) return rc; }
 	if (!n_lines) return BH_OK;
 	uint64_t *clump_off = malloc(((size_t)R->n_clumps + 1) * 8);
 	PileObs *ob = malloc((n_obs + 1) * sizeof(*ob));
@@ -139,7 +149,7 @@ static int solve_device(void *ctx, const uint8_t *q_codes, const uint64_t *q_off
 	return BH_OK;
 }
 
-static char *sample_name(const char *path) {      /* base name without its last extension (as the coverage names its columns) */
+char *bh_pile_sample_name(const char *path) {      /* base name without its last extension (as the coverage names its columns) */
 	const char *b = strrchr(path, '/');
 	b = b ? b + 1 : path;
 	char *s = strdup(b);
@@ -197,6 +207,29 @@ int bh_pile_open(const BhDb *db, const char *prefix, uint32_t min_depth, uint32_
 	return rc;
 }
 
+/* a collector alone (bh_vcf.c): no table, no file; the lines keep the header numbers they come with */
+int bh_pile_open_lines(uint32_t n_headers, int unique_only, BhPile **out) {
+	if (!out) return bh_set_error(BH_E_USAGE, "bh_pile_open_lines: no place for the object");
+	*out = NULL;
+	if (!n_headers) return bh_set_error(BH_E_USAGE, "bh_pile_open_lines: no headers");
+	BhPile *pl = calloc(1, sizeof(*pl));
+	if (!pl) return bh_set_error(BH_E_OOM, "OOM:variants");
+	pl->nH = n_headers; pl->minDepth = pl->minAlt = 1; pl->uniqueOnly = unique_only != 0;
+	pl->rank = malloc((size_t)n_headers * 4); pl->byRank = malloc((size_t)n_headers * 4);
+	if (!pl->rank || !pl->byRank) { bh_pile_close(pl); return bh_set_error(BH_E_OOM, "OOM:variants"); }
+	for (uint32_t h = 0; h < n_headers; ++h) pl->rank[h] = pl->byRank[h] = h;
+	*out = pl;
+	return BH_OK;
+}
+uint64_t bh_pile_lines(const BhPile *pl, const BhipPileLine **lines, const uint32_t **ops, uint64_t *n_ops, uint64_t *n_printed) {
+	if (lines) *lines = pl ? pl->lines : NULL;
+	if (ops) *ops = pl ? pl->ops : NULL;
+	if (n_ops) *n_ops = pl ? pl->nOps : 0;
+	if (n_printed) *n_printed = pl ? pl->nPrinted : 0;
+	return pl ? pl->nLines : 0;
+}
+void bh_pile_drop_lines(BhPile *pl) { if (pl) pl->nLines = pl->nOps = pl->nPrinted = 0; }
+
 void bh_pile_set_solver(BhPile *pl, bh_pile_solver_fn fn, void *ctx) { if (pl) { pl->fn = fn; pl->ctx = ctx; } }
 void bh_pile_abort(BhPile *pl) { if (pl && !pl->dead) pl->dead = BH_E_DEVICE; }
 
@@ -206,7 +239,7 @@ static void drop_lines(BhPile *pl) { pl->nLines = pl->nOps = pl->nPrinted = 0; }
 static int new_sample(BhPile *pl, const char *out_path) {
 	char **nn = realloc(pl->names, ((size_t)pl->nSamples + 1) * sizeof(*nn));
 	if (nn) pl->names = nn;
-	char *nm = sample_name(out_path ? out_path : "sample");
+	char *nm = bh_pile_sample_name(out_path ? out_path : "sample");
 	if (!nn || !nm) { free(nm); return bh_set_error(BH_E_OOM, "OOM:variants"); }
 	pl->names[pl->nSamples++] = nm;
 	return BH_OK;

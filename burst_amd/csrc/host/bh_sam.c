@@ -82,6 +82,35 @@ static size_t name_len(const char *s) { size_t n = 0; while (s[n] && s[n] != ' '
 typedef struct { const char *sn, *head; } SnRow;
 static int sn_cmp(const void *a, const void *b) { return strcmp(((const SnRow *)a)->sn, ((const SnRow *)b)->sn); }
 
+/* SN of every header: the header up to its first white space.  Two different headers must not share one (`flag` opens the error text) */
+int bh_sam_names(const char *flag, uint32_t n_headers, const char *const *heads, char ***out) {
+	if (!out || !flag) return bh_set_error(BH_E_USAGE, "bh_sam_names: no place for the names");
+	*out = NULL;
+	if (!n_headers || !heads) return bh_set_error(BH_E_USAGE, "bh_sam_names: no headers");
+	char **sn = calloc(n_headers, sizeof(*sn));
+	SnRow *rows = malloc((size_t)n_headers * sizeof(*rows));
+	int ok = sn && rows;
+	for (uint32_t h = 0; ok && h < n_headers; ++h) {
+		const char *s = heads[h] ? heads[h] : "";
+		ok = (sn[h] = strndup(s, name_len(s))) != NULL;
+		if (ok) { rows[h].sn = sn[h]; rows[h].head = s; }
+	}
+	int rc = ok ? BH_OK : bh_set_error(BH_E_OOM, "OOM:sam");
+	if (ok) {
+		qsort(rows, n_headers, sizeof(*rows), sn_cmp);
+		for (uint32_t r = 1; r < n_headers && !rc; ++r) if (!strcmp(rows[r].sn, rows[r - 1].sn) && strcmp(rows[r].head, rows[r - 1].head))
+			rc = bh_set_error(BH_E_USAGE, "ERROR: %s: the reference headers '%s' and '%s' share the name '%s' (a header up to its first white space)", flag, rows[r - 1].head, rows[r].head, rows[r].sn);
+	}
+	free(rows);
+	if (rc) { bh_sam_names_free(sn, n_headers); return rc; }
+	*out = sn;
+	return BH_OK;
+}
+void bh_sam_names_free(char **sn, uint32_t n_headers) {
+	if (sn) for (uint32_t h = 0; h < n_headers; ++h) free(sn[h]);
+	free(sn);
+}
+
 int bh_sam_open_heads(uint32_t n_headers, const char *const *heads, const uint32_t *lengths, int unmapped, BhSam **out) {
 	if (!out) return bh_set_error(BH_E_USAGE, "bh_sam_open: no place for the object");
 	*out = NULL;
@@ -89,24 +118,10 @@ int bh_sam_open_heads(uint32_t n_headers, const char *const *heads, const uint32
 	BhSam *sm = calloc(1, sizeof(*sm));
 	if (!sm) return bh_set_error(BH_E_OOM, "OOM:sam");
 	sm->nH = n_headers; sm->unmapped = unmapped != 0;
-	sm->sn = calloc(n_headers, sizeof(*sm->sn));
 	sm->len = calloc(n_headers, 4);
-	SnRow *rows = malloc((size_t)n_headers * sizeof(*rows));
-	int ok = sm->sn && sm->len && rows;
-	for (uint32_t h = 0; ok && h < n_headers; ++h) {
-		const char *s = heads[h] ? heads[h] : "";
-		ok = (sm->sn[h] = strndup(s, name_len(s))) != NULL;
-		if (ok) { rows[h].sn = sm->sn[h]; rows[h].head = s; }
-	}
-	if (!ok) { free(rows); bh_sam_close(sm); return bh_set_error(BH_E_OOM, "OOM:sam"); }
-	/* SN is the header up to its first white space: two different headers must not share one */
-	qsort(rows, n_headers, sizeof(*rows), sn_cmp);
-	for (uint32_t r = 1; r < n_headers; ++r) if (!strcmp(rows[r].sn, rows[r - 1].sn) && strcmp(rows[r].head, rows[r - 1].head)) {
-		const int rc = bh_set_error(BH_E_USAGE, "ERROR: --sam: the reference headers '%s' and '%s' share the name '%s' (a header up to its first white space)", rows[r - 1].head, rows[r].head, rows[r].sn);
-		free(rows); bh_sam_close(sm);
-		return rc;
-	}
-	free(rows);
+	if (!sm->len) { bh_sam_close(sm); return bh_set_error(BH_E_OOM, "OOM:sam"); }
+	const int rc = bh_sam_names("--sam", n_headers, heads, &sm->sn);
+	if (rc) { bh_sam_close(sm); return rc; }
 	if (lengths) { memcpy(sm->len, lengths, (size_t)n_headers * 4); sm->have_len = 1; }
 	*out = sm;
 	return BH_OK;

@@ -42,6 +42,7 @@ struct BhSession {
 	BhChimera *chimera;             /* bh_session_set_chimera: NULL, or the chimera check every reported sample is given */
 	BhSam *sam;                     /* bh_session_set_sam: NULL, or the SAM writer every reported sample is given */
 	BhCons *cons;                   /* bh_session_set_consensus: NULL, or the consensus every reported sample feeds */
+	BhVcf *vcf;                     /* bh_session_set_vcf: NULL, or the VCF writer every reported sample is given */
 	BhPaths *paths;                 /* with o.cigar, o.pile, a consensus, a chimera check or a SAM writer: the tracer on the reporting rank's handle, opened by the first sample that reports */
 	int dead, dbg, threads_ok;
 	int alive;                      /* query tables alive (the current sample's and the prefetched one's) */
@@ -117,6 +118,7 @@ int bh_session_set_cluster(BhSession *s, BhCluster *cl) {
 	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_cluster: no session");
 	if (cl && s->o.mode != BH_FORAGE) return bh_set_error(BH_E_USAGE, "ERROR: clusters need every relationship under the identity cutoff: a session in mode FORAGE");
 	if (cl && s->cons) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with the consensus");
+	if (cl && s->vcf) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with the VCF output");
 	if (cl && (s->o.cov || s->o.em || s->o.pile || s->o.shard_db > 1)) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with coverage, abundance, variants or database shards");
 	s->cluster = cl;
 	return BH_OK;
@@ -125,6 +127,7 @@ int bh_session_set_chimera(BhSession *s, BhChimera *ch) {
 	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_chimera: no session");
 	if (ch && s->o.mode != BH_FORAGE) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check needs every relationship under the identity cutoff: a session in mode FORAGE");
 	if (ch && s->cons) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check does not go with the consensus");
+	if (ch && s->vcf) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check does not go with the VCF output");
 	if (ch && (s->o.cov || s->o.em || s->o.pile || s->o.shard_db > 1)) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check does not go with coverage, abundance, variants or database shards");
 	s->chimera = ch;
 	return BH_OK;
@@ -140,6 +143,13 @@ int bh_session_set_consensus(BhSession *s, BhCons *cons) {
 	if (cons && s->o.shard_db > 1) return bh_set_error(BH_E_USAGE, "ERROR: --consensus traces the paths on rank 0's handle, which must hold the whole database: it does not go with database shards");
 	if (cons && (s->cluster || s->chimera)) return bh_set_error(BH_E_USAGE, "ERROR: the consensus does not go with clusters or the chimera check");
 	s->cons = cons;
+	return BH_OK;
+}
+int bh_session_set_vcf(BhSession *s, BhVcf *vcf) {
+	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_vcf: no session");
+	if (vcf && s->o.shard_db > 1) return bh_set_error(BH_E_USAGE, "ERROR: --vcf traces the paths on rank 0's handle, which must hold the whole database: it does not go with database shards");
+	if (vcf && (s->cluster || s->chimera)) return bh_set_error(BH_E_USAGE, "ERROR: the VCF output does not go with clusters or the chimera check");
+	s->vcf = vcf;
 	return BH_OK;
 }
 const BhQueries *bh_session_sample(const BhSession *s) { return s && s->cur ? &s->cur->Q : NULL; }
@@ -183,6 +193,7 @@ static int sample_fail_ex(BhSession *s, BhSampleResult *res, int rc, const char 
 		else if (s->cov_name && !s->cons_col) (void)bh_consensus_sample_failed(s->cons, s->cov_name);
 	}
 	if (s->sam && s->i0 >= 0) { if (s->dead) bh_sam_abort(s->sam); else bh_sam_discard(s->sam); }      /* (no OUT.sam of a sample that failed) */
+	if (s->vcf && s->i0 >= 0) { if (s->dead) bh_vcf_abort(s->vcf); else bh_vcf_sample_failed(s->vcf); }      /* (no OUT.vcf either) */
 	free(s->cov_name); s->cov_name = NULL;
 	return bh_set_error(rc, "%s", res->err);
 }
@@ -197,7 +208,7 @@ int bh_session_load(BhSession *s, const char *queries, const char *out_path, BhS
 	if (s->cur) return bh_set_error(BH_E_USAGE, "bh_session_load: the previous sample has not been finished or dropped");
 	s->tLoad = wall();
 	free(s->cov_name); s->cov_name = NULL; s->cov_col = s->em_col = s->pile_col = s->cons_col = 0;
-	if ((s->o.cov || s->o.em || s->o.pile || s->cons) && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
+	if ((s->o.cov || s->o.em || s->o.pile || s->cons || s->vcf) && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
 	SessIngest *g = NULL;
 	/* the outstanding ingest is this sample's: take it.  If it is another one's (prefetched before this sample was named) it stays
 	 * outstanding and this sample is read here */
@@ -249,6 +260,7 @@ int bh_session_drop(BhSession *s) {
 	if (s->o.em && s->cur && s->cov_name && !s->dead) (void)bh_em_sample_failed(s->o.em, s->cov_name);
 	if (s->o.pile && s->cur && s->cov_name && !s->dead) (void)bh_pile_sample_failed(s->o.pile, s->cov_name);
 	if (s->cons && s->cur && s->cov_name && !s->dead) (void)bh_consensus_sample_failed(s->cons, s->cov_name);
+	if (s->vcf && s->cur) bh_vcf_sample_failed(s->vcf);
 	drop_sample(s);
 	return BH_OK;
 }
@@ -354,12 +366,13 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		const double tr = wall();
 		uint64_t lines = 0;
 		setvbuf(s->out, NULL, _IOFBF, 1 << 22);
-		rc = (o->cigar || o->pile || s->cons || s->chimera || s->sam) && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
+		rc = (o->cigar || o->pile || s->cons || s->vcf || s->chimera || s->sam) && !s->paths ? bh_paths_open(R[s->i0].hh, &s->paths) : BH_OK;
 		if (!rc && s->paths) bh_paths_set_pile(s->paths, o->pile, o->cigar);
 		if (!rc && s->chimera && !(rc = bh_chimera_begin(s->chimera, s->db, Q))) bh_paths_set_chimera(s->paths, s->chimera, o->cigar);
 		if (!rc && s->sam) rc = bh_sam_begin(s->sam, R[s->i0].hh, Q, s->out_path);
 		if (!rc && s->paths) rc = bh_paths_set_sam(s->paths, s->sam, o->cigar);
 		if (!rc && s->paths) rc = bh_paths_set_consensus(s->paths, s->cons, o->cigar);
+		if (!rc && s->paths) rc = bh_paths_set_vcf(s->paths, s->vcf, o->cigar);
 		s->sink.want_re = s->cluster != NULL;
 		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov || o->em || s->cluster ? &s->sink : NULL, s->paths);
 		if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
@@ -397,6 +410,12 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
 			if (o->verbose) bh_consensus_print_info(s->cons);
 			PHASE("consensus of the sample");
+		}
+		if (s->vcf) {      /* the sample's OUT.vcf: its sites and its alleles, one call each over the lines the tracer handed over */
+			rc = bh_vcf_sample(s->vcf, R[s->i0].hh, s->cov_name, Q->codes, Q->qoff, Q->numEntries);
+			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
+			if (o->verbose) bh_vcf_print_info(s->vcf);
+			PHASE("VCF of the sample");
 		}
 		if (s->cluster) {  /* the sample's reads clustered from its own lines, on rank 0's device as well; the tables at once */
 			rc = bh_cluster_sample(s->cluster, R[s->i0].hh, s->db, Q, &s->sink);
@@ -458,6 +477,7 @@ int bh_session_run_mates(BhSession *s, const char *queries1, const char *queries
 	if (s->o.em) return mates_fail(s, res, BH_E_USAGE, "ERROR: the abundance of paired output is out of scope: mates do not go with it");
 	if (s->o.pile) return mates_fail(s, res, BH_E_USAGE, "ERROR: variants of paired output are out of scope: mates do not go with them");
 	if (s->cons) return mates_fail(s, res, BH_E_USAGE, "ERROR: the consensus of paired output is out of scope: mates do not go with it");
+	if (s->vcf) return mates_fail(s, res, BH_E_USAGE, "ERROR: the VCF output of paired output is out of scope: mates do not go with it");
 	if (s->chimera) return mates_fail(s, res, BH_E_USAGE, "ERROR: the chimera check works from the lines of one query file against itself: mates do not go with it");
 	if (s->sam) return mates_fail(s, res, BH_E_USAGE, "ERROR: paired flags, RNEXT and TLEN are out of scope: mates do not go with the SAM output");
 	if (s->cluster) return mates_fail(s, res, BH_E_USAGE, "ERROR: clusters come from the lines of one query file against itself: mates do not go with them");

@@ -457,6 +457,15 @@ int  bh_pile_write(BhPile *pile);
 void bh_pile_print_info(BhPile *pile);
 void bh_pile_last_info(const BhPile *pile, uint64_t info[8], uint64_t *lines);
 void bh_pile_close(BhPile *pile);
+/* what bh_vcf.c shares: the base name of an output without its last extension; a collector alone (no table, no file: bh_pile_collect fills
+ * it, the lines keep the header numbers they come with; bh_pile_lines returns their number and the arrays, bh_pile_drop_lines empties it);
+ * the checks of a solver's lines in plain C (`who` opens the texts; *n_obs: an upper bound of the records one walk writes) */
+char *bh_pile_sample_name(const char *path);
+int  bh_pile_open_lines(uint32_t n_headers, int unique_only, BhPile **pile);
+uint64_t bh_pile_lines(const BhPile *pile, const BhipPileLine **lines, const uint32_t **ops, uint64_t *n_ops, uint64_t *n_printed);
+void bh_pile_drop_lines(BhPile *pile);
+int  bh_pile_check_lines(const char *who, const BhPileRefs *refs, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
+                         const uint32_t *ops, uint64_t n_ops, uint64_t *n_obs);
 int  bh_pile_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
                   const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipPileSite *sites, uint64_t cap, uint64_t *n_sites, uint64_t info[8]);
 
@@ -503,6 +512,53 @@ void bh_consensus_close(BhCons *cons);
 int  bh_consensus_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
                        const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, BhipConsSeg *segs, uint64_t seg_cap, uint64_t *n_segs,
                        char *letters, uint64_t letter_cap, uint64_t *n_letters, uint64_t info[8]);
+
+/* ---- VCF output beside the .b6: SNVs and indel alleles per sample from the alignment paths (bh_vcf.c; burst_hip --vcf) ----
+ * The alleles are bhip_alleles_run's (include/burst_hip.h "Indel alleles"), the SNVs a subset of bhip_pile_run's sites.  Per sample the
+ * lines the tracer handed over (bh_pile.c's collector: the same lines, the same unique-read rule) go through ONE bhip_pile_run and ONE
+ * bhip_alleles_run on the reporting rank's handle, and the two ordered lists are merged into the records of OUT.vcf, written under a
+ * temporary name and renamed when the sample has succeeded; a sample that failed and a run that ended on an error leave none.  The file
+ * holds no date and no command line.  Header lines: fileformat, source, a contig line per header in header-number order (SN and LN as
+ * --sam's @SQ: bh_sam_names; LN from the table of --vcf-lengths or the database's own extents), INFO DP, FORMAT DP and AD, the column
+ * line with the sample's name (bh_pile_sample_name).  Records in header-number order, then by POS; at one POS the SNV record first, then
+ * the alleles in their order.  Letters: A C G T for the codes 1 .. 4, N for every other code.  ID, QUAL, FILTER `.`, INFO DP=Depth, FORMAT
+ * DP:AD, no GT.
+ *   SNV   a site whose Ref is A/C/G/T with Depth >= min_depth and a base b != Ref of A, C, G, T with n[b] >= min_alt: ALT those bases in the
+ *         order A, C, G, T; sample field Depth:n[Ref],n[alt1],...
+ *   Del   POS the anchor, REF the anchor's letter and the n deleted letters, ALT the anchor's letter; Depth:Depth-count,count
+ *   Ins   POS the anchor, REF the anchor's letter, ALT the anchor's letter and the inserted letters; Depth:Depth-count,count
+ *         (for both, AD's first number is the observing reads that do not carry this allele)
+ *   bh_vcf_open          the headers are the database's unique-header numbers; two headers of one SN are BH_E_USAGE that names both
+ *   bh_vcf_open_heads    any headers, with their lengths
+ *   bh_vcf_set_solver    other solvers (tests): bhip_pile_run's and bhip_alleles_run's arguments behind a ctx each, return codes in this
+ *                        file's terms (BH_E_CAPACITY = the numbers wanted); NULL: the device
+ *   bh_vcf_sample        the end of a sample: the two calls (the room grows once), OUT.vcf; bh_vcf_sample_failed: its lines are dropped
+ *   bh_vcf_print_info    the `Vcf:` line of the last sample; bh_vcf_last_info: [0] lines [1] allele events [2] distinct alleles [3] returned
+ *                        alleles [4] SNV [5] Del [6] Ins records [7] END [8] ADJACENT [9] LONG skipped runs [10] device microseconds of both
+ *                        calls [11] peak device bytes
+ *   bh_alleles_host      the definition in plain sequential C, a solver: ctx = a BhPileRefs; one record per allele run, sorted and counted */
+typedef struct BhVcf BhVcf;
+typedef int (*bh_alleles_solver_fn)(void *ctx, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
+                                    const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipAllele *alleles, uint64_t cap, uint64_t *n_alleles,
+                                    uint8_t *codes, uint64_t code_cap, uint64_t *n_codes, uint64_t info[8]);
+int  bh_sam_names(const char *flag, uint32_t n_headers, const char *const *heads, char ***sn);      /* (bh_sam.c) SN per header; a clash is BH_E_USAGE that opens with `flag` */
+void bh_sam_names_free(char **sn, uint32_t n_headers);
+int  bh_vcf_check_opts(uint32_t min_depth, uint32_t min_alt);      /* BH_E_USAGE with the command line's text for a value outside its range */
+int  bh_vcf_open(const BhDb *db, const char *lengths_file, uint32_t min_depth, uint32_t min_alt, int unique_only, BhVcf **vcf);
+int  bh_vcf_open_heads(uint32_t n_headers, const char *const *heads, const uint32_t *lengths, uint32_t min_depth, uint32_t min_alt, int unique_only, BhVcf **vcf);
+void bh_vcf_set_solver(BhVcf *vcf, bh_pile_solver_fn pile_fn, void *pile_ctx, bh_alleles_solver_fn alleles_fn, void *alleles_ctx);
+int  bh_vcf_collect(BhVcf *vcf, const uint64_t *idx, const BhipPathReq *req, const uint32_t *first, const uint64_t *off, const uint32_t *ops, uint64_t n_records,
+                    const BhPathBuf *bufs, uint64_t n_chunks);
+int  bh_paths_set_vcf(BhPaths *paths, BhVcf *vcf, int columns);      /* BH_E_USAGE: the tracer's list of collectors is full */
+int  bh_vcf_sample(BhVcf *vcf, void *hip_handle, const char *out_path, const uint8_t *q_codes, const uint64_t *q_off, uint64_t n_queries);
+void bh_vcf_sample_failed(BhVcf *vcf);
+void bh_vcf_abort(BhVcf *vcf);
+void bh_vcf_print_info(BhVcf *vcf);
+void bh_vcf_last_info(const BhVcf *vcf, uint64_t info[12]);
+void bh_vcf_close(BhVcf *vcf);
+int  bh_alleles_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries, const BhipPileLine *lines, uint64_t n_lines,
+                     const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipAllele *alleles, uint64_t cap, uint64_t *n_alleles,
+                     uint8_t *codes, uint64_t code_cap, uint64_t *n_codes, uint64_t info[8]);
 
 /* ---- greedy centroid clusters of the reads of a query file aligned against itself (bh_cluster.c; burst_hip --cluster) ----
  * The definition is bhip_cluster_run's (include/burst_hip.h): nodes = the reads in file order, named by column 1; weight 1, or with
@@ -704,6 +760,10 @@ int  bh_session_set_sam(BhSession *s, BhSam *sam);
  * opens the path tracer (without the --cigar columns unless the session has them) and goes with coverage, abundance, variants and the SAM
  * writer.  Not with database shards, clusters, the chimera check or bh_session_run_mates */
 int  bh_session_set_consensus(BhSession *s, BhCons *cons);
+/* likewise NULL, or the VCF writer every reported sample is given (rank 0's process; the caller opens and closes it): OUT.vcf beside the
+ * output OUT.  Goes with coverage, abundance, variants, the consensus, cigar and the SAM writer.  Not with database shards, clusters, the
+ * chimera check or bh_session_run_mates */
+int  bh_session_set_vcf(BhSession *s, BhVcf *vcf);
 int  bh_session_ended(const BhSession *s);      /* 0, or the code of the error that ended the session */
 void bh_session_close(BhSession *s);
 

@@ -13,6 +13,7 @@
  *             [--chimera-min-seg G] [--chimera-min-gain D]      de-novo two-parent chimera check of the reads from their self-hits and the hits' paths (bh_chimera.c)
  *   ... -q / -o or --samples ... --variants PREFIX [--variants-min-depth N] [--variants-min-alt N] [--variants-reads all|unique]   variant sites per sample (bh_pile.c)
  *   ... -q / -o or --samples ... --consensus PREFIX [--consensus-min-depth N] [--consensus-min-breadth PERMILLE] [--consensus-reads all|unique] [--consensus-lengths FILE]   consensus per reference and sample (bh_consensus.c)
+ *   ... -q / -o or --samples ... --vcf [--vcf-min-depth N] [--vcf-min-alt N] [--vcf-reads all|unique] [--vcf-lengths FILE]   OUT.vcf beside every .b6 output OUT: SNVs and indel alleles (bh_vcf.c)
  *   ... -q / -o or --samples ... --sam [--sam-unmapped] [--sam-lengths FILE]      OUT.sam beside every .b6 output OUT, with NM and MD tags (bh_sam.c)
  *
  * Flags not on the hot path (-f fingerprints, -p prepass, -x alphabet, -hr) are refused with the
@@ -131,6 +132,7 @@ typedef struct {
 	const char *var_prefix; uint32_t var_min_depth, var_min_alt; int var_unique;
 	int sam, sam_unmapped; const char *sam_lengths;
 	const char *cons_prefix; uint32_t cons_min_depth, cons_min_breadth; int cons_unique; const char *cons_lengths;
+	int vcf; uint32_t vcf_min_depth, vcf_min_alt; int vcf_unique; const char *vcf_lengths;
 } SamplesArgs;
 typedef struct { char *q, *o, *m; int line; } Sample;      /* m: the mates file of a three-field line, or NULL */
 
@@ -180,6 +182,18 @@ static int open_consensus(const BhDb *db, const char *prefix, const char *length
 	atexit(cons_atexit);
 	return 0;
 }
+/* the VCF writer of a run: closed on every way out */
+static BhVcf *g_vcf;
+static void vcf_atexit(void) { bh_vcf_close(g_vcf); g_vcf = NULL; }
+/* opened before a device is touched: two headers of one name, a lengths table without a header */
+static int open_vcf(const BhDb *db, const char *lengths, uint32_t min_depth, uint32_t min_alt, int unique) {
+	if (!db->refMap || !db->numRefHeads) { puts("ERROR: --vcf needs the reference headers of the database"); return 1; }
+	const int rc = bh_vcf_open(db, lengths, min_depth, min_alt, unique, &g_vcf);
+	if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; }
+	if (rc) { fprintf(stderr, "%s\n", bh_last_error()); return code_to_exit(rc); }
+	atexit(vcf_atexit);
+	return 0;
+}
 static int samples_main(SamplesArgs *a) {
 	Sample *S = NULL; int nS = 0, rc;
 	if (a->list_FN) { const int e = read_sample_list(a, &S, &nS); if (e) return e; }
@@ -197,6 +211,7 @@ static int samples_main(SamplesArgs *a) {
 	if (any_mates && a->em_prefix) { puts("ERROR: --abundance of paired output is out of scope: it does not go with mates"); return 1; }
 	if (any_mates && a->var_prefix) { puts("ERROR: --variants of paired output are out of scope: they do not go with mates"); return 1; }
 	if (any_mates && a->cons_prefix) { puts("ERROR: --consensus of paired output is out of scope: it does not go with mates"); return 1; }
+	if (any_mates && a->vcf) { puts("ERROR: --vcf of paired output is out of scope: it does not go with mates"); return 1; }
 	if (any_mates && a->sam) { puts("ERROR: --sam of paired output (paired flags, RNEXT, TLEN) is out of scope: it does not go with mates"); return 1; }
 	const int usedb = bh_is_edx(a->ref_FN);
 	if (usedb < 0) DIE(usedb);
@@ -268,6 +283,11 @@ static int samples_main(SamplesArgs *a) {
 		if (e) { bh_session_close(ses); return e; }
 		if ((rc = bh_session_set_consensus(ses, g_cons))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); bh_session_close(ses); return 1; } DIES(rc); }
 	}
+	if (a->vcf) {
+		const int e = open_vcf(&db, a->vcf_lengths, a->vcf_min_depth, a->vcf_min_alt, a->vcf_unique);
+		if (e) { bh_session_close(ses); return e; }
+		if ((rc = bh_session_set_vcf(ses, g_vcf))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); bh_session_close(ses); return 1; } DIES(rc); }
+	}
 	if (shard_db && (uint32_t)n_shards > db.numRclumps) { bh_session_close(ses); puts("ERROR: more database shards than clumps"); return 1; }
 	{ const int e = open_devices(&db, n_gpus, dev_list, shard_db, n_shards, a->accel_dev, K, a->z, hhs, ranks, slices); if (e) { bh_session_close(ses); return e; } }
 	for (int r = 0; r < n_gpus; ++r) ranks[r].hh = hhs[r];
@@ -313,6 +333,7 @@ static int samples_main(SamplesArgs *a) {
 		else printf("Consensus written: %sconsensus.fa, %sconsensus.txt\n", a->cons_prefix, a->cons_prefix);
 	} else if (g_cons) puts("No consensus is written: the run ended on an error");
 	bh_consensus_close(g_cons); g_cons = NULL;
+	bh_vcf_close(g_vcf); g_vcf = NULL;     /* (every sample's file was renamed or removed when the sample ended) */
 	bh_sam_close(sam); sam = NULL;         /* (every sample's file was renamed or removed when the sample ended) */
 	printf("\nSamples: %d done, %d failed. Alignment time: %f seconds\n", n_done, n_failed, wall() - start);
 	fflush(NULL);
@@ -379,6 +400,14 @@ static void usage(void) {
 	puts("                  letter where it is an ambiguity code), N elsewhere.  Insertions are counted (InsMajor), not written.  A record is written when");
 	puts("                  a position was called and 1000 * Called >= --consensus-min-breadth (0) * length; the table has a row per covered (sample,");
 	puts("                  header).  --consensus-reads unique counts only reads printed on one line.  Refuses what --variants refuses");
+	puts("--vcf [--vcf-min-depth <int>] [--vcf-min-alt <int>] [--vcf-reads all|unique] [--vcf-lengths <file>]: with -q / -o or --samples, leave OUT.vcf");
+	puts("                  beside every output OUT (VCFv4.2, one sample, no genotypes): a contig line per reference (ID and length as --sam's @SQ), and from");
+	puts("                  the alignment paths of the printed lines three kinds of records at positions with Depth >= --vcf-min-depth (4): an SNV where the");
+	puts("                  reference base is A/C/G/T and another base has >= --vcf-min-alt (2) reads; a deletion, REF the base before it and the deleted");
+	puts("                  reference bases; an insertion of at most 15 bases, ALT the base before it and the inserted bases -- each indel allele with");
+	puts("                  >= --vcf-min-alt reads.  INFO DP=Depth, sample field DP:AD (for an indel AD's first number is the observing reads without this");
+	puts("                  allele).  An indel at an end of a path or directly behind the other kind is no allele; nothing is left-aligned.  --vcf-reads");
+	puts("                  unique counts only reads printed on one line.  Refuses what --variants refuses, and --cluster and --chimeras");
 	puts("--cluster <prefix> [--cluster-sizes]: with -q reads -r the same reads (FASTA or .edx) -m FORAGE, greedy centroid clusters of the reads from the");
 	puts("                  lines they print against each other: the reads in the order of their weight (1, or with --cluster-sizes the N of a trailing");
 	puts("                  ;size=N of the name), ties in file order; a read with a line to an earlier centroid joins the one with the fewest edits, any");
@@ -418,6 +447,7 @@ int main(int argc, char **argv) {
 	const char *mates_FN = 0; BhMatesOpts mopts = {BHIP_MATES_FR, 0, 1000, BHIP_MATES_ALL}; int mates_opts_given = 0;
 	const char *clu_prefix = 0; int clu_sizes = 0;
 	int sam = 0, sam_unmapped = 0; const char *sam_lengths = 0;
+	int vcf = 0, vcf_unique = 0, vcf_opts_given = 0; uint32_t vcf_min_depth = 4, vcf_min_alt = 2; const char *vcf_lengths = 0;
 	const char *cons_prefix = 0, *cons_lengths = 0; uint32_t cons_min_depth = 4, cons_min_breadth = 0; int cons_unique = 0, cons_opts_given = 0;
 	const char *chi_prefix = 0; int chi_sizes = 0, chi_opts_given = 0; uint32_t chi_skew = 2, chi_min_seg = 16, chi_min_gain = 3;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
@@ -481,6 +511,20 @@ int main(int argc, char **argv) {
 			em_opts_given = 1;
 		}
 		else if (!strcmp(a, "--cigar")) cigar = 1;
+		else if (!strcmp(a, "--vcf")) vcf = 1;
+		else if (!strcmp(a, "--vcf-min-depth") || !strcmp(a, "--vcf-min-alt")) {
+			const int is_alt = !strcmp(a, "--vcf-min-alt");
+			NEEDARG(a);
+			char *end = NULL; const unsigned long long v = strtoull(argv[i], &end, 10);
+			if (!*argv[i] || *end || argv[i][0] == '-' || !v || v > 0x7FFFFFFFull) { puts(is_alt ? "ERROR: --vcf-min-alt takes 1 .. 2147483647" : "ERROR: --vcf-min-depth takes 1 .. 2147483647"); return 1; }
+			if (is_alt) vcf_min_alt = (uint32_t)v; else vcf_min_depth = (uint32_t)v;
+			vcf_opts_given = 1;
+		}
+		else if (!strcmp(a, "--vcf-reads")) {
+			NEEDARG("--vcf-reads"); vcf_opts_given = 1;
+			if (!strcmp(argv[i], "all")) vcf_unique = 0; else if (!strcmp(argv[i], "unique")) vcf_unique = 1; else { puts("ERROR: --vcf-reads all|unique"); return 1; }
+		}
+		else if (!strcmp(a, "--vcf-lengths")) { NEEDARG("--vcf-lengths"); vcf_lengths = argv[i]; vcf_opts_given = 1; }
 		else if (!strcmp(a, "--sam")) sam = 1;
 		else if (!strcmp(a, "--sam-unmapped")) sam_unmapped = 1;
 		else if (!strcmp(a, "--sam-lengths")) { NEEDARG("--sam-lengths"); sam_lengths = argv[i]; }
@@ -635,6 +679,14 @@ int main(int argc, char **argv) {
 	if (cons_prefix && mates_FN) { puts("ERROR: --consensus of paired output is out of scope: it does not go with --mates"); return 1; }
 	if (cons_prefix && (clu_prefix || chi_prefix)) { puts("ERROR: --consensus does not go with --cluster or --chimeras: per-reference outputs of a self-alignment are out of scope"); return 1; }
 	if (cons_prefix && !samples_FN && !(ref_FN && query_FN && output_FN)) { puts("ERROR: --consensus goes with an alignment run: -r, -q and -o, or --samples"); return 1; }
+	/* (--vcf counts from the same paths, traced on the same handle: it refuses what --variants refuses, and the self-alignment outputs) */
+	if (vcf_opts_given && !vcf) { puts("ERROR: --vcf-min-depth, --vcf-min-alt, --vcf-reads and --vcf-lengths go with --vcf"); return 1; }
+	if (vcf && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --vcf calls from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (vcf && (shard_db || n_shards)) { puts("ERROR: --vcf traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
+	if (vcf && !gather_host) { puts("ERROR: --vcf takes the host gather only (drop --gather rccl)"); return 1; }
+	if (vcf && mates_FN) { puts("ERROR: --vcf of paired output is out of scope: it does not go with --mates"); return 1; }
+	if (vcf && (clu_prefix || chi_prefix)) { puts("ERROR: --vcf does not go with --cluster or --chimeras: per-reference outputs of a self-alignment are out of scope"); return 1; }
+	if (vcf && !samples_FN && !(ref_FN && query_FN && output_FN)) { puts("ERROR: --vcf goes with an alignment run: -r, -q and -o, or --samples"); return 1; }
 	/* (--cluster picks clusters from the lines one query file prints against itself: refused before a device is touched whatever would
 	 * discard those lines, print other files' lines, or leave rank 0 without the whole report) */
 	if (clu_sizes && !clu_prefix) { puts("ERROR: --cluster-sizes goes with --cluster <prefix>"); return 1; }
@@ -679,7 +731,8 @@ int main(int argc, char **argv) {
 		                  n_gpus, n_gpus_given, n_dev_list, dev_list, shard_db, n_shards, batch, &txo, cov_prefix, cov_lengths, cov_pad, cigar,
 		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given, em_prefix, em_iters, em_tol,
 		                  var_prefix, var_min_depth, var_min_alt, var_unique, sam, sam_unmapped, sam_lengths,
-		                  cons_prefix, cons_min_depth, cons_min_breadth, cons_unique, cons_lengths};
+		                  cons_prefix, cons_min_depth, cons_min_breadth, cons_unique, cons_lengths,
+		                  vcf, vcf_min_depth, vcf_min_alt, vcf_unique, vcf_lengths};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
@@ -814,6 +867,7 @@ int main(int argc, char **argv) {
 	BhEm *em = NULL;
 	if (em_prefix && (rc = bh_em_open(&db, em_prefix, em_iters, em_tol, &em))) DIEJ(rc);
 	if (cons_prefix) { const int e = open_consensus(&db, cons_prefix, cons_lengths, cons_min_depth, cons_min_breadth, cons_unique); if (e) { JOIN_INGEST(); return e; } }
+	if (vcf) { const int e = open_vcf(&db, vcf_lengths, vcf_min_depth, vcf_min_alt, vcf_unique); if (e) { JOIN_INGEST(); return e; } }
 	if (sam) {      /* (before a device is touched: two headers of one name, a lengths table without a header) */
 		if ((rc = bh_sam_open(&db, sam_lengths, sam_unmapped, &g_sam))) { JOIN_INGEST(); if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
 		atexit(sam_atexit);      /* (whichever way the run ends before bh_sam_end: no file, no temporary file) */
@@ -944,7 +998,7 @@ int main(int argc, char **argv) {
 	setvbuf(output, NULL, _IOFBF, 1 << 22);
 	BhPlaceSink sink; memset(&sink, 0, sizeof sink);
 	BhPaths *paths = NULL;
-	if ((cigar || var_prefix || cons_prefix || chi_prefix || sam) && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
+	if ((cigar || var_prefix || cons_prefix || vcf || chi_prefix || sam) && (rc = bh_paths_open(hhs[0], &paths))) DIE(rc);      /* (rank 0's handle, as the coverage) */
 	BhPile *pile = NULL;      /* a study of one sample; opened here: its temporary file exists from now until it is renamed or the object is closed */
 	#define DIEP(rc) do { bh_pile_close(pile); DIE(rc); } while (0)
 	if (var_prefix) {
@@ -965,6 +1019,7 @@ int main(int argc, char **argv) {
 		if ((rc = bh_paths_set_sam(paths, g_sam, cigar))) DIEP(rc);
 	}
 	if (g_cons && (rc = bh_paths_set_consensus(paths, g_cons, cigar))) DIEP(rc);
+	if (g_vcf && (rc = bh_paths_set_vcf(paths, g_vcf, cigar))) DIEP(rc);
 	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em || clu ? &sink : NULL, paths))) DIEP(rc);
 	if (fclose(output)) { fprintf(stderr, "ERROR: write failed: %s\n", output_FN); return 2; }      /* (the last buffer of the report: a full disk must not end in exit code 0) */
 	printf("Wrote %lu alignments\n", (unsigned long)lines);
@@ -983,6 +1038,13 @@ int main(int argc, char **argv) {
 		printf("Consensus written: %sconsensus.fa, %sconsensus.txt\n", cons_prefix, cons_prefix);
 		PHASE("consensus");
 		bh_consensus_close(g_cons); g_cons = NULL;
+	}
+	if (g_vcf) {    /* OUT.vcf: written under a temporary name, renamed when it is whole (a failure leaves none) */
+		if ((rc = bh_vcf_sample(g_vcf, hhs[0], output_FN, Q.codes, Q.qoff, Q.numEntries))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
+		bh_vcf_print_info(g_vcf);
+		printf("VCF records written: %s.vcf\n", output_FN);
+		PHASE("VCF");
+		bh_vcf_close(g_vcf); g_vcf = NULL;
 	}
 	if (cov) {      /* a study of one sample: the Dataset column and the sample's (rank 0's handle; the lines exist only here) */
 		if ((shard_db && (rc = bh_cov_lengths_host(cov))) || (rc = bh_cov_sample(cov, hhs[0], output_FN, sink.lines, sink.n)) || (rc = bh_cov_write(cov))) DIE(rc);

@@ -347,6 +347,20 @@ def lib():
         L.bh_consensus_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         L.bh_session_set_consensus.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_vcf_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        L.bh_vcf_open_heads.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        L.bh_vcf_set_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_vcf_set_solver.restype = None
+        L.bh_vcf_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BhPathBuf), C.c_uint64]
+        L.bh_vcf_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        for name in ("bh_vcf_sample_failed", "bh_vcf_abort", "bh_vcf_print_info", "bh_vcf_close"):
+            getattr(L, name).argtypes = [C.c_void_p]
+            getattr(L, name).restype = None
+        L.bh_vcf_last_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_vcf_last_info.restype = None
+        L.bh_alleles_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+        L.bh_session_set_vcf.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_sam_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
         L.bh_sam_open_heads.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.bh_sam_set_md.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -599,6 +613,31 @@ def consensus_host(refs, q_codes, q_off, lines, ops, min_depth=4, seg_cap=None, 
         raise HostError("bh_consensus_host: %d segments and %d letters, room for %d and %d" % (ns.value, nl.value, seg_cap, letter_cap))
     _chk(rc)
     return segs[:ns.value], letters[:nl.value].tobytes(), info
+
+
+VCF_INFO = ("lines", "events", "distinct", "alleles", "snv", "del", "ins", "skipped_end", "skipped_adjacent", "skipped_long", "device_us", "peak_bytes")
+
+
+def alleles_host(refs, q_codes, q_off, lines, ops, min_depth=4, min_alt=2, cap=None, code_cap=None):
+    """bh_alleles_host, the indel-allele definition in plain sequential C (no device; one record per allele run): (alleles capi.ALLELE_DTYPE,
+    codes uint8, info uint64 [8]: events, distinct, returned alleles, skipped end / adjacent / long runs).  refs: pile_refs(...); the rest as
+    pile_host"""
+    q_codes, q_off = np.ascontiguousarray(q_codes, dtype=np.uint8), np.ascontiguousarray(q_off, dtype=np.uint64)
+    lines, ops = capi.pile_lines(lines), np.ascontiguousarray(ops, dtype=np.uint32)
+    cap = max(len(lines), 16) if cap is None else int(cap)
+    code_cap = 1 << 12 if code_cap is None else int(code_cap)
+    na, nc, info = C.c_uint64(0), C.c_uint64(0), np.zeros(8, np.uint64)
+    for _ in range(2):
+        out, codes = np.zeros(max(cap, 1), capi.ALLELE_DTYPE), np.zeros(max(code_cap, 1), np.uint8)
+        rc = lib().bh_alleles_host(C.byref(refs), q_codes.ctypes.data, q_off.ctypes.data, len(q_off) - 1, lines.ctypes.data, len(lines), ops.ctypes.data, len(ops),
+                                   int(min_depth), int(min_alt), out.ctypes.data, cap, C.byref(na), codes.ctypes.data, code_cap, C.byref(nc), info.ctypes.data)
+        if rc != E_CAPACITY or (na.value <= cap and nc.value <= code_cap):
+            break
+        cap, code_cap = max(cap, na.value), max(code_cap, nc.value)
+    if rc == E_CAPACITY:
+        raise HostError("bh_alleles_host: %d alleles and %d codes, room for %d and %d" % (na.value, nc.value, cap, code_cap))
+    _chk(rc)
+    return out[:na.value], codes[:nc.value], info
 
 
 def pile_host(refs, q_codes, q_off, lines, ops, min_depth=4, min_alt=2, cap=None):
@@ -966,7 +1005,8 @@ class Session:
                  cluster=None, cluster_sizes=False, cluster_host=False,
                  chimeras=None, chimera_sizes=False, chimera_skew=2, chimera_min_seg=16, chimera_min_gain=3, chimera_host=False,
                  sam=False, sam_unmapped=False, sam_lengths=None, sam_md=None,
-                 consensus=None, consensus_min_depth=4, consensus_min_breadth=0, consensus_reads="all", consensus_lengths=None, consensus_host=False):
+                 consensus=None, consensus_min_depth=4, consensus_min_breadth=0, consensus_reads="all", consensus_lengths=None, consensus_host=False,
+                 vcf=False, vcf_min_depth=4, vcf_min_alt=2, vcf_reads="all", vcf_lengths=None, vcf_host=False):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
         reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
         process only).
@@ -1002,7 +1042,13 @@ class Session:
         record written at consensus_min_breadth permille of the header's length; consensus_reads "unique": only reads printed on one line;
         consensus_lengths: a `name<TAB>length` table, default the database's own extents), from ONE bhip_consensus_run per sample on rank
         0's device handle -- or bh_consensus_host with consensus_host=True; consensus() returns the table's rows so far, close() writes both
-        files unless the session ended on an error.  Same limits as variants; goes with them, coverage, abundance, cigar and sam."""
+        files unless the session ended on an error.  Same limits as variants; goes with them, coverage, abundance, cigar and sam.
+        vcf: every reported sample's output OUT gets OUT.vcf beside it (bh_vcf.c: VCFv4.2, one sample, no genotypes; an SNV record where a
+        base other than an A/C/G/T reference base has vcf_min_alt reads, a record per deletion and per insertion of at most 15 symbols with
+        vcf_min_alt reads, at positions of vcf_min_depth reads; vcf_reads "unique": only reads printed on one line; vcf_lengths: a
+        `name<TAB>length` table for the contig lines, default the database's own extents), from ONE bhip_pile_run and ONE bhip_alleles_run
+        per sample on rank 0's device handle -- or bh_pile_host and bh_alleles_host with vcf_host=True.  Same limits as variants; goes with
+        them, the consensus, coverage, abundance, cigar and sam.  vcf_info() has the last sample's figures."""
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
         self._mates_join = mates_join
         self.cov, self.em, self.pile, self.cluster, self.chimera = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -1043,6 +1089,7 @@ class Session:
         self.ended = False
         self.cov_aborted = False
         self.cons = C.c_void_p()
+        self.vcf = C.c_void_p()
         if coverage is not None and (rank == 0 or len(devs) > 1):      # (in a job of processes the lines exist only where rank 0 reports)
             _chk(lib().bh_cov_open(C.byref(db.c), coverage.encode(), coverage_lengths.encode() if coverage_lengths else None, int(coverage_pad), C.byref(self.cov)))
             if coverage_tap is not None:
@@ -1108,6 +1155,22 @@ class Session:
             if consensus_host:
                 self._cons_refs = BhPileRefs(C.cast(db.c.packed, C.c_void_p), C.cast(db.c.clumpLen, C.c_void_p), db.c.numRclumps, db.c.totR)
                 lib().bh_consensus_set_solver(self.cons, C.cast(lib().bh_consensus_host, C.c_void_p), C.cast(C.pointer(self._cons_refs), C.c_void_p))
+        if vcf_lengths and not vcf:
+            raise ValueError("vcf_lengths goes with vcf=True")
+        if vcf:
+            if vcf_reads not in ("all", "unique") or not 1 <= int(vcf_min_depth) < 1 << 31 or not 1 <= int(vcf_min_alt) < 1 << 31:
+                raise ValueError("vcf: reads all|unique, 1 <= min_depth < 2^31, 1 <= min_alt < 2^31")
+            if shard_db and int(shard_db) > 1:
+                raise ValueError("vcf: the paths are traced on one handle, which must hold the whole database (no shard_db)")
+            if align is not None or world != n_local:
+                raise ValueError("vcf: needs the device handles of one process (no align back end, no job of processes)")
+            if cluster is not None or chimeras is not None:
+                raise ValueError("vcf: per-reference outputs of a self-alignment are out of scope (no cluster, no chimeras)")
+            _chk(lib().bh_vcf_open(C.byref(db.c), vcf_lengths.encode() if vcf_lengths else None, int(vcf_min_depth), int(vcf_min_alt), int(vcf_reads == "unique"), C.byref(self.vcf)))
+            if vcf_host:
+                self._vcf_refs = BhPileRefs(C.cast(db.c.packed, C.c_void_p), C.cast(db.c.clumpLen, C.c_void_p), db.c.numRclumps, db.c.totR)
+                ctx = C.cast(C.pointer(self._vcf_refs), C.c_void_p)
+                lib().bh_vcf_set_solver(self.vcf, C.cast(lib().bh_pile_host, C.c_void_p), ctx, C.cast(lib().bh_alleles_host, C.c_void_p), ctx)
         if (sam_unmapped or sam_lengths) and not sam:
             raise ValueError("sam_unmapped and sam_lengths go with sam=True")
         if sam:
@@ -1125,6 +1188,8 @@ class Session:
                 _chk(lib().bh_session_set_sam(self.h, self.sam))
             if self.cons:
                 _chk(lib().bh_session_set_consensus(self.h, self.cons))
+            if self.vcf:
+                _chk(lib().bh_session_set_vcf(self.h, self.vcf))
             if self.cluster:
                 _chk(lib().bh_session_set_cluster(self.h, self.cluster))
             if self.chimera:
@@ -1133,7 +1198,7 @@ class Session:
             if self.h:
                 lib().bh_session_close(self.h)
                 self.h = C.c_void_p()
-            for name, close in (("sam", lib().bh_sam_close), ("cons", lib().bh_consensus_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
+            for name, close in (("sam", lib().bh_sam_close), ("vcf", lib().bh_vcf_close), ("cons", lib().bh_consensus_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
                 if getattr(self, name):
                     close(getattr(self, name))
                     setattr(self, name, C.c_void_p())
@@ -1327,6 +1392,13 @@ class Session:
         lines (printed), foreign"""
         return _chimera_info(self.chimera)
 
+    def vcf_info(self):
+        """the last written sample's figures: lines, events, distinct, alleles, snv, del, ins (records), skipped_end, skipped_adjacent,
+        skipped_long, device_us, peak_bytes"""
+        info = np.zeros(12, np.uint64)
+        lib().bh_vcf_last_info(self.vcf, info.ctypes.data)
+        return dict(zip(VCF_INFO, (int(x) for x in info)))
+
     def sam_info(self):
         """the last written sample's figures: records, unmapped, md_bytes, device_us"""
         info = np.zeros(4, np.uint64)
@@ -1368,6 +1440,9 @@ class Session:
                     err = lib().bh_last_error().decode("utf-8", "replace")
                 lib().bh_consensus_close(self.cons)
                 self.cons = C.c_void_p()
+            if self.vcf:          # (every sample's file was renamed or removed when the sample ended)
+                lib().bh_vcf_close(self.vcf)
+                self.vcf = C.c_void_p()
             if self.cluster:      # (its tables were written when the sample was reported)
                 lib().bh_cluster_close(self.cluster)
                 self.cluster = C.c_void_p()

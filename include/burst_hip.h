@@ -476,6 +476,45 @@ BHIP_API int bhip_consensus_run(void *handle, const uint8_t *q_codes, const uint
                                 uint64_t info[8]);
 BHIP_API int bhip_consensus_info(void *handle, uint64_t info[8]);
 
+/* Indel alleles: which bases one sample's reads insert behind a reference position, and which reference columns they delete there
+ * (burst_hip --vcf; no reference counterpart: the definition is this project's own).  A function of the sample's printed lines, all
+ * integer arithmetic, bit-exact on any machine.  Lines, the walk (reference position p, query index j), observations, Depth, Ref and the
+ * meaning of the weights are exactly those of "Variant sites" above (a reverse line carries the path of its reverse-complement entry, so
+ * alleles are forward-strand; a duplicate read is a line of its own).
+ *   ALLELE RUN  an I or D run (ops are merged runs) whose directly preceding op is '=' or X and which is not the last op of its path.  Its
+ *               ANCHOR is (header, p - 1), the column the preceding op consumed: every line that carries an allele observes its anchor, so
+ *               count <= Depth(anchor) always.  A run that is the first or the last op (END) or stands directly behind the other indel kind
+ *               (ADJACENT, ...3D2I...) is no allele; it still counts in the site's Ins / Del of the variant sites, and is counted as skipped,
+ *               END before ADJACENT.
+ *   Del(n)      a D allele run of n columns.
+ *   Ins(c1..cn) an I allele run of n query symbols, 1 <= n <= 15: the stored query codes j .. j + n - 1, 0 .. 15 each.  A run of more than 15
+ *               symbols is LONG: it gives no allele and is counted.  The limit is policy: an allele is then ONE 64-bit word (4 bits of
+ *               length, 60 of codes) and stays an exact sort key, nothing is hashed.
+ *   WORD        Del(n): n (top 4 bits 0).  Ins: n << 60 | c1 << 56 | c2 << 52 | ...  Plain integer order of the words is the order below.
+ *   COUNT       of (anchor, allele): the sum of w over the lines that carry it.
+ *   RETURNED    when Depth(anchor) >= min_depth and count >= min_alt, whatever the anchor's reference code; 1 .. 2^31 - 1 each.
+ *   ORDER       ascending (header, pos), then Del before Ins, Del by n, Ins by n, then by c1..cn lexicographically.
+ * A returned allele carries the anchor's reference code (ref) and Depth(anchor); a Del(n) also owns the n reference codes of the columns
+ * p .. p + n - 1, codes[code_off .. code_off + n) (one byte per code; code_off is the running sum of the n of the returned Dels before it, for an
+ * Ins as well, which owns no codes).  Lanes that share header positions agree there, so the codes are read from ONE carrying line (the one of the smallest index).
+ * The cost follows lines + allele events (csrc/bhip_alleles.hip): the events are sorted by (anchor, word) in two
+ * stable radix passes and reduced by key -- a pile-up of any depth on one allele is reduced in parallel --, Depth(anchor) is the stabbing
+ * count of the variant sites.  All sums are 64-bit integers and every choice a minimum: no order of threads, and no order of the lines,
+ * changes a byte.
+ * The inputs and the BHIP_E_ARG checks are those of bhip_pile_run, before any device memory is touched and with the handle staying usable;
+ * also for a threshold of 0 or above 2^31 - 1, and for more than 2^31 - 1 allele events in one call.  BHIP_E_CAPACITY when cap or code_cap
+ * is too small: *n_alleles and *n_codes are the numbers wanted, nothing is written, the handle stays usable.  n_lines == 0: nothing is
+ * launched.
+ * info (may be NULL; bhip_alleles_info returns that of the last call on the handle): [0] allele events, [1] distinct alleles, [2] returned
+ * alleles, [3] skipped END runs, [4] skipped ADJACENT runs, [5] skipped LONG runs, [6] device microseconds (HIP events around everything
+ * launched), [7] peak device bytes of the scratch buffers (those of bhip_pile_run included; bhip_destroy frees them). */
+typedef struct BhipAllele { uint32_t header, pos; uint64_t allele; uint32_t ref, depth, count, pad; uint64_t code_off; } BhipAllele;
+BHIP_API int bhip_alleles_run(void *handle, const uint8_t *q_codes, const uint64_t *q_off, uint32_t n_queries,
+                              const BhipPileLine *lines, uint64_t n_lines, const uint32_t *ops, uint64_t n_ops,
+                              uint32_t min_depth, uint32_t min_alt, BhipAllele *alleles, uint64_t cap, uint64_t *n_alleles,
+                              uint8_t *codes, uint64_t code_cap, uint64_t *n_codes, uint64_t info[8]);
+BHIP_API int bhip_alleles_info(void *handle, uint64_t info[8]);
+
 /* Clustering: greedy centroid clusters of the reads of a query file from the lines it prints against itself (burst_hip --cluster; no
  * reference counterpart: its README lists clustering "as an output mode" as planned and names the recipe -- the queries as their own
  * references in FORAGE, then clusters picked from that hit graph).  All of it is integer arithmetic, bit-exact on any machine.
