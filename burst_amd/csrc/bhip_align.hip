@@ -424,10 +424,11 @@ static int launch_seed(Handle *h, Lane *L, hipStream_t st, StageSlot *S, int cls
 }
 
 // the counting-filter kernel of a choice (bhip_pf_select.h), first pass (big = 0) or second pass over the queries that overflowed it
-// (big = 1: the largest tables); null: a superseded kernel and no test-only library in the process
-static bhip_pf_kernel_t pf_kernel(const BhipPfChoice &c, int big) {
+// (big = 1: the largest tables); gw: lanes per query of the first pass (bhip_pf_group: 8 only for k_prefilter_cq in slot mode 0); null: a
+// superseded kernel and no test-only library in the process
+static bhip_pf_kernel_t pf_kernel(const BhipPfChoice &c, int big, int gw = 16) {
 	if (c.legacy) return bhip_legacy_pf_kernel ? bhip_legacy_pf_kernel(c.kind, big ? 11 : c.htb, big ? 4 : c.rb, c.cw_mode, big) : nullptr;
-	if (c.kind == BHIP_PF_CQ) return c.cw_mode == 0 ? (big ? k_prefilter_cq<0, 1> : k_prefilter_cq<0, 0>) : (big ? k_prefilter_cq<1, 1> : k_prefilter_cq<1, 0>);
+	if (c.kind == BHIP_PF_CQ) return c.cw_mode == 0 ? (big ? k_prefilter_cq<0, 1, 16> : gw == 8 ? k_prefilter_cq<0, 0, 8> : k_prefilter_cq<0, 0, 16>) : (big ? k_prefilter_cq<1, 1, 16> : k_prefilter_cq<1, 0, 16>);
 	return big ? k_prefilter_cw<2, 1> : k_prefilter_cw<2, 0>;      // plans beyond 16 lists per query: one query per wave
 }
 
@@ -444,9 +445,13 @@ static int launch_prefilter_mask(Handle *h, Lane *L, hipStream_t st, int cls, co
 	if (!(L->seeded_ok[cls] && L->seeded_seq[cls] == h->cur->seq && L->seeded_n[cls] == n_list && L->seeded_W16[cls] == W16))
 		if ((rc = launch_seed(h, L, st, h->cur, cls, d_qlist, n_list, maxwords, mean_words))) return rc;
 	// expected number of distinct clumps of a query: sampled words x occurrence-weighted mean list length
-	const BhipPfChoice c = bhip_pf_choose(algo, h->opt_pf_cw, h->opt_pf_table, h->opt_pf_rb, W16, mean_words * h->acx_wmean);
+	const double expect = mean_words * h->acx_wmean;
+	const BhipPfChoice c = bhip_pf_choose(algo, h->opt_pf_cw, h->opt_pf_table, h->opt_pf_rb, W16, expect);
 	const bool filter = c.kind != BHIP_PF_MASK, cw = c.kind == BHIP_PF_CW || c.kind == BHIP_PF_CQ;
-	const bhip_pf_kernel_t fp = filter ? pf_kernel(c, 0) : nullptr, fp2 = filter && c.two_pass ? pf_kernel(c, 1) : nullptr;
+	// lanes per query of the first pass, queries per wave (k_prefilter_cq only: every other kernel's grid is sized as before)
+	const int gw = bhip_pf_group(h->opt_pf_group, c, W16, expect, L->pf_surv_per_query);
+	const uint32_t qw = 64u / (uint32_t)gw;
+	const bhip_pf_kernel_t fp = filter ? pf_kernel(c, 0, gw) : nullptr, fp2 = filter && c.two_pass ? pf_kernel(c, 1) : nullptr;
 	if (filter && (!fp || (c.two_pass && !fp2)))
 		return fail(BHIP_E_ARG, "option prefilter_cw = %d selects a superseded prefilter kernel that is not part of libburst_hip.so (tests: libburst_hip_legacy.so is loaded first)", h->opt_pf_cw);
 	// As many single-wave blocks per CU as are resident at once: the kernel is a persistent loop over a static partition of the list, one
@@ -455,11 +460,11 @@ static int launch_prefilter_mask(Handle *h, Lane *L, hipStream_t st, int cls, co
 	const void *fn = filter ? (const void *)fp : c.htb == 9 ? (const void *)k_prefilter_mask<9> : c.htb == 10 ? (const void *)k_prefilter_mask<10> : (const void *)k_prefilter_mask<11>;
 	const uint32_t fit = std::min<uint32_t>(cw ? 32u : 12u, blocks_per_cu(fn, 64u, 0, &fa));
 	if (getenv("BHIP_DEBUG")) {
-		if (cw) fprintf(stderr, "[bhip] prefilter kernel: %s, slot mode %d, %zu B LDS, %d VGPRs -> %u blocks per CU\n", c.kind == BHIP_PF_CQ ? "four queries per wave, streams by the whole wave" : "one query per wave", c.cw_mode, fa.sharedSizeBytes, fa.numRegs, fit);
+		if (cw) fprintf(stderr, "[bhip] prefilter kernel: %s, slot mode %d, %zu B LDS, %d VGPRs -> %u blocks per CU (expected stream %.0f records, %.1f survivors per query in the lane's last chain)\n", c.kind != BHIP_PF_CQ ? "one query per wave" : gw == 8 ? "eight queries per wave, 8 lanes each, streams by the whole wave" : "four queries per wave, 16 lanes each, streams by the whole wave", c.cw_mode, fa.sharedSizeBytes, fa.numRegs, fit, expect, L->pf_surv_per_query);
 		else fprintf(stderr, "[bhip] prefilter kernel: table 2^%d, %d record blocks in registers, %zu B LDS, %d VGPRs -> %u blocks per CU\n", c.htb, c.rb, fa.sharedSizeBytes, fa.numRegs, fit);
 	}
 	const uint32_t waves = h->opt_pf_waves ? std::min<uint32_t>((uint32_t)h->opt_pf_waves, fit) : fit;
-	const uint32_t grid = std::min<uint32_t>(c.kind == BHIP_PF_CW ? n_list : (n_list + 3) / 4, (uint32_t)h->n_cu * waves);
+	const uint32_t grid = std::min<uint32_t>(c.kind == BHIP_PF_CW ? n_list : (n_list + qw - 1) / qw, (uint32_t)h->n_cu * waves);
 	HIPCHK(hipEventRecord(L->ev_pf[cls][PF_HASH_START], st));
 	const uint32_t *fb_dense = ov.fb1, *n_fb_dense = ov.n_fb1;
 	if (filter) {
@@ -986,6 +991,10 @@ static void adapt_prefilter_algo(Handle *h, const BatchCall &b) {
 		// of a 500-strain family meets the family's clumps in every one of its lists): the exact-table kernel took 61.5 ms per 2 M reads where
 		// k_prefilter_cq takes 8.5 (gpurun_out/r06a, r06b) -- with the minimum-only semantics the switch is off while that kernel is in use
 		const bool cq_min_only = !b.all_hits && h->opt_pf_cw == 2 && L->pf_algo_used == 3;
+		// (survivors per prefiltered query of this chain: bhip_pf_group keeps a strain-rich lane at 16 lanes per query from its second batch on)
+		uint32_t n_pf = 0;
+		for (int cls = 0; cls < kNumClasses; ++cls) n_pf += L->npf[cls];
+		if (L->n_entries && n_pf) L->pf_surv_per_query = (double)L->hc.surv_sum / (double)n_pf;
 		if (L->n_entries && L->pf_algo == 0 && !cq_min_only && L->hc.ent_read > 100000 && (double)L->hc.surv_sum > (b.all_hits ? 0.20 : 0.50) * (double)L->hc.ent_read) L->pf_algo = 1;
 	}
 }

@@ -56,7 +56,7 @@ template <int HTB> __global__ void k_prefilter_mask(const uint2 *, const uint2 *
 	uint2 *, uint32_t *, uint32_t, unsigned long long *, uint32_t *, uint32_t *, unsigned long long *, unsigned long long *, unsigned long long *,
 	uint2 *, uint32_t *, uint32_t);
 // (the counting-filter kernels: every instantiation is a bhip_pf_kernel_t, bhip_internal.h; k_prefilter_cf and k_prefilter_cw<0 / 1> come from the test-only library)
-template <int MODE, int BIG> __global__ void k_prefilter_cq(const uint2 *, const uint2 *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, uint32_t, const uint32_t *, uint32_t,
+template <int MODE, int BIG, int GW> __global__ void k_prefilter_cq(const uint2 *, const uint2 *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, uint32_t, const uint32_t *, uint32_t,
 	uint2 *, uint32_t *, uint32_t, unsigned long long *, uint32_t *, uint32_t *, unsigned long long *, unsigned long long *, unsigned long long *, unsigned long long *,
 	uint2 *, uint32_t *, int, const uint32_t *, const uint32_t *, int);
 template <int MODE, int BIG> __global__ void k_prefilter_cw(const uint2 *, const uint2 *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, uint32_t, const uint32_t *, uint32_t,
@@ -327,6 +327,7 @@ struct Lane {
 	bool pruned[kNumClasses] = {false};   // a second (filtered) sweep ran for this class
 	int pf_algo_used = 0;
 	int pf_algo = 0;              // algorithm of this lane's next prefilter launches (follows opt_pf_algo: -1 = adapt)
+	double pf_surv_per_query = -1.0;      // survivors of the counting filter per prefiltered query in this lane's last chain (-1: no chain yet); bhip_pf_group's guard
 	const uint32_t *qlist[kNumClasses] = {nullptr};      // (lane, class) lists of the current batch: entries of the slot's sorted index array
 	DBuf peq, peqp, cand, candcnt, wins, raw, wide, scratch, fb_list, gcnt, counters, tasks, tasks2, tasks2k, wins2, rs_lists;
 	// seed lookups (k_seed_ranges) per class: list ranges + query headers for the prefilter.  They depend on the staged batch alone,
@@ -438,6 +439,7 @@ struct Handle {
 	int opt_pf_table = 0;         // log2 of the per-query hash table (0 = from the workload: 9, 10 or 11)
 	int opt_pf_cw = 2;            // the counting filter as: 0 k_prefilter_cf (four queries per wave, 16 lanes each), 1 k_prefilter_cw (one query per wave, list-mask slots),
 	                              // 2 k_prefilter_cq (four queries per wave, their record streams walked by the whole wave; plans beyond 16 lists: k_prefilter_cw)
+	int opt_pf_group = 0;         // lanes per query of k_prefilter_cq's first pass: 0 = by rule (bhip_pf_group), 8 (eight queries per wave; slot mode 0 only, wider rows still run 16), 16
 	int opt_pf_bytes = 1;         // byte counters (twice as many) for queries whose record stream is at most 255 records
 	int opt_pf_rb = 0;            // 64-record blocks per query the counting-filter kernel fetches a quad ahead and keeps in registers (0 = from the workload: 2, 3 or 4)
 	int opt_seed_ahead = 1;       // seed lookups of the next staged batch run while the current one is swept

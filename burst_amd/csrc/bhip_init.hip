@@ -250,6 +250,7 @@ extern "C" int bhip_set_option(void *handle, const char *name, long long value) 
 	if (!strcmp(name, "prefilter_algo")) { if (value < -1 || value > 1) return fail(BHIP_E_ARG, "prefilter_algo must be -1, 0 or 1"); h->opt_pf_algo = (int)value; return BHIP_OK; }
 	if (!strcmp(name, "prefilter_table")) { if (value != 0 && (value < 9 || value > 11)) return fail(BHIP_E_ARG, "prefilter_table must be 0, 9, 10 or 11"); h->opt_pf_table = (int)value; return BHIP_OK; }
 	if (!strcmp(name, "prefilter_cw")) { if (value < 0 || value > 2) return fail(BHIP_E_ARG, "prefilter_cw must be 0, 1 or 2"); h->opt_pf_cw = (int)value; return BHIP_OK; }
+	if (!strcmp(name, "prefilter_group")) { if (value != 0 && value != 8 && value != 16) return fail(BHIP_E_ARG, "prefilter_group must be 0, 8 or 16"); h->opt_pf_group = (int)value; return BHIP_OK; }
 	if (!strcmp(name, "prefilter_bytes")) { h->opt_pf_bytes = value != 0; return BHIP_OK; }
 	if (!strcmp(name, "prefilter_rb")) { if (value != 0 && (value < 2 || value > 4)) return fail(BHIP_E_ARG, "prefilter_rb must be 0, 2, 3 or 4"); h->opt_pf_rb = (int)value; return BHIP_OK; }
 	if (!strcmp(name, "cov_event_cap")) { if (value < 0) return fail(BHIP_E_ARG, "cov_event_cap must be >= 0 bytes (0 = a fifth of the free memory)"); h->opt_cov_event_cap = value; return BHIP_OK; }

@@ -106,7 +106,7 @@ struct BhipStageInfo {
 	uint32_t maxE_all, maxlen_all;
 };
 
-// The counting-filter prefilter kernels -- k_prefilter_cq<MODE, BIG>, k_prefilter_cw<MODE, BIG>, k_prefilter_cf<CB, RB> -- share ONE signature:
+// The counting-filter prefilter kernels -- k_prefilter_cq<MODE, BIG, GW>, k_prefilter_cw<MODE, BIG>, k_prefilter_cf<CB, RB> -- share ONE signature:
 // (ranges, hdr, W16, n_list, ent, bad, n_bad, clump_len, tot_refs, tasks, n_tasks, task_cap, ent_read, fb_list, n_fb, unit_sum, col_sum,
 // qlen_sum, surv_sum, tasks2, n_tasks2, prune, sel, n_sel_dev, byte_counters).  The host picks one as a pointer of this type, asks the
 // runtime about its occupancy and launches it (bhip_align.hip: pf_kernel, launch_prefilter_mask).

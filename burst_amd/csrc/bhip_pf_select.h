@@ -9,7 +9,7 @@
 enum { BHIP_PF_CF = 0,       // k_prefilter_cf<htb, rb>: counting filter, four queries per wave, 16 lanes each (superseded: test-only library)
        BHIP_PF_MASK = 1,     // k_prefilter_mask<htb>: exact clump hash table
        BHIP_PF_CW = 2,       // k_prefilter_cw<cw_mode, BIG>: counting filter, one query per wave (cw_mode 0 / 1 superseded: test-only library)
-       BHIP_PF_CQ = 3 };     // k_prefilter_cq<cw_mode, BIG>: counting filter, four queries per wave, streams walked by the whole wave
+       BHIP_PF_CQ = 3 };     // k_prefilter_cq<cw_mode, BIG, GW>: counting filter, four (GW = 16) or eight (GW = 8, bhip_pf_group) queries per wave, streams walked by the whole wave
 struct BhipPfChoice {
 	int kind;
 	int htb;                 // log2 of the per-query table (k_prefilter_cf: approximate counters; k_prefilter_mask: hash slots)
@@ -47,6 +47,29 @@ static inline BhipPfChoice bhip_pf_choose(int algo, int opt_pf_cw, int opt_pf_ta
 	c.legacy = algo == 0 && !cq && !(cw && c.cw_mode == 2);
 	c.two_pass = algo == 0 && (cw || c.htb != 11);
 	return c;
+}
+
+// Lanes per query of k_prefilter_cq's FIRST pass: 16 (four queries per wave) or 8 (eight).  The kernel's per-quad half -- list scan, survivor
+// rounds, emit, clears -- costs the same instructions whatever the number of queries in the wave, so eight queries halve it per query; the
+// price is half of everything a query owns: 512 approximate slots, a 16-slot exact table, 8 survivors per round, two resident rows of 64
+// records.  That pays for short streams with few survivors and nowhere else:
+//  * only BHIP_PF_CQ in slot mode 0 (a query's lists are the lanes of its group: at most 8; a wider row runs 16 lanes whatever the option);
+//  * expect <= BHIP_PF_GROUP8_MAX_EXPECT records per query (beyond two rows the records are loaded twice, and 512 slots fill up);
+//  * the lane's previous chain left at most BHIP_PF_GROUP8_MAX_SURV survivors per query (a strain-rich lane: its queries fill the 16-slot
+//    table and would all go through the BIG pass; surv_last < 0: no chain yet, the lane's first batch goes by expect alone).
+// opt_group: 0 = by this rule, 8 / 16 = that width wherever the kernel has it.  Both limits are measurements (profiles/prefilter_group8.md,
+// ms per launch at 16 / 8 lanes, 2 M 100-bp reads per batch on one MI355X):
+//  * expect 37 (2.77 GB database): 0.78 / 0.69; 64 (5.5 GB): 0.83 / 0.73; 117 (11 GB, 88 records read per query): 0.96 / 0.88 -- 8 lanes win by
+//    more than three times the leg-to-leg difference (at 117 in one run of two; every leg of the other has the same sign); 223 (22 GB, 173 records read): 1.14 / 1.83 -- they lose.  The limit sits at the two
+//    resident rows, between the last win and the first loss.
+//  * survivors per query: 6.3 - 6.9 on those databases; 34 - 52 on the strain-rich profile at 2.6 GB, where 8 lanes take 10.2 ms against 7.2.
+//    The limit sits where a round of 8 no longer holds the mean query's survivors with some room; nothing between 7 and 34 was measured.
+#define BHIP_PF_GROUP8_MAX_EXPECT 128.0
+#define BHIP_PF_GROUP8_MAX_SURV 12.0
+static inline int bhip_pf_group(int opt_group, const BhipPfChoice &c, uint32_t W16, double expect, double surv_last) {
+	if (c.kind != BHIP_PF_CQ || c.cw_mode != 0 || W16 > 8 || opt_group == 16) return 16;
+	if (opt_group == 8) return 8;
+	return expect <= BHIP_PF_GROUP8_MAX_EXPECT && surv_last <= BHIP_PF_GROUP8_MAX_SURV ? 8 : 16;
 }
 
 // Leaving out a query's longest list (k_seed_ranges: its guaranteed count drops from 4 to 3 for a 100-bp read at 98 %) walks ~21 % fewer

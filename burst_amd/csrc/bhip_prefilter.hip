@@ -1,5 +1,5 @@
 // burst_amd/csrc/bhip_prefilter.hip -- the product's lane-resolved prefilter: k_seed_ranges (sampled words -> accelerator list ranges) and
-// k_prefilter_cq (four queries per wave, their record streams walked by the whole wave).  Replaces word extraction + qsort + postScour20/24 +
+// k_prefilter_cq (four or eight queries per wave, their record streams walked by the whole wave).  Replaces word extraction + qsort + postScour20/24 +
 // selection (burst.c:4096-4133, 3238-3285).  The fallbacks a batch can reach (plans beyond 16 lists, overflowed queries, the clump-level
 // path, the exact-table kernel for FORAGE over dense families) are in bhip_prefilter_alt.hip; the superseded counting-filter kernels
 // (k_prefilter_cf, k_prefilter_cw<0 / 1>) in bhip_prefilter_legacy.hip, outside the product library.
@@ -161,6 +161,10 @@ __global__ __launch_bounds__(256) void k_seed_ranges(
 //    repeat its last record), the records of the first R rows stay in registers between the looks.
 // For lists per query <= 16 (MODE 0: <= 8, byte slots; MODE 1: halfword slots); longer plans keep k_prefilter_cw<2>.  BIG = 1: the second
 // pass over queries whose survivors overflowed the 32-slot exact table of the first, with four times the slots and the table.
+// GW = lanes per query (16, or 8 for <0, 0> alone): in slot mode 0 a query has at most 8 lists, one or two used table slots and a handful of
+// survivors on a small database, so half of every group idles through the per-quad half above.  With 8 lanes a wave serves EIGHT queries
+// with the same instruction stream (an "octet" wherever the code says quad), and each query owns half of everything: 512 byte slots, a
+// 16-slot exact table, rounds of 8 survivors, a 32-entry ring, two resident rows.  Which width a launch gets: bhip_pf_group (bhip_pf_select.h).
 // ------------------------------------------------------------------------------------------------
 #ifndef CQ_MINWAVES
 #define CQ_MINWAVES 1          // waves per SIMD the register allocation aims at (tools/build_variant.sh: -DCQ_MINWAVES=5 -DCQ_LTB=4 -DCQ_STAGE_N=32 for the occupancy A/B)
@@ -177,7 +181,7 @@ __global__ __launch_bounds__(256) void k_seed_ranges(
 #ifndef CQ_RING
 #define CQ_RING 64             // survivors of a query waiting for the rounds at the end of the quad (a power of two, >= one row... or half a row with CQ_RING=32: drained more often)
 #endif
-template <int MODE, int BIG>
+template <int MODE, int BIG, int GW_>
 __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 		const uint2 *__restrict__ ranges, const uint2 *__restrict__ hdr, uint32_t W16, uint32_t n_list,
 		const uint32_t *__restrict__ ent,   // 4-byte (clump, lane-set code) records
@@ -189,27 +193,32 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 		unsigned long long *__restrict__ surv_sum,
 		uint2 *__restrict__ tasks2, uint32_t *__restrict__ n_tasks2, int prune,
 		const uint32_t *__restrict__ sel, const uint32_t *__restrict__ n_sel_dev, int) {
+	static_assert(GW_ == 16 || (GW_ == 8 && MODE == 0 && BIG == 0), "eight lanes per query: slot mode 0 (at most 8 lists), first pass only");
+	// Group geometry: GW lanes per query, QW queries per wave (a "quad" of four, or an octet).  With 8 lanes the per-query tables are halved
+	// so that a wave's LDS stays what it was: 512 byte slots (the streams the rule of bhip_pf_group admits load them to 0.07 .. 0.25), a
+	// 16-slot exact table (a query with more distinct surviving clumps goes to the BIG pass, as one that overflows 32 does), a 32-entry ring.
+	constexpr uint32_t GW = (uint32_t)GW_, QW = 64u / GW, GMASK = (1u << GW) - 1u, GBASE = 64u - GW;      // lanes per query, queries per wave, a group's bits of a ballot, lane -> first lane of its group
 	constexpr uint32_t FB = MODE == 0 ? 8u : 16u;                         // bits per slot
 	constexpr uint32_t SB = MODE == 0 ? 2u : 1u;                          // log2 slots per dword
-	constexpr uint32_t NDW = BIG ? 1024u : 256u;                          // dwords of slots per query: 1 KB (4 KB)
+	constexpr uint32_t NDW = BIG ? 1024u : GW == 8u ? 128u : 256u;        // dwords of slots per query: 1 KB (4 KB; 512 B with 8 lanes)
 	constexpr uint32_t NS = NDW << SB;                                    // slots per query
-	constexpr uint32_t LTB = BIG ? 7u : (uint32_t)CQ_LTB, LT = 1u << LTB;               // exact lane-table slots per query
-	constexpr uint32_t RING = (uint32_t)CQ_RING;                          // survivors of a query waiting for the rounds at the end of the quad
+	constexpr uint32_t LTB = BIG ? 7u : GW == 8u ? 4u : (uint32_t)CQ_LTB, LT = 1u << LTB;               // exact lane-table slots per query
+	constexpr uint32_t RING = GW == 8u ? 32u : (uint32_t)CQ_RING;         // survivors of a query waiting for the rounds at the end of the quad
 	constexpr uint32_t CQ_STAGE = (uint32_t)CQ_STAGE_N;
-	constexpr uint32_t R = (uint32_t)CQ_R;                                // rows of 64 records of a query that stay in registers between the two looks
-	__shared__ __attribute__((aligned(16))) uint32_t s_cnt[4][NDW];
-	__shared__ uint32_t s_key[4][LT];
-	__shared__ unsigned long long s_lc[4][LT][2];
-	__shared__ uint32_t s_ring[4][RING];
+	constexpr uint32_t R = GW == 8u ? 2u : (uint32_t)CQ_R;                // rows of 64 records of a query that stay in registers between the two looks
+	__shared__ __attribute__((aligned(16))) uint32_t s_cnt[QW][NDW];
+	__shared__ uint32_t s_key[QW][LT];
+	__shared__ unsigned long long s_lc[QW][LT][2];
+	__shared__ uint32_t s_ring[QW][RING];
 	__shared__ uint16_t s_lut[256];
-	__shared__ uint8_t s_used[4][LT];
+	__shared__ uint8_t s_used[QW][LT];
 	__shared__ uint2 s_stage[2][CQ_STAGE];
 	__shared__ uint32_t s_dummy[16];          // compare-and-swap target of idle lanes (never written: the compare value cannot match)
-	const uint32_t lane = threadIdx.x, g = lane >> 4, gl = lane & 15u;
+	const uint32_t lane = threadIdx.x, g = lane / GW, gl = lane % GW;
 	if (lane < 16) s_dummy[lane] = 0;
 	for (uint32_t i = lane; i < 256; i += 64) s_lut[i] = (uint16_t)bhip_lane_code_mask(i);
-	for (uint32_t i = lane; i < 4 * NDW; i += 64) (&s_cnt[0][0])[i] = 0;
-	for (uint32_t i = lane; i < 4 * LT; i += 64) { (&s_key[0][0])[i] = 0; (&s_lc[0][0][0])[2 * i] = 0; (&s_lc[0][0][0])[2 * i + 1] = 0; }
+	for (uint32_t i = lane; i < QW * NDW; i += 64) (&s_cnt[0][0])[i] = 0;
+	for (uint32_t i = lane; i < QW * LT; i += 64) { (&s_key[0][0])[i] = 0; (&s_lc[0][0][0])[2 * i] = 0; (&s_lc[0][0][0])[2 * i + 1] = 0; }
 	__syncthreads();
 	uint32_t my_ent = 0, my_units = 0, my_qlen = 0, my_surv = 0;         // (per wave and launch: well inside 32 bits)
 	const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -244,34 +253,42 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 		if (mine) s_stage[which][nst[which] + (uint32_t)__popcll(m & lt_mask)] = make_uint2(a, b);
 		nst[which] += cnt;
 	};
-	auto group_scan = [&](uint32_t n) -> uint32_t {                       // inclusive prefix sum inside each group of 16 lanes
+	auto group_scan = [&](uint32_t n) -> uint32_t {                       // inclusive prefix sum inside each group of GW lanes
 		int ps = (int)n;
+		if constexpr (GW == 8u) {
+			// a row of the data-parallel moves is 16 lanes = two groups: a lane whose source lies in the neighbouring group adds 0
+			int t;
+			t = __builtin_amdgcn_update_dpp(0, ps, 0x111, 0xF, 0xF, false); ps += gl >= 1u ? t : 0;
+			t = __builtin_amdgcn_update_dpp(0, ps, 0x112, 0xF, 0xF, false); ps += gl >= 2u ? t : 0;
+			t = __builtin_amdgcn_update_dpp(0, ps, 0x114, 0xF, 0xF, false); ps += gl >= 4u ? t : 0;
+			return (uint32_t)ps;
+		}
 		ps += __builtin_amdgcn_update_dpp(0, ps, 0x111, 0xF, 0xF, false);    // row_shr:1 (a row = the 16 lanes of a group; lanes without a source add 0)
 		ps += __builtin_amdgcn_update_dpp(0, ps, 0x112, 0xF, 0xF, false);
 		ps += __builtin_amdgcn_update_dpp(0, ps, 0x114, 0xF, 0xF, false);
 		ps += __builtin_amdgcn_update_dpp(0, ps, 0x118, 0xF, 0xF, false);
 		return (uint32_t)ps;
 	};
-	auto group_max = [&](uint32_t v) -> uint32_t {                        // maximum over the 16 lanes of the group, in every lane
+	auto group_max = [&](uint32_t v) -> uint32_t {                        // maximum over the GW lanes of the group, in every lane
 		int t;
 		t = __builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false); v = (uint32_t)t > v ? (uint32_t)t : v;     // quad_perm:[1,0,3,2]
 		t = __builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false); v = (uint32_t)t > v ? (uint32_t)t : v;     // quad_perm:[2,3,0,1]
 		t = __builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false); v = (uint32_t)t > v ? (uint32_t)t : v;    // row_half_mirror
-		t = __builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false); v = (uint32_t)t > v ? (uint32_t)t : v;    // row_mirror
+		if constexpr (GW == 16u) { t = __builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false); v = (uint32_t)t > v ? (uint32_t)t : v; }    // row_mirror
 		return v;
 	};
-	auto wave_max4 = [&](uint32_t v) -> uint32_t {                        // maximum over the four groups of a group-uniform value
-		const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), b = (uint32_t)__builtin_amdgcn_readlane((int)v, 16),
-			c = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), d = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-		const uint32_t ab = a > b ? a : b, cd = c > d ? c : d;
-		return ab > cd ? ab : cd;
+	auto wave_max_groups = [&](uint32_t v) -> uint32_t {                  // maximum over the QW groups of a group-uniform value
+		uint32_t m = 0;
+		#pragma unroll
+		for (uint32_t q = 0; q < QW; ++q) { const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)(q * GW)); m = a > m ? a : m; }
+		return m;
 	};
 	auto spread4 = [](uint32_t nib) -> uint32_t { return (nib * 0x00204081u) & 0x01010101u; };      // bit i of a nibble -> bit 8 i
 	const uint32_t n_items = sel ? (*n_sel_dev < n_list ? *n_sel_dev : n_list) : n_list;
-	const uint32_t n_quads = (n_items + 3) >> 2;
+	const uint32_t n_quads = (n_items + QW - 1u) / QW;
 	typedef const unsigned long long __attribute__((address_space(1))) *g64_t;
 	auto fetch = [&](uint32_t quad, unsigned long long &h, unsigned long long &r) {      // header of this group's query and range gl of it (clamped: always a valid address)
-		const uint32_t it = quad * 4 + g;
+		const uint32_t it = quad * QW + g;
 		const uint32_t itc = it < n_items ? it : 0u;
 		const uint32_t lic = sel ? (n_items ? sel[itc] : 0u) : itc;
 		h = ((g64_t)(uintptr_t)(hdr + lic))[0];
@@ -285,29 +302,29 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 	// its loads are issued right there (`prep`), and they are in flight during this quad's survivor rounds, emit and table clears.  What a quad
 	// needs after its second look (list position, threshold, budget, ...) is copied out of the carried state at the top of its iteration.
 	constexpr uint32_t NB = MODE == 0 ? 7u : 15u, KB = MODE == 0 ? 3u : 4u;      // list ends that matter / bits of a list number
-	uint32_t rc[4][R];                                                // records of the resident rows of the quad that is looked at next
-	bool n_live = false; uint32_t n_li = 0, n_hx = 0, n_hy = 0, n_eend = 0, n_krp[4] = {0u, 0u, 0u, 0u}; unsigned long long n_ab = 0;
+	uint32_t rc[QW][R];                                               // records of the resident rows of the quad that is looked at next
+	bool n_live = false; uint32_t n_li = 0, n_hx = 0, n_hy = 0, n_eend = 0, n_krp[QW] = {}; unsigned long long n_ab = 0;
 	auto row_rec_of = [&](uint32_t q, uint32_t T, const uint32_t (&eb)[NB], uint32_t r, uint32_t &kreg, unsigned long long ab_) -> uint32_t {
 		const uint32_t i = r * 64u + lane;
 		const uint32_t ic = i < T ? i : T - 1u;                       // beyond the stream: its last record once more (OR is idempotent; the second look tests i < T)
 		uint32_t kk = 0;
 		#pragma unroll
 		for (uint32_t j = 0; j < NB; ++j) kk += eb[j] <= ic ? 1u : 0u;          // lists that end at or before the position = its list
-		const uint32_t src = q * 16u + kk;
+		const uint32_t src = q * GW + kk;
 		const uint32_t a_lo = (uint32_t)__shfl((int)(uint32_t)ab_, (int)src, 64), a_hi = (uint32_t)__shfl((int)(uint32_t)(ab_ >> 32), (int)src, 64);
 		kreg = kk;
 		return ((bhip_gptr_t)(uintptr_t)(((unsigned long long)a_hi << 32 | a_lo) + 4ull * ic))[0];
 	};
 	auto list_ends_of = [&](uint32_t q, uint32_t (&eb)[NB], uint32_t eend_) {           // ends of the query's lists but the last: wave-uniform
 		#pragma unroll
-		for (uint32_t j = 0; j < NB; ++j) eb[j] = (uint32_t)__builtin_amdgcn_readlane((int)eend_, (int)(q * 16u + j));
+		for (uint32_t j = 0; j < NB; ++j) eb[j] = (uint32_t)__builtin_amdgcn_readlane((int)eend_, (int)(q * GW + j));
 	};
 	// the lists of quad `quad`'s queries (lane gl of group g = list gl of query g; eend = end of the list in its query's flattened stream;
 	// ab = biased address: the record at stream position i of the list is at ab + 4 i), the loads of the first R rows of ALL four queries
 	// (their gathers are in flight together), and the header / ranges of the quad after it
 	auto prep = [&](uint32_t quad) {
-		n_live = quad * 4 + g < n_items;
-		n_li = sel ? (n_live ? sel[quad * 4 + g] : 0u) : quad * 4 + g;      // list position of this group's query
+		n_live = quad * QW + g < n_items;
+		n_li = sel ? (n_live ? sel[quad * QW + g] : 0u) : quad * QW + g;    // list position of this group's query
 		n_hx = (uint32_t)h_n; n_hy = (uint32_t)(h_n >> 32);
 		const unsigned long long r_c = r_n;
 		fetch(quad + gridDim.x, h_n, r_n);                                // one quad ahead
@@ -317,8 +334,8 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 		n_eend = group_scan(n0);
 		n_ab = (unsigned long long)(uintptr_t)ent + 4ull * (beg - (unsigned long long)(n_eend - n0));
 		#pragma unroll
-		for (uint32_t q = 0; q < 4; ++q) {
-			const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)n_eend, (int)(q * 16u + 15u));
+		for (uint32_t q = 0; q < QW; ++q) {
+			const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)n_eend, (int)(q * GW + GW - 1u));
 			n_krp[q] = 0;
 			if (T == 0u) continue;                                        // (wave-uniform)
 			my_ent += T;
@@ -339,31 +356,34 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 		const uint32_t thr = need ? need : 1u;                            // (group-uniform)
 		const uint32_t eend = n_eend;
 		const unsigned long long ab = n_ab;
-		const uint32_t krp[4] = {n_krp[0], n_krp[1], n_krp[2], n_krp[3]};
-		uint32_t pend[4] = {0u, 0u, 0u, 0u};                              // survivors waiting in the queries' rings (wave-uniform)
+		uint32_t krp[QW], pend[QW];                                       // pend: survivors waiting in the queries' rings (wave-uniform)
+		#pragma unroll
+		for (uint32_t q = 0; q < QW; ++q) { krp[q] = n_krp[q]; pend[q] = 0u; }
 		uint32_t nused = 0, ovf = 0;                                      // slots of this group's lane table in use / table overflow (replicated in the group)
-		// ---- survivor rounds: every group moves up to 16 survivors of its query into its exact lane table
+		// ---- survivor rounds: every group moves up to GW survivors of its query into its exact lane table
 		auto drain = [&]() {
-			uint32_t pv = g == 0 ? pend[0] : g == 1 ? pend[1] : g == 2 ? pend[2] : pend[3];
+			uint32_t pv = 0;
+			#pragma unroll
+			for (uint32_t q = 0; q < QW; ++q) pv = g == q ? pend[q] : pv;
 			uint32_t head = 0;
 			while (__any(pv > 0)) {
-				const uint32_t take = pv < 16u ? pv : 16u;
+				const uint32_t take = pv < GW ? pv : GW;
 				const bool active = gl < take;
 				const uint32_t rec = active ? s_ring[g][head + gl] : 0u;
 				const uint32_t clump = rec & 0xFFFFFFu, key = clump + 1u, mask = s_lut[rec >> 24];
 				uint32_t slot = (clump * 0x85EBCA6Bu) >> (32u - LTB);
 				bool act = active, found = false, fresh = false;
 				for (uint32_t probes = 0; __any(act) && probes < LT; ++probes) {
-					const uint32_t old = atomicCAS(act ? &s_key[g][slot] : &s_dummy[gl], act ? 0u : 0xFFFFFFFFu, key);
+					const uint32_t old = atomicCAS(act ? &s_key[g][slot] : &s_dummy[lane & 15u], act ? 0u : 0xFFFFFFFFu, key);
 					const bool ok = act && (old == 0u || old == key);
 					fresh |= act && old == 0u;
 					found |= ok;
 					act = act && !ok;
 					slot = act ? (slot + 1u) & (LT - 1u) : slot;
 				}
-				const uint32_t m_act = (uint32_t)(__ballot(act) >> (lane & 48u)) & 0xFFFFu;
+				const uint32_t m_act = (uint32_t)(__ballot(act) >> (lane & GBASE)) & GMASK;
 				if (m_act) ovf = 1u;
-				const uint32_t m16 = (uint32_t)(__ballot(fresh) >> (lane & 48u)) & 0xFFFFu;
+				const uint32_t m16 = (uint32_t)(__ballot(fresh) >> (lane & GBASE)) & GMASK;
 				if (fresh) s_used[g][nused + __popc(m16 & ((1u << gl) - 1u))] = (uint8_t)slot;
 				nused += __popc(m16);
 				if (found) {
@@ -374,13 +394,14 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 				}
 				head += take; pv -= take;
 			}
-			pend[0] = pend[1] = pend[2] = pend[3] = 0;
+			#pragma unroll
+			for (uint32_t q = 0; q < QW; ++q) pend[q] = 0;
 		};
 		PFM_T(6);
 		// ---- the record streams, 64 stream positions per row: the first R rows of the four queries are in `rc` (issued by prep one quad ago)
-		uint32_t Tq[4];
+		uint32_t Tq[QW];
 		#pragma unroll
-		for (uint32_t q = 0; q < 4; ++q) Tq[q] = (uint32_t)__builtin_amdgcn_readlane((int)eend, (int)(q * 16u + 15u));
+		for (uint32_t q = 0; q < QW; ++q) Tq[q] = (uint32_t)__builtin_amdgcn_readlane((int)eend, (int)(q * GW + GW - 1u));
 		auto row_rec = [&](uint32_t q, uint32_t T, const uint32_t (&eb)[NB], uint32_t r, uint32_t &kreg) -> uint32_t { return row_rec_of(q, T, eb, r, kreg, ab); };
 		auto list_ends = [&](uint32_t q, uint32_t (&eb)[NB]) { list_ends_of(q, eb, eend); };
 		PFM_T(0);
@@ -388,7 +409,7 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 			atomicOr(&s_cnt[q][(rec & (NS - 1u)) >> SB], 1u << ((rec & ((1u << SB) - 1u)) * FB + kreg));
 		};
 		#pragma unroll
-		for (uint32_t q = 0; q < 4; ++q) {
+		for (uint32_t q = 0; q < QW; ++q) {
 			const uint32_t T = Tq[q];
 			if (T == 0u) continue;
 			const uint32_t rows = (T + 63u) >> 6;
@@ -403,20 +424,34 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 		CF_WAVE_ORDER();
 		PFM_T(1);
 		#pragma unroll
-		for (uint32_t q = 0; q < 4; ++q) {
+		for (uint32_t q = 0; q < QW; ++q) {
 			const uint32_t T = Tq[q];
 			if (T == 0u) continue;
 			const uint32_t rows = (T + 63u) >> 6;
-			const uint32_t thr_q = (uint32_t)__builtin_amdgcn_readlane((int)thr, (int)(q * 16u));
+			const uint32_t thr_q = (uint32_t)__builtin_amdgcn_readlane((int)thr, (int)(q * GW));
 			auto offer1 = [&](uint32_t rec, uint32_t i) {                 // second look: records whose slot names enough lists go to the query's ring
 				const uint32_t f = (s_cnt[q][(rec & (NS - 1u)) >> SB] >> ((rec & ((1u << SB) - 1u)) * FB)) & ((1u << FB) - 1u);
 				const bool surv = (uint32_t)__popc(f) >= thr_q && i < T;
 				const unsigned long long m = __ballot(surv);
 				if (m) {
 					const uint32_t cnt = (uint32_t)__popcll(m);
-					if (pend[q] + cnt > RING) drain();                    // (rare: the rings are drained at the end of every quad)
-					if (surv) s_ring[q][pend[q] + (uint32_t)__popcll(m & lt_mask)] = rec;
-					pend[q] += cnt;
+					if constexpr (RING >= 64u) {
+						if (pend[q] + cnt > RING) drain();                // (rare: the rings are drained at the end of every quad)
+						if (surv) s_ring[q][pend[q] + (uint32_t)__popcll(m & lt_mask)] = rec;
+						pend[q] += cnt;
+					} else {
+						// a ring shorter than a row: what does not fit is held back while the rings are drained (rare; twice for a row of survivors)
+						const uint32_t rank = (uint32_t)__popcll(m & lt_mask);
+						uint32_t done = 0;
+						while (pend[q] + (cnt - done) > RING) {
+							const uint32_t room = RING - pend[q];
+							if (surv && rank >= done && rank < done + room) s_ring[q][pend[q] + (rank - done)] = rec;
+							pend[q] = RING; done += room;
+							drain();
+						}
+						if (surv && rank >= done) s_ring[q][pend[q] + (rank - done)] = rec;
+						pend[q] += cnt - done;
+					}
 					my_surv += cnt;
 				}
 			};
@@ -442,7 +477,7 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 		// once; the others wait for the minimum those produce (k_task_filter).
 		const bool em = live && !ovf;
 		const uint32_t nu = em ? nused : 0u;
-		const uint32_t nu_max = wave_max4(nu);
+		const uint32_t nu_max = wave_max_groups(nu);
 		const uint32_t inv_dper = 65536u / dper + 1u;                     // x / dper == (x * inv_dper) >> 16 for x < 256, dper < 16
 		auto lanes_ge = [&](unsigned long long lo, unsigned long long hi, uint32_t t) -> uint32_t {      // 16-bit set of the slot's lane counters >= t (t < 128)
 			const unsigned long long H = 0x8080808080808080ull, L1 = 0x0101010101010101ull, G = 0x0102040810204080ull;
@@ -470,7 +505,7 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 		if (prune) {
 			uint32_t cmax = 0;
 			for (uint32_t m = m16_0; m; m &= m - 1) { const uint32_t v = byte_of(lo0, hi0, (uint32_t)__builtin_ctz(m)); cmax = v > cmax ? v : cmax; }
-			for (uint32_t iu0 = 16; iu0 < nu_max; iu0 += 16) {
+			for (uint32_t iu0 = GW; iu0 < nu_max; iu0 += GW) {
 				uint32_t sl, c; unsigned long long lo, hi;
 				for (uint32_t m = look(iu0 + gl, sl, c, lo, hi); m; m &= m - 1) { const uint32_t v = byte_of(lo, hi, (uint32_t)__builtin_ctz(m)); cmax = v > cmax ? v : cmax; }
 			}
@@ -510,26 +545,27 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 			PFM_T(4);
 		};
 		if (nu_max) emit_slots(gl, slot0, c0, lo0, hi0, m16_0);
-		for (uint32_t iu0 = 16; iu0 < nu_max; iu0 += 16) {
+		for (uint32_t iu0 = GW; iu0 < nu_max; iu0 += GW) {
 			uint32_t sl, c; unsigned long long lo, hi;
 			const uint32_t m16 = look(iu0 + gl, sl, c, lo, hi);
 			emit_slots(iu0 + gl, sl, c, lo, hi, m16);
 		}
 		for (uint32_t i = 0; i < n_bad; ++i) {                            // burst.c:4136-4138, 4282-4283: every lane of the ambiguous clumps
 			const uint32_t c = bad[i];
-			put(0, em && c * 16u + gl < tot_refs, li, c * 16u + gl);
+			#pragma unroll
+			for (uint32_t z0 = 0; z0 < 16u; z0 += GW) put(0, em && c * 16u + z0 + gl < tot_refs, li, c * 16u + z0 + gl);      // (8 lanes per query: the clump's 16 reference lanes in two halves)
 			if (em && gl == 0) { ++my_units; my_qlen += len; }
 		}
 		if (__any(ovf != 0u)) {
 			if (ovf) {
-				for (uint32_t i = gl; i < LT; i += 16) { s_key[g][i] = 0; s_lc[g][i][0] = 0; s_lc[g][i][1] = 0; }
+				for (uint32_t i = gl; i < LT; i += GW) { s_key[g][i] = 0; s_lc[g][i][0] = 0; s_lc[g][i][1] = 0; }
 				if (live && gl == 0) { const uint32_t pos = atomicAdd(n_fb, 1u); fb_list[pos] = li; }
 			}
 		}
 		PFM_T(3);
 		{
 			uint4 *cz4 = (uint4 *)&s_cnt[0][0];
-			for (uint32_t i = lane; i < 4u * NDW / 4u; i += 64) cz4[i] = make_uint4(0, 0, 0, 0);
+			for (uint32_t i = lane; i < QW * NDW / 4u; i += 64) cz4[i] = make_uint4(0, 0, 0, 0);
 		}
 		CF_WAVE_ORDER();
 		PFM_T(5);
@@ -545,11 +581,11 @@ __global__ __launch_bounds__(64, CQ_MINWAVES) void k_prefilter_cq(
 	if (my_units) { atomicAdd(unit_sum, (unsigned long long)my_units); atomicAdd(qlen_sum, (unsigned long long)my_qlen); }
 	(void)clump_len; (void)col_sum;
 }
-#define BHIP_INST_PFCQ(M, B) \
-	template __global__ void k_prefilter_cq<M, B>(const uint2 *, const uint2 *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, uint32_t, const uint32_t *, uint32_t, \
+#define BHIP_INST_PFCQ(M, B, G) \
+	template __global__ void k_prefilter_cq<M, B, G>(const uint2 *, const uint2 *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, uint32_t, const uint32_t *, uint32_t, \
 		uint2 *, uint32_t *, uint32_t, unsigned long long *, uint32_t *, uint32_t *, unsigned long long *, unsigned long long *, unsigned long long *, unsigned long long *, \
 		uint2 *, uint32_t *, int, const uint32_t *, const uint32_t *, int);
-BHIP_INST_PFCQ(0, 0) BHIP_INST_PFCQ(1, 0) BHIP_INST_PFCQ(0, 1) BHIP_INST_PFCQ(1, 1)
+BHIP_INST_PFCQ(0, 0, 16) BHIP_INST_PFCQ(1, 0, 16) BHIP_INST_PFCQ(0, 1, 16) BHIP_INST_PFCQ(1, 1, 16) BHIP_INST_PFCQ(0, 0, 8)
 
 
 #ifdef PFM_PROF
