@@ -48,7 +48,7 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_comm_create", "bhip_comm_unique_id", "bhip_comm_create_rank", "bhip_comm_allreduce_min", "bhip_comm_fetch_gathered", "bhip_comm_gather_hits", "bhip_comm_stage_device", "bhip_comm_gather_staged", "bhip_comm_stage_reset", "bhip_comm_destroy", "bhip_acx_export", "bhip_reserve", "bhip_reserve_symbols", "bhip_sort_queries", "bhip_stage_spans", "bhip_alloc_host", "bhip_free_host", "bhip_host_register", "bhip_host_unregister", "bhip_set_enqueued_hook", "bhip_acx_export_entries",
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
-           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_pile_run", "bhip_consensus_run", "bhip_consensus_info",
+           "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_taxa_run", "bhip_taxa_rollup", "bhip_pile_run", "bhip_consensus_run", "bhip_consensus_info",
            "bhip_alleles_run", "bhip_alleles_info",
            "bhip_cluster_run", "bhip_cluster_info", "bhip_chimera_run", "bhip_chimera_info", "bhip_md_tags"]
 
@@ -270,6 +270,10 @@ def _load():
     lib.bhip_mates_info.restype = i32
     lib.bhip_em_run.argtypes = [vp, u32, u32, vp, vp, u64, u32, u64, vp, vp]
     lib.bhip_em_run.restype = i32
+    lib.bhip_taxa_run.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, u64, u32, vp, vp, vp, vp]
+    lib.bhip_taxa_run.restype = i32
+    lib.bhip_taxa_rollup.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
+    lib.bhip_taxa_rollup.restype = i32
     lib.bhip_pile_run.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, C.POINTER(u64), vp]
     lib.bhip_pile_run.restype = i32
     lib.bhip_consensus_run.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), vp]
@@ -535,6 +539,29 @@ class Device:
         info = np.zeros(4, np.uint64)
         _chk(lib().bhip_mates_info(self._h, _ptr(info)))
         return dict(zip(("us_last", "us_total", "lines", "combinations"), (int(x) for x in info)))
+
+    def taxa_run(self, parent, header_node, group_w, lines, agree=1000):
+        """the taxa of one sample's groups (bhip_taxa_run): parent[v] of a tree numbered in preorder, header_node[h], group_w[g] = reads of group
+        g, lines: EM_LINE_DTYPE array (or rows group, ref), agree in permille.  Returns (group_node uint32 [groups], 0xFFFFFFFF = no lines;
+        own, clade uint64 [nodes]; info uint64 [8]: pairs, groups with lines, their reads, reads at the root, deepest level, device
+        microseconds, peak device bytes, 0)"""
+        parent, header_node = np.ascontiguousarray(parent, dtype=np.uint32), np.ascontiguousarray(header_node, dtype=np.uint32)
+        group_w = np.ascontiguousarray(group_w, dtype=np.uint32)
+        lines = em_lines(lines)
+        nn = len(parent)
+        gn, own, clade, info = np.zeros(max(len(group_w), 1), np.uint32), np.zeros(max(nn, 1), np.uint64), np.zeros(max(nn, 1), np.uint64), np.zeros(8, np.uint64)
+        _chk(lib().bhip_taxa_run(self._h, nn, _ptr(parent), len(header_node), _ptr(header_node), len(group_w), _ptr(group_w), _ptr(lines), len(lines), int(agree),
+                                 _ptr(gn), _ptr(own), _ptr(clade), _ptr(info)))
+        return gn[:len(group_w)], own[:nn], clade[:nn], info
+
+    def taxa_rollup(self, parent, header_node, header_count):
+        """counts per header summed per node and per subtree (bhip_taxa_rollup): (own, clade) uint64 [nodes]"""
+        parent, header_node = np.ascontiguousarray(parent, dtype=np.uint32), np.ascontiguousarray(header_node, dtype=np.uint32)
+        header_count = np.ascontiguousarray(header_count, dtype=np.uint64)
+        nn = len(parent)
+        own, clade = np.zeros(max(nn, 1), np.uint64), np.zeros(max(nn, 1), np.uint64)
+        _chk(lib().bhip_taxa_rollup(self._h, nn, _ptr(parent), len(header_node), _ptr(header_node), _ptr(header_count), _ptr(own), _ptr(clade)))
+        return own[:nn], clade[:nn]
 
     def em_run(self, n_headers, group_w, lines, max_iters=1000, tol=1024):
         """abundance of one sample (bhip_em_run): group_w[g] = reads of group g, lines: EM_LINE_DTYPE array (or rows group, ref).  Returns

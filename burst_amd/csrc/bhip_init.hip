@@ -78,6 +78,7 @@ extern "C" void bhip_destroy(void *handle) {
 	bhip_alleles_release(h);
 	bhip_pile_release(h);
 	bhip_cluster_release(h);
+	bhip_taxa_release(h);
 	bhip_chimera_release(h);
 	bhip_md_release(h);
 	if (h->hsc_pinned) (void)hipHostFree(h->hsc_pinned);

@@ -276,6 +276,8 @@ void bh_em_last_info(const BhEm *em, uint64_t info[8], uint64_t *reads) {
 	if (reads) *reads = em && em->have_info ? em->reads : 0;
 }
 
+const uint64_t *bh_em_last_column(const BhEm *em) { return em && em->nCols && !em->dead ? em->cols[em->nCols - 1] : NULL; }
+
 void bh_em_close(BhEm *em) {
 	if (!em) return;
 	for (uint32_t c = 0; c < em->nCols; ++c) { free(em->names[c]); free(em->cols[c]); }

@@ -35,6 +35,7 @@ struct BhSession {
 	SessIngest *cur, *ahead; pthread_t th; char *pending;
 	FILE *out; char *out_path;
 	char *cov_name;                 /* with a coverage or an abundance: the output the loaded sample was given (names its column, also when the sample fails) */
+	int taxa_col;                   /* ... and its column in the taxon tables */
 	int cov_col, em_col, pile_col, cons_col;  /* the loaded sample has its column in the coverage / the abundance, its block in the variants / the consensus already */
 	BhPlaceSink sink;               /* the report's placements of the current sample (buffer kept across samples) */
 	BhMates *mates;                 /* bh_session_run_mates: the joiner, made on first use */
@@ -43,6 +44,7 @@ struct BhSession {
 	BhSam *sam;                     /* bh_session_set_sam: NULL, or the SAM writer every reported sample is given */
 	BhCons *cons;                   /* bh_session_set_consensus: NULL, or the consensus every reported sample feeds */
 	BhVcf *vcf;                     /* bh_session_set_vcf: NULL, or the VCF writer every reported sample is given */
+	BhTaxa *taxa;                   /* bh_session_set_taxa: NULL, or the taxon tables every reported sample feeds */
 	BhPaths *paths;                 /* with o.cigar, o.pile, a consensus, a chimera check or a SAM writer: the tracer on the reporting rank's handle, opened by the first sample that reports */
 	int dead, dbg, threads_ok;
 	int alive;                      /* query tables alive (the current sample's and the prefetched one's) */
@@ -119,6 +121,7 @@ int bh_session_set_cluster(BhSession *s, BhCluster *cl) {
 	if (cl && s->o.mode != BH_FORAGE) return bh_set_error(BH_E_USAGE, "ERROR: clusters need every relationship under the identity cutoff: a session in mode FORAGE");
 	if (cl && s->cons) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with the consensus");
 	if (cl && s->vcf) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with the VCF output");
+	if (cl && s->taxa) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with the taxon tables");
 	if (cl && (s->o.cov || s->o.em || s->o.pile || s->o.shard_db > 1)) return bh_set_error(BH_E_USAGE, "ERROR: clusters do not go with coverage, abundance, variants or database shards");
 	s->cluster = cl;
 	return BH_OK;
@@ -128,6 +131,7 @@ int bh_session_set_chimera(BhSession *s, BhChimera *ch) {
 	if (ch && s->o.mode != BH_FORAGE) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check needs every relationship under the identity cutoff: a session in mode FORAGE");
 	if (ch && s->cons) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check does not go with the consensus");
 	if (ch && s->vcf) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check does not go with the VCF output");
+	if (ch && s->taxa) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check does not go with the taxon tables");
 	if (ch && (s->o.cov || s->o.em || s->o.pile || s->o.shard_db > 1)) return bh_set_error(BH_E_USAGE, "ERROR: the chimera check does not go with coverage, abundance, variants or database shards");
 	s->chimera = ch;
 	return BH_OK;
@@ -150,6 +154,12 @@ int bh_session_set_vcf(BhSession *s, BhVcf *vcf) {
 	if (vcf && s->o.shard_db > 1) return bh_set_error(BH_E_USAGE, "ERROR: --vcf traces the paths on rank 0's handle, which must hold the whole database: it does not go with database shards");
 	if (vcf && (s->cluster || s->chimera)) return bh_set_error(BH_E_USAGE, "ERROR: the VCF output does not go with clusters or the chimera check");
 	s->vcf = vcf;
+	return BH_OK;
+}
+int bh_session_set_taxa(BhSession *s, BhTaxa *tx) {
+	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_taxa: no session");
+	if (tx && (s->cluster || s->chimera)) return bh_set_error(BH_E_USAGE, "ERROR: the taxon tables do not go with clusters or the chimera check: per-reference tables of a self-alignment are out of scope");
+	s->taxa = tx;
 	return BH_OK;
 }
 const BhQueries *bh_session_sample(const BhSession *s) { return s && s->cur ? &s->cur->Q : NULL; }
@@ -184,6 +194,10 @@ static int sample_fail_ex(BhSession *s, BhSampleResult *res, int rc, const char 
 		if (s->dead) bh_em_abort(s->o.em);
 		else if (s->cov_name && !s->em_col) (void)bh_em_sample_failed(s->o.em, s->cov_name);
 	}
+	if (s->taxa && s->i0 >= 0) {
+		if (s->dead) bh_taxa_abort(s->taxa);
+		else if (s->cov_name && !s->taxa_col) (void)bh_taxa_sample_failed(s->taxa, s->cov_name);
+	}
 	if (s->o.pile && s->i0 >= 0) {
 		if (s->dead) bh_pile_abort(s->o.pile);
 		else if (s->cov_name && !s->pile_col) (void)bh_pile_sample_failed(s->o.pile, s->cov_name);
@@ -207,8 +221,8 @@ int bh_session_load(BhSession *s, const char *queries, const char *out_path, BhS
 	if (s->dead) { res->rc = s->dead; snprintf(res->err, sizeof res->err, "the session was ended by an earlier error (code %d)", s->dead); return bh_set_error(s->dead, "%s", res->err); }
 	if (s->cur) return bh_set_error(BH_E_USAGE, "bh_session_load: the previous sample has not been finished or dropped");
 	s->tLoad = wall();
-	free(s->cov_name); s->cov_name = NULL; s->cov_col = s->em_col = s->pile_col = s->cons_col = 0;
-	if ((s->o.cov || s->o.em || s->o.pile || s->cons || s->vcf) && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
+	free(s->cov_name); s->cov_name = NULL; s->cov_col = s->em_col = s->taxa_col = s->pile_col = s->cons_col = 0;
+	if ((s->o.cov || s->o.em || s->o.pile || s->cons || s->vcf || s->taxa) && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
 	SessIngest *g = NULL;
 	/* the outstanding ingest is this sample's: take it.  If it is another one's (prefetched before this sample was named) it stays
 	 * outstanding and this sample is read here */
@@ -258,6 +272,7 @@ int bh_session_drop(BhSession *s) {
 	 * its name, so that the later samples keep their columns */
 	if (s->o.cov && s->cur && s->cov_name && !s->dead) (void)bh_cov_sample_failed(s->o.cov, s->cov_name);
 	if (s->o.em && s->cur && s->cov_name && !s->dead) (void)bh_em_sample_failed(s->o.em, s->cov_name);
+	if (s->taxa && s->cur && s->cov_name && !s->dead) (void)bh_taxa_sample_failed(s->taxa, s->cov_name);
 	if (s->o.pile && s->cur && s->cov_name && !s->dead) (void)bh_pile_sample_failed(s->o.pile, s->cov_name);
 	if (s->cons && s->cur && s->cov_name && !s->dead) (void)bh_consensus_sample_failed(s->cons, s->cov_name);
 	if (s->vcf && s->cur) bh_vcf_sample_failed(s->vcf);
@@ -374,7 +389,7 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		if (!rc && s->paths) rc = bh_paths_set_consensus(s->paths, s->cons, o->cigar);
 		if (!rc && s->paths) rc = bh_paths_set_vcf(s->paths, s->vcf, o->cigar);
 		s->sink.want_re = s->cluster != NULL;
-		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov || o->em || s->cluster ? &s->sink : NULL, s->paths);
+		if (!rc) rc = bh_report_view_paths(s->out, s->db, Q, &view, o->mode, (o->do_accel ? 0 : BH_REP_MERGED_LIST) | o->rep_flags, o->tax ? o->tax : NULL, &lines, o->cov || o->em || s->cluster || s->taxa ? &s->sink : NULL, s->paths);
 		if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
 		FILE *f = s->out; s->out = NULL;
 		if (fclose(f)) { char msg[512]; snprintf(msg, sizeof msg, "ERROR: write failed: %s", s->out_path); return sample_fail(s, res, BH_E_IO, msg); }      /* (a full disk must not end in success) */
@@ -396,6 +411,13 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
 			if (o->verbose) bh_em_print_info(o->em);
 			PHASE("abundance of the sample");
+		}
+		if (s->taxa) {     /* the sample's column of the taxon tables from the same groups, with the abundance's counts when there are any */
+			rc = bh_taxa_sample(s->taxa, R[s->i0].hh, s->cov_name, s->sink.uq, s->sink.lines, s->sink.n, o->em ? bh_em_last_column(o->em) : NULL);
+			s->taxa_col = 1;
+			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail_ex(s, res, rc, msg, 1); }
+			if (o->verbose) bh_taxa_print_info(s->taxa);
+			PHASE("taxa of the sample");
 		}
 		if (o->pile) {     /* the sample's variant sites: one call over the lines the tracer handed over, on rank 0's device as well */
 			rc = bh_pile_sample(o->pile, R[s->i0].hh, s->cov_name, Q->codes, Q->qoff, Q->numEntries);
@@ -475,6 +497,7 @@ int bh_session_run_mates(BhSession *s, const char *queries1, const char *queries
 	if (!s->o.do_rc) return mates_fail(s, res, BH_E_USAGE, "ERROR: mates need both strands searched (-fr)");
 	if (s->o.cov || s->o.cigar) return mates_fail(s, res, BH_E_USAGE, "ERROR: coverage and alignment paths of paired output are out of scope: mates go with neither");
 	if (s->o.em) return mates_fail(s, res, BH_E_USAGE, "ERROR: the abundance of paired output is out of scope: mates do not go with it");
+	if (s->taxa) return mates_fail(s, res, BH_E_USAGE, "ERROR: the taxon tables of paired output are out of scope: mates do not go with them");
 	if (s->o.pile) return mates_fail(s, res, BH_E_USAGE, "ERROR: variants of paired output are out of scope: mates do not go with them");
 	if (s->cons) return mates_fail(s, res, BH_E_USAGE, "ERROR: the consensus of paired output is out of scope: mates do not go with it");
 	if (s->vcf) return mates_fail(s, res, BH_E_USAGE, "ERROR: the VCF output of paired output is out of scope: mates do not go with it");

@@ -419,6 +419,59 @@ void bh_em_last_info(const BhEm *em, uint64_t info[8], uint64_t *reads);
 void bh_em_close(BhEm *em);
 int  bh_em_host(void *unused, uint32_t n_headers, uint32_t n_groups, const uint32_t *group_w, const BhipEmLine *lines, uint64_t n_lines, uint32_t max_iters,
                 uint64_t tol, uint64_t *counts, uint64_t info[8]);
+const uint64_t *bh_em_last_column(const BhEm *em);      /* the counts [n_headers] of the last sample, NULL when it failed or none came (bh_taxa.c rolls them up) */
+
+/* ---- taxon tables per sample: a read goes to the lowest common ancestor of its references' taxonomies (bh_taxa.c; burst_hip --taxa) ----
+ * The definition is bhip_taxa_run's (include/burst_hip.h).  The taxonomy of a header is what bh_tax_lookup returns for it (the
+ * string of column 13; ncbi as -bn), without trailing ';'; empty or exactly `Unassigned` is no taxonomy.  It splits at every ';' into levels,
+ * bytes kept as they are (a leading blank stays, an empty inner level is a level); more than 64 levels is BH_E_USAGE that names the header.
+ * The distinct level prefixes are the nodes, node 0 the root (depth 0, printed `Unassigned`), a node's name the string up to the end of its
+ * last level; numbered in preorder (a subtree is a range of numbers), siblings in byte order with ';' below every other byte -- an order no
+ * result depends on.  A header without taxonomy is at the root.  Groups, weights and candidates are the abundance's (bh_em.c).
+ * Files, written under temporary names and renamed together, rows in strcmp order of the name, `#OTU ID<TAB>Dataset[<TAB>sample...]`,
+ * Dataset = the integer sum of the sample columns, a failed sample an all-zero column:
+ *   PREFIXtaxa.txt                  own counts, the nodes with a Dataset value other than zero (the root as `Unassigned`), integers
+ *   PREFIXtaxa_L<k>.txt             k = 1 .. D, D the deepest level with a clade count: the nodes of depth k, clade counts, integers
+ *   PREFIXtaxa_abundance_L<k>.txt   with an abundance beside it: the same rows, k = 1 .. D, from clade_em, %.4f of count / 2^30
+ *   bh_taxa_tree          nodes, names, parents, depths and header -> node from headers and the map; bh_taxa_tree_free
+ *   bh_taxa_open          the headers are the database's unique-header numbers (RefMap), as the abundance's; bh_taxa_open_heads: any headers
+ *   bh_taxa_sample        the next sample (column), reduced on `hip_handle`; em_counts: NULL, or the sample's abundance counts per header
+ *   bh_taxa_sample_failed the next column stays all zero; named on standard output
+ *   bh_taxa_abort         the run ends on an error: nothing will be written
+ *   bh_taxa_stats         [4][columns][nodes]: own, clade, own_em, clade_em; column 0 = Dataset
+ *   bh_taxa_write         the files; n_levels / n_em_levels: how many level files of either kind
+ *   bh_taxa_print_info    the `Taxa:` line of the last sample; bh_taxa_last_info: the same figures (bhip_taxa_run's info)
+ *   bh_taxa_set_solver    other solvers (tests) for bhip_taxa_run and bhip_taxa_rollup, return codes in this file's terms; NULL: the device
+ *   bh_taxa_host, bh_taxa_rollup_host   the definition in plain C (candidates counted below every ancestor), solvers whose first argument is ignored
+ *   bh_taxa_check_opts    BH_E_USAGE with the command line's text: no map, or an agreement outside 501 .. 1000
+ * Any error of a solver is final: later calls return it and nothing is written. */
+typedef struct BhTaxa BhTaxa;
+typedef struct BhTaxaTree { uint32_t n_nodes, n_headers; uint32_t *parent, *depth, *header_node; char **name; } BhTaxaTree;
+typedef int (*bh_taxa_run_fn)(void *ctx, uint32_t n_nodes, const uint32_t *parent, uint32_t n_headers, const uint32_t *header_node, uint32_t n_groups,
+                              const uint32_t *group_w, const BhipEmLine *lines, uint64_t n_lines, uint32_t agree, uint32_t *group_node, uint64_t *own, uint64_t *clade,
+                              uint64_t info[8]);
+typedef int (*bh_taxa_rollup_fn)(void *ctx, uint32_t n_nodes, const uint32_t *parent, uint32_t n_headers, const uint32_t *header_node, const uint64_t *header_count,
+                                 uint64_t *own, uint64_t *clade);
+int  bh_taxa_tree(uint32_t n_headers, const char *const *heads, const BhTax *map, int ncbi, BhTaxaTree *tree);
+void bh_taxa_tree_free(BhTaxaTree *tree);
+int  bh_taxa_check_opts(const char *tax_file, int agree_given, long long agree);
+int  bh_taxa_open(const BhDb *db, const char *prefix, const BhTax *map, int ncbi, uint32_t agree, BhTaxa **tx);
+int  bh_taxa_open_heads(const char *prefix, uint32_t n_headers, const char *const *heads, const BhTax *map, int ncbi, uint32_t agree, BhTaxa **tx);
+void bh_taxa_set_solver(BhTaxa *tx, bh_taxa_run_fn run, bh_taxa_rollup_fn rollup, void *ctx);
+int  bh_taxa_sample(BhTaxa *tx, void *hip_handle, const char *out_path, const uint32_t *reads, const BhipCovLine *lines, uint64_t n, const uint64_t *em_counts);
+int  bh_taxa_sample_failed(BhTaxa *tx, const char *out_path);
+void bh_taxa_abort(BhTaxa *tx);
+const BhTaxaTree *bh_taxa_tree_of(const BhTaxa *tx);
+void bh_taxa_dims(const BhTaxa *tx, uint32_t *n_columns, uint32_t *n_nodes);
+int  bh_taxa_stats(BhTaxa *tx, uint64_t *columns);
+int  bh_taxa_write(BhTaxa *tx, uint32_t *n_levels, uint32_t *n_em_levels);
+void bh_taxa_print_info(BhTaxa *tx);
+void bh_taxa_last_info(const BhTaxa *tx, uint64_t info[8]);
+void bh_taxa_close(BhTaxa *tx);
+int  bh_taxa_host(void *unused, uint32_t n_nodes, const uint32_t *parent, uint32_t n_headers, const uint32_t *header_node, uint32_t n_groups, const uint32_t *group_w,
+                  const BhipEmLine *lines, uint64_t n_lines, uint32_t agree, uint32_t *group_node, uint64_t *own, uint64_t *clade, uint64_t info[8]);
+int  bh_taxa_rollup_host(void *unused, uint32_t n_nodes, const uint32_t *parent, uint32_t n_headers, const uint32_t *header_node, const uint64_t *header_count,
+                         uint64_t *own, uint64_t *clade);
 
 /* ---- variant sites per sample from the alignment paths (bh_pile.c; burst_hip --variants) ----
  * The definition is bhip_pile_run's (include/burst_hip.h): per sample, every printed line is a line of the pile-up -- its record's path
@@ -756,6 +809,10 @@ int  bh_session_set_chimera(BhSession *s, BhChimera *ch);
  * output OUT.  It opens the path tracer (without the --cigar columns unless the session has them) and goes with variants and the chimera
  * check.  Not with database shards, not with bh_session_run_mates */
 int  bh_session_set_sam(BhSession *s, BhSam *sam);
+/* likewise NULL, or the taxon tables every reported sample feeds (rank 0's process; the caller opens it, writes the tables and closes it):
+ * the report's sink is filled for it alone, and a session with an abundance hands each sample's counts over for the roll-up.  Not with
+ * clusters or the chimera check, not with bh_session_run_mates */
+int  bh_session_set_taxa(BhSession *s, BhTaxa *tx);
 /* likewise NULL, or the consensus every reported sample feeds (rank 0's process; the caller opens it, writes the files and closes it): it
  * opens the path tracer (without the --cigar columns unless the session has them) and goes with coverage, abundance, variants and the SAM
  * writer.  Not with database shards, clusters, the chimera check or bh_session_run_mates */

@@ -8,6 +8,7 @@
  *             [--mates-orientation fr|rf|ff] [--mates-report all|best]      paired-end reads: the concordant combinations of the two mates' placements (bh_mates.c)
  *   ... -q / -o or --samples ... --coverage PREFIX [--coverage-lengths FILE] [--coverage-pad N]      coverage and count tables per reference and sample (bh_cov.c)
  *   ... -q / -o or --samples ... --abundance PREFIX [--abundance-iters N] [--abundance-tol UNITS]   multi-mapped reads split over their references by EM (bh_em.c)
+ *   ... -q / -o or --samples ... -b MAP --taxa PREFIX [--taxa-agree PERMILLE]   taxon tables: a read to the lowest common ancestor of its references (bh_taxa.c)
  *   burst_hip -r reads.fa|reads.edx [-a|-ad ...] -q reads.fa -o self.b6 -m FORAGE -i ... [-fr] --cluster PREFIX [--cluster-sizes]      greedy centroid clusters of the reads from their self-hits (bh_cluster.c)
  *   burst_hip -r reads.fa|reads.edx [-a|-ad ...] -q reads.fa -o self.b6 -m FORAGE -i ... [-fr] --chimeras PREFIX [--chimera-sizes] [--chimera-skew S]
  *             [--chimera-min-seg G] [--chimera-min-gain D]      de-novo two-parent chimera check of the reads from their self-hits and the hits' paths (bh_chimera.c)
@@ -120,6 +121,12 @@ static int open_devices(const BhDb *db, int n_gpus, const int *dev_list, int sha
 	return 0;
 }
 
+static void print_taxa_written(const char *prefix, uint32_t n_levels, uint32_t n_em_levels) {
+	printf("Taxon tables written: %staxa.txt, %staxa_L<k>.txt for k = 1 .. %u", prefix, prefix, n_levels);
+	if (n_em_levels) printf(", %staxa_abundance_L<k>.txt likewise", prefix);
+	putchar('\n');
+}
+
 /* ---- --samples LIST: a list of query files against one resident database, each to its own .b6 (bh_session.c) ---- */
 typedef struct {
 	const char *ref_FN, *xcel_FN, *tax_FN, *list_FN;
@@ -133,6 +140,7 @@ typedef struct {
 	int sam, sam_unmapped; const char *sam_lengths;
 	const char *cons_prefix; uint32_t cons_min_depth, cons_min_breadth; int cons_unique; const char *cons_lengths;
 	int vcf; uint32_t vcf_min_depth, vcf_min_alt; int vcf_unique; const char *vcf_lengths;
+	const char *taxa_prefix; uint32_t taxa_agree;
 } SamplesArgs;
 typedef struct { char *q, *o, *m; int line; } Sample;      /* m: the mates file of a three-field line, or NULL */
 
@@ -209,6 +217,7 @@ static int samples_main(SamplesArgs *a) {
 	if (any_mates && !a->do_rc) { puts("ERROR: a --samples line with a mates file needs both strands searched: add -fr"); return 1; }
 	if (any_mates && (a->cigar || a->cov_prefix)) { puts("ERROR: --cigar and --coverage of paired output are out of scope: neither goes with mates"); return 1; }
 	if (any_mates && a->em_prefix) { puts("ERROR: --abundance of paired output is out of scope: it does not go with mates"); return 1; }
+	if (any_mates && a->taxa_prefix) { puts("ERROR: --taxa of paired output is out of scope: it does not go with mates"); return 1; }
 	if (any_mates && a->var_prefix) { puts("ERROR: --variants of paired output are out of scope: they do not go with mates"); return 1; }
 	if (any_mates && a->cons_prefix) { puts("ERROR: --consensus of paired output is out of scope: it does not go with mates"); return 1; }
 	if (any_mates && a->vcf) { puts("ERROR: --vcf of paired output is out of scope: it does not go with mates"); return 1; }
@@ -274,6 +283,10 @@ static int samples_main(SamplesArgs *a) {
 		if ((rc = bh_em_open(&db, a->em_prefix, a->em_iters, a->em_tol, &em))) DIES(rc);
 		bh_session_set_abundance(ses, em);
 	}
+	BhTaxa *taxa = NULL;
+	if (a->taxa_prefix) {      /* (the tree of the map's strings is built, and a string of too many levels refused, before a device is touched) */
+		if ((rc = bh_taxa_open(&db, a->taxa_prefix, &taxonomy, a->txo->ncbi, a->taxa_agree, &taxa)) || (rc = bh_session_set_taxa(ses, taxa))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); bh_session_close(ses); return 1; } DIES(rc); }
+	}
 	BhSam *sam = NULL;
 	if (a->sam) {      /* (the names and the lengths table are checked against the database's headers before a device is touched) */
 		if ((rc = bh_sam_open(&db, a->sam_lengths, a->sam_unmapped, &sam)) || (rc = bh_session_set_sam(ses, sam))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); bh_session_close(ses); return 1; } DIES(rc); }
@@ -323,6 +336,12 @@ static int samples_main(SamplesArgs *a) {
 		if ((rc = bh_em_write(em))) { fprintf(stderr, "%s\n", bh_last_error()); if (!first_fail) first_fail = code_to_exit(rc); }
 		else { printf("Abundance table written: %sabundance.txt\n", a->em_prefix); PHASE("abundance table"); }
 	} else if (em) puts("No abundance table is written: the run ended on an error");
+	if (taxa && !bh_session_ended(ses)) {
+		uint32_t nl = 0, nel = 0;
+		tp = wall();
+		if ((rc = bh_taxa_write(taxa, &nl, &nel))) { fprintf(stderr, "%s\n", bh_last_error()); if (!first_fail) first_fail = code_to_exit(rc); }
+		else { print_taxa_written(a->taxa_prefix, nl, nel); PHASE("taxon tables"); }
+	} else if (taxa) puts("No taxon tables are written: the run ended on an error");
 	if (pile && !bh_session_ended(ses)) {
 		if ((rc = bh_pile_write(pile))) { fprintf(stderr, "%s\n", bh_last_error()); if (!first_fail) first_fail = code_to_exit(rc); }
 		else printf("Variants table written: %svariants.txt\n", a->var_prefix);
@@ -341,7 +360,7 @@ static int samples_main(SamplesArgs *a) {
 	#undef DIES
 	if (!getenv("BURST_HOST_TEARDOWN")) _exit(first_fail);      /* (as the single-sample path: the operating system releases a finished process's memory faster) */
 	bh_session_close(ses);
-	bh_cov_close(cov); bh_em_close(em);
+	bh_cov_close(cov); bh_em_close(em); bh_taxa_close(taxa);
 	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); bh_run_free(&ranks[r].run); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
 	bh_db_free(&db); bh_tax_free(&taxonomy);
 	for (int i = 0; i < nS; ++i) { free(S[i].q); free(S[i].o); free(S[i].m); }
@@ -427,6 +446,9 @@ static void usage(void) {
 	puts("                  count of matches, then the reference base under every X, ^ and the reference bases under every D, the count again, also");
 	puts("                  when it is 0 (3=2D1X4= gives 3^AC0T4; I adds nothing).  --sam-unmapped: behind them one FLAG 4 record per read without a");
 	puts("                  line, in query-file order.  Refuses what --cigar refuses, and --mates");
+	puts("--taxa <prefix> [--taxa-agree <permille>]: with -q / -o or --samples and -b <map>, leave taxon tables per sample: every read goes to the lowest");
+	puts("                  common ancestor of the taxonomies of the references it was placed on (at least <permille> of them, 501 .. 1000, default 1000:");
+	puts("                  all of them): <prefix>taxa.txt, <prefix>taxa_L<k>.txt per level, with --abundance also <prefix>taxa_abundance_L<k>.txt");
 	puts("--host-acx: build accelerators (-d ... -a, --make-acx) with the host builder instead of the device");
 }
 
@@ -442,6 +464,7 @@ int main(int argc, char **argv) {
 	uint64_t batch = 1u << 21;      /* unique queries per device batch: the fixed cost of a batch (launches, synchronisation) is about 1 ms of device time */
 	const char *ref_FN = 0, *query_FN = 0, *output_FN = 0, *xcel_FN = 0, *mkacx_FN = 0, *tax_FN = 0, *samples_FN = 0, *cov_prefix = 0, *cov_lengths = 0;
 	uint32_t cov_pad = 0;
+	const char *taxa_prefix = 0; long long taxa_agree = 1000; int taxa_agree_given = 0;
 	const char *em_prefix = 0; uint32_t em_iters = 1000; uint64_t em_tol = 1024; int em_opts_given = 0;
 	const char *var_prefix = 0; uint32_t var_min_depth = 4, var_min_alt = 2; int var_unique = 0, var_opts_given = 0;
 	const char *mates_FN = 0; BhMatesOpts mopts = {BHIP_MATES_FR, 0, 1000, BHIP_MATES_ALL}; int mates_opts_given = 0;
@@ -501,6 +524,13 @@ int main(int argc, char **argv) {
 		else if (!strcmp(a, "--samples")) { NEEDARG("--samples"); samples_FN = argv[i]; }
 		else if (!strcmp(a, "--make-acx")) { NEEDARG("--make-acx"); mkacx_FN = argv[i]; }
 		else if (!strcmp(a, "--coverage")) { NEEDARG("--coverage"); cov_prefix = argv[i]; }
+		else if (!strcmp(a, "--taxa")) { NEEDARG("--taxa"); taxa_prefix = argv[i]; }
+		else if (!strcmp(a, "--taxa-agree")) {
+			NEEDARG("--taxa-agree");
+			char *end = NULL; taxa_agree = strtoll(argv[i], &end, 10);
+			if (!*argv[i] || *end) taxa_agree = -1;
+			taxa_agree_given = 1;
+		}
 		else if (!strcmp(a, "--abundance")) { NEEDARG("--abundance"); em_prefix = argv[i]; }
 		else if (!strcmp(a, "--abundance-iters") || !strcmp(a, "--abundance-tol")) {
 			const int is_tol = !strcmp(a, "--abundance-tol");
@@ -651,6 +681,12 @@ int main(int argc, char **argv) {
 	if (n_dev_list && n_dev_list != n_gpus) { puts("ERROR: --devices must name one device per --gpus rank"); return 1; }
 	if ((cov_lengths || cov_pad) && !cov_prefix) { puts("ERROR: --coverage-lengths and --coverage-pad go with --coverage <prefix>"); return 1; }
 	if (cov_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --coverage works from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (taxa_agree_given && !taxa_prefix) { puts("ERROR: --taxa-agree goes with --taxa <prefix>"); return 1; }
+	if (taxa_prefix && bh_taxa_check_opts(tax_FN, taxa_agree_given, taxa_agree)) { puts(bh_last_error()); return 1; }
+	if (taxa_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --taxa works from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
+	if (taxa_prefix && shard_db && n_gpus == 1 && n_shards > 1) { puts("ERROR: --taxa needs a resident device handle: it does not go with the serial-shards path (--gpus 1 --shards S)"); return 1; }
+	if (taxa_prefix && mates_FN) { puts("ERROR: --taxa of paired output is out of scope: it does not go with --mates"); return 1; }
+	if (taxa_prefix && !samples_FN && !(ref_FN && query_FN && output_FN)) { puts("ERROR: --taxa goes with an alignment run: -r, -q and -o, or --samples"); return 1; }
 	if (em_opts_given && !em_prefix) { puts("ERROR: --abundance-iters and --abundance-tol go with --abundance <prefix>"); return 1; }
 	if (em_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --abundance works from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
 	if (em_prefix && shard_db && n_gpus == 1 && n_shards > 1) { puts("ERROR: --abundance needs a resident device handle: it does not go with the serial-shards path (--gpus 1 --shards S)"); return 1; }
@@ -696,6 +732,7 @@ int main(int argc, char **argv) {
 	if (clu_prefix && mates_FN) { puts("ERROR: --cluster takes one query file aligned against itself: it does not go with --mates"); return 1; }
 	if (clu_prefix && (shard_db || n_shards)) { puts("ERROR: --cluster needs the whole report on rank 0: it does not go with --shard db or --shards"); return 1; }
 	if (clu_prefix && !gather_host) { puts("ERROR: --cluster takes the host gather only (drop --gather rccl)"); return 1; }
+	if (clu_prefix && taxa_prefix) { puts("ERROR: --cluster does not go with --taxa: per-reference tables of a self-alignment are out of scope"); return 1; }
 	if (clu_prefix && (cov_prefix || em_prefix || var_prefix)) { puts("ERROR: --cluster does not go with --coverage, --abundance or --variants: per-reference tables of a self-alignment are out of scope"); return 1; }
 	/* (--chimeras works from the same lines as --cluster, and from their paths: the same refusals, before a device is touched) */
 	if (chi_opts_given && !chi_prefix) { puts("ERROR: --chimera-sizes, --chimera-skew, --chimera-min-seg and --chimera-min-gain go with --chimeras <prefix>"); return 1; }
@@ -705,6 +742,7 @@ int main(int argc, char **argv) {
 	if (chi_prefix && mates_FN) { puts("ERROR: --chimeras takes one query file aligned against itself: it does not go with --mates"); return 1; }
 	if (chi_prefix && (shard_db || n_shards)) { puts("ERROR: --chimeras needs the whole report on rank 0: it does not go with --shard db or --shards"); return 1; }
 	if (chi_prefix && !gather_host) { puts("ERROR: --chimeras takes the host gather only (drop --gather rccl)"); return 1; }
+	if (chi_prefix && taxa_prefix) { puts("ERROR: --chimeras does not go with --taxa: per-reference tables of a self-alignment are out of scope"); return 1; }
 	if (chi_prefix && (cov_prefix || em_prefix || var_prefix)) { puts("ERROR: --chimeras does not go with --coverage, --abundance or --variants: per-reference tables of a self-alignment are out of scope"); return 1; }
 	if (mates_opts_given && mopts.ins_min > mopts.ins_max) { puts("ERROR: --insert-min is larger than --insert-max"); return 1; }
 	if (mates_opts_given && !mates_FN && !samples_FN) { puts("ERROR: --insert-min, --insert-max, --mates-orientation and --mates-report go with --mates"); return 1; }
@@ -732,7 +770,7 @@ int main(int argc, char **argv) {
 		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given, em_prefix, em_iters, em_tol,
 		                  var_prefix, var_min_depth, var_min_alt, var_unique, sam, sam_unmapped, sam_lengths,
 		                  cons_prefix, cons_min_depth, cons_min_breadth, cons_unique, cons_lengths,
-		                  vcf, vcf_min_depth, vcf_min_alt, vcf_unique, vcf_lengths};
+		                  vcf, vcf_min_depth, vcf_min_alt, vcf_unique, vcf_lengths, taxa_prefix, (uint32_t)taxa_agree};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
@@ -866,6 +904,8 @@ int main(int argc, char **argv) {
 	if (cov_prefix && (rc = bh_cov_open(&db, cov_prefix, cov_lengths, cov_pad, &cov))) DIEJ(rc);      /* (before a device is touched) */
 	BhEm *em = NULL;
 	if (em_prefix && (rc = bh_em_open(&db, em_prefix, em_iters, em_tol, &em))) DIEJ(rc);
+	BhTaxa *taxa = NULL;      /* (the tree of the map's strings: a string of too many levels is refused before a device is touched) */
+	if (taxa_prefix && (rc = bh_taxa_open(&db, taxa_prefix, &taxonomy, txo.ncbi, (uint32_t)taxa_agree, &taxa))) { JOIN_INGEST(); if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
 	if (cons_prefix) { const int e = open_consensus(&db, cons_prefix, cons_lengths, cons_min_depth, cons_min_breadth, cons_unique); if (e) { JOIN_INGEST(); return e; } }
 	if (vcf) { const int e = open_vcf(&db, vcf_lengths, vcf_min_depth, vcf_min_alt, vcf_unique); if (e) { JOIN_INGEST(); return e; } }
 	if (sam) {      /* (before a device is touched: two headers of one name, a lengths table without a header) */
@@ -1020,7 +1060,7 @@ int main(int argc, char **argv) {
 	}
 	if (g_cons && (rc = bh_paths_set_consensus(paths, g_cons, cigar))) DIEP(rc);
 	if (g_vcf && (rc = bh_paths_set_vcf(paths, g_vcf, cigar))) DIEP(rc);
-	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em || clu ? &sink : NULL, paths))) DIEP(rc);
+	if ((rc = bh_report_view_paths(output, &db, &Q, &view, mode, (do_accel ? 0 : BH_REP_MERGED_LIST) | rep_flags, tax_FN ? &txo : NULL, &lines, cov || em || clu || taxa ? &sink : NULL, paths))) DIEP(rc);
 	if (fclose(output)) { fprintf(stderr, "ERROR: write failed: %s\n", output_FN); return 2; }      /* (the last buffer of the report: a full disk must not end in exit code 0) */
 	printf("Wrote %lu alignments\n", (unsigned long)lines);
 	if (paths && cigar) bh_paths_print_info(paths, hhs[0]);
@@ -1058,6 +1098,13 @@ int main(int argc, char **argv) {
 		printf("Abundance table written: %sabundance.txt\n", em_prefix);
 		PHASE("abundance");
 	}
+	if (taxa) {     /* likewise, from the same groups; the abundance's counts rolled up beside them */
+		uint32_t nl = 0, nel = 0;
+		if ((rc = bh_taxa_sample(taxa, hhs[0], output_FN, sink.uq, sink.lines, sink.n, em ? bh_em_last_column(em) : NULL)) || (rc = bh_taxa_write(taxa, &nl, &nel))) DIE(rc);
+		bh_taxa_print_info(taxa);
+		print_taxa_written(taxa_prefix, nl, nel);
+		PHASE("taxa");
+	}
 	if (clu) {      /* the reads clustered from the lines just printed (rank 0's handle); a usage error -- two reads of one name -- writes no table */
 		if ((rc = bh_cluster_sample(clu, hhs[0], &db, &Q, &sink)) || (rc = bh_cluster_write(clu))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
 		bh_cluster_print_info(clu);
@@ -1083,7 +1130,7 @@ int main(int argc, char **argv) {
 	 * second for a 32 M-read job; the operating system releases a finished process's memory (host and device) far faster.
 	 * BURST_HOST_TEARDOWN=1 walks through the orderly release instead (leak checks). */
 	if (!getenv("BURST_HOST_TEARDOWN")) _exit(0);
-	bh_cov_close(cov); bh_em_close(em); bh_cluster_close(clu); bh_chimera_close(chi); free(sink.lines); free(sink.uq); free(sink.re); bh_paths_close(paths);
+	bh_cov_close(cov); bh_em_close(em); bh_taxa_close(taxa); bh_cluster_close(clu); bh_chimera_close(chi); free(sink.lines); free(sink.uq); free(sink.re); bh_paths_close(paths);
 	if (comm) bhip_comm_destroy(comm);
 	for (int r = 0; r < n_gpus; ++r) { bhip_destroy(hhs[r]); if (slices[r].numRclumps) bh_db_free(&slices[r]); }
 	for (int r = 0; r < n_gpus; ++r) bh_run_free(&ranks[r].run);

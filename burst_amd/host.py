@@ -79,6 +79,10 @@ class BhTax(C.Structure):
     _fields_ = [("n", C.c_uint64), ("pair", C.c_void_p), ("blob", C.c_void_p)]
 
 
+class BhTaxaTree(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("n_headers", C.c_uint32), ("parent", u32p), ("depth", u32p), ("header_node", u32p), ("name", C.POINTER(C.c_char_p))]
+
+
 class BhTaxOpts(C.Structure):
     _fields_ = [("tax", C.POINTER(BhTax)), ("suppress", C.c_int), ("strict", C.c_int), ("taxacut", C.c_uint32), ("ncbi", C.c_int)]
 
@@ -116,6 +120,11 @@ E_CAPACITY = -6
 COV_TAP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64)
 # a solver in place of bhip_em_run (bh_em_set_solver): ctx, n_headers, n_groups, group_w, lines, n_lines, max_iters, tol, counts, info
 EM_SOLVER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p)
+# solvers in place of bhip_taxa_run and bhip_taxa_rollup (bh_taxa_set_solver): ctx, n_nodes, parent, n_headers, header_node, then n_groups, group_w,
+# lines, n_lines, agree, group_node, own, clade, info -- or header_count, own, clade
+TAXA_RUN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                          C.c_void_p, C.c_void_p)
+TAXA_ROLLUP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
 
 # a solver in place of bhip_cluster_run (bh_cluster_set_solver): ctx, n_nodes, weights, edges, n_edges, centroid, edits, info
@@ -260,6 +269,36 @@ def lib():
         L.bh_em_last_info.restype = None
         L.bh_em_close.argtypes = [C.c_void_p]
         L.bh_em_close.restype = None
+        L.bh_em_last_column.argtypes = [C.c_void_p]
+        L.bh_em_last_column.restype = C.c_void_p
+        L.bh_taxa_tree.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(BhTax), C.c_int, C.POINTER(BhTaxaTree)]
+        L.bh_taxa_tree_free.argtypes = [C.POINTER(BhTaxaTree)]
+        L.bh_taxa_tree_free.restype = None
+        L.bh_taxa_check_opts.argtypes = [C.c_char_p, C.c_int, C.c_longlong]
+        L.bh_taxa_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.POINTER(BhTax), C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.bh_taxa_open_heads.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(BhTax), C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.bh_taxa_set_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_taxa_set_solver.restype = None
+        L.bh_taxa_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.bh_taxa_sample_failed.argtypes = [C.c_void_p, C.c_char_p]
+        L.bh_taxa_abort.argtypes = [C.c_void_p]
+        L.bh_taxa_abort.restype = None
+        L.bh_taxa_tree_of.argtypes = [C.c_void_p]
+        L.bh_taxa_tree_of.restype = C.POINTER(BhTaxaTree)
+        L.bh_taxa_dims.argtypes = [C.c_void_p, u32p, u32p]
+        L.bh_taxa_dims.restype = None
+        L.bh_taxa_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_taxa_write.argtypes = [C.c_void_p, u32p, u32p]
+        L.bh_taxa_print_info.argtypes = [C.c_void_p]
+        L.bh_taxa_print_info.restype = None
+        L.bh_taxa_last_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_taxa_last_info.restype = None
+        L.bh_taxa_close.argtypes = [C.c_void_p]
+        L.bh_taxa_close.restype = None
+        L.bh_taxa_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]
+        L.bh_taxa_rollup_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_session_set_taxa.argtypes = [C.c_void_p, C.c_void_p]
         L.bh_em_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
         L.bh_pile_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.bh_pile_open_heads.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
@@ -380,6 +419,53 @@ def lib():
         L.bh_session_set_sam.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
+
+
+def _taxa_tree_arrays(t):
+    """names (bytes), parent, depth, header_node of a BhTaxaTree, copied"""
+    n, nh = t.n_nodes, t.n_headers
+    return ([t.name[v] for v in range(n)], np.ctypeslib.as_array(t.parent, (n,)).copy(), np.ctypeslib.as_array(t.depth, (n,)).copy(),
+            np.ctypeslib.as_array(t.header_node, (nh,)).copy() if nh else np.zeros(0, np.uint32))
+
+
+def taxa_tree(headers, taxonomy, ncbi=False):
+    """bh_taxa_tree: the tree of the taxonomy map's strings for these headers (str or bytes); taxonomy: the map file of -b.  Returns (names
+    as bytes, node 0 = b"Unassigned"; parent, depth uint32 [nodes]; header_node uint32 [headers]), nodes in preorder"""
+    tax, tree = BhTax(), BhTaxaTree()
+    _chk(lib().bh_tax_load(taxonomy.encode(), C.byref(tax)))
+    try:
+        hs = [h.encode() if isinstance(h, str) else bytes(h) for h in headers]
+        arr = (C.c_char_p * max(len(hs), 1))(*hs)
+        _chk(lib().bh_taxa_tree(len(hs), arr, C.byref(tax), int(bool(ncbi)), C.byref(tree)))
+        try:
+            return _taxa_tree_arrays(tree)
+        finally:
+            lib().bh_taxa_tree_free(C.byref(tree))
+    finally:
+        lib().bh_tax_free(C.byref(tax))
+
+
+def taxa_host(parent, header_node, group_w, lines, agree=1000):
+    """bh_taxa_host, the taxon definition in plain C (no device; candidates counted below every ancestor): (group_node uint32 [groups],
+    0xFFFFFFFF = no lines; own, clade uint64 [nodes]; info uint64 [8]); lines: capi.EM_LINE_DTYPE or rows (group, ref)"""
+    parent, header_node = np.ascontiguousarray(parent, dtype=np.uint32), np.ascontiguousarray(header_node, dtype=np.uint32)
+    group_w = np.ascontiguousarray(group_w, dtype=np.uint32)
+    lines = capi.em_lines(lines)
+    nn = len(parent)
+    gn, own, clade, info = np.zeros(max(len(group_w), 1), np.uint32), np.zeros(max(nn, 1), np.uint64), np.zeros(max(nn, 1), np.uint64), np.zeros(8, np.uint64)
+    _chk(lib().bh_taxa_host(None, nn, parent.ctypes.data, len(header_node), header_node.ctypes.data, len(group_w), group_w.ctypes.data, lines.ctypes.data, len(lines), int(agree),
+                            gn.ctypes.data, own.ctypes.data, clade.ctypes.data, info.ctypes.data))
+    return gn[:len(group_w)], own[:nn], clade[:nn], info
+
+
+def taxa_rollup_host(parent, header_node, header_count):
+    """bh_taxa_rollup_host: counts per header summed per node and per subtree, (own, clade) uint64 [nodes]"""
+    parent, header_node = np.ascontiguousarray(parent, dtype=np.uint32), np.ascontiguousarray(header_node, dtype=np.uint32)
+    header_count = np.ascontiguousarray(header_count, dtype=np.uint64)
+    nn = len(parent)
+    own, clade = np.zeros(max(nn, 1), np.uint64), np.zeros(max(nn, 1), np.uint64)
+    _chk(lib().bh_taxa_rollup_host(None, nn, parent.ctypes.data, len(header_node), header_node.ctypes.data, header_count.ctypes.data, own.ctypes.data, clade.ctypes.data))
+    return own[:nn], clade[:nn]
 
 
 def em_host(n_headers, group_w, lines, max_iters=1000, tol=1024):
@@ -1006,7 +1092,8 @@ class Session:
                  chimeras=None, chimera_sizes=False, chimera_skew=2, chimera_min_seg=16, chimera_min_gain=3, chimera_host=False,
                  sam=False, sam_unmapped=False, sam_lengths=None, sam_md=None,
                  consensus=None, consensus_min_depth=4, consensus_min_breadth=0, consensus_reads="all", consensus_lengths=None, consensus_host=False,
-                 vcf=False, vcf_min_depth=4, vcf_min_alt=2, vcf_reads="all", vcf_lengths=None, vcf_host=False):
+                 vcf=False, vcf_min_depth=4, vcf_min_alt=2, vcf_reads="all", vcf_lengths=None, vcf_host=False,
+                 taxa=None, taxa_agree=1000, taxa_host=False):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
         reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
         process only).
@@ -1048,11 +1135,17 @@ class Session:
         vcf_min_alt reads, at positions of vcf_min_depth reads; vcf_reads "unique": only reads printed on one line; vcf_lengths: a
         `name<TAB>length` table for the contig lines, default the database's own extents), from ONE bhip_pile_run and ONE bhip_alleles_run
         per sample on rank 0's device handle -- or bh_pile_host and bh_alleles_host with vcf_host=True.  Same limits as variants; goes with
-        them, the consensus, coverage, abundance, cigar and sam.  vcf_info() has the last sample's figures."""
+        them, the consensus, coverage, abundance, cigar and sam.  vcf_info() has the last sample's figures.
+        taxa = prefix (needs taxonomy=): every reported sample gets a column of the taxon tables (bh_taxa.c: every read goes to the deepest
+        taxonomy node that holds at least taxa_agree permille, 501 .. 1000, of the references it was placed on -- 1000: their lowest common
+        ancestor), reduced on rank 0's device handle -- or by bh_taxa_host with taxa_host=True; with abundance= its counts are rolled up the
+        tree as well.  close() writes prefix + "taxa.txt", "taxa_L<k>.txt" and "taxa_abundance_L<k>.txt" unless the session ended on an
+        error; taxa() returns names, depths and the integer columns.  Not with mates, cluster or chimeras."""
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
         self._mates_join = mates_join
         self.cov, self.em, self.pile, self.cluster, self.chimera = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         self.sam = C.c_void_p()
+        self.taxa_obj = C.c_void_p()
         devs = list(devs) if isinstance(devs, (list, tuple)) else [devs]
         n_local = len(devs)
         world = world or n_local
@@ -1109,6 +1202,16 @@ class Session:
             if abundance_host:
                 lib().bh_em_set_solver(self.em, C.cast(lib().bh_em_host, C.c_void_p), None)
             o.em = self.em
+        if taxa is not None and (rank == 0 or len(devs) > 1):
+            if not taxonomy:
+                raise ValueError("taxa: needs the taxonomy map (taxonomy=)")
+            if not 501 <= int(taxa_agree) <= 1000:
+                raise ValueError("taxa: taxa_agree is the permille of a read's references that must agree, 501 .. 1000")
+            if cluster is not None or chimeras is not None:
+                raise ValueError("taxa: per-reference tables of a self-alignment are out of scope (no cluster, no chimeras)")
+            _chk(lib().bh_taxa_open(C.byref(db.c), taxa.encode(), C.byref(self.tax), int(tax_ncbi), int(taxa_agree), C.byref(self.taxa_obj)))
+            if taxa_host:
+                lib().bh_taxa_set_solver(self.taxa_obj, C.cast(lib().bh_taxa_host, C.c_void_p), C.cast(lib().bh_taxa_rollup_host, C.c_void_p), None)
         if variants is not None:
             if variants_reads not in ("all", "unique") or not 1 <= int(variants_min_depth) < 1 << 31 or not 1 <= int(variants_min_alt) < 1 << 31:
                 raise ValueError("variants: reads all|unique, 1 <= min_depth, min_alt < 2^31")
@@ -1190,6 +1293,8 @@ class Session:
                 _chk(lib().bh_session_set_consensus(self.h, self.cons))
             if self.vcf:
                 _chk(lib().bh_session_set_vcf(self.h, self.vcf))
+            if self.taxa_obj:
+                _chk(lib().bh_session_set_taxa(self.h, self.taxa_obj))
             if self.cluster:
                 _chk(lib().bh_session_set_cluster(self.h, self.cluster))
             if self.chimera:
@@ -1198,7 +1303,7 @@ class Session:
             if self.h:
                 lib().bh_session_close(self.h)
                 self.h = C.c_void_p()
-            for name, close in (("sam", lib().bh_sam_close), ("vcf", lib().bh_vcf_close), ("cons", lib().bh_consensus_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
+            for name, close in (("sam", lib().bh_sam_close), ("taxa_obj", lib().bh_taxa_close), ("vcf", lib().bh_vcf_close), ("cons", lib().bh_consensus_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
                 if getattr(self, name):
                     close(getattr(self, name))
                     setattr(self, name, C.c_void_p())
@@ -1326,6 +1431,24 @@ class Session:
         _chk(lib().bh_em_stats(self.em, cols.ctypes.data))
         return cols
 
+    def taxa(self):
+        """the taxon tables so far: dict of names (bytes per node, node 0 = b"Unassigned"), parent, depth, header_node and the uint64 columns
+        own, clade, own_em, clade_em, each [columns][nodes] with column 0 = Dataset (the _em ones in units of 2^-30 read, zero without abundance)"""
+        if not self.taxa_obj:
+            raise HostError("the session has no taxa")
+        nc, nn = C.c_uint32(), C.c_uint32()
+        lib().bh_taxa_dims(self.taxa_obj, C.byref(nc), C.byref(nn))
+        cols = np.zeros((4, nc.value, nn.value), np.uint64)
+        _chk(lib().bh_taxa_stats(self.taxa_obj, cols.ctypes.data))
+        names, parent, depth, hn = _taxa_tree_arrays(lib().bh_taxa_tree_of(self.taxa_obj).contents)
+        return dict(names=names, parent=parent, depth=depth, header_node=hn, own=cols[0], clade=cols[1], own_em=cols[2], clade_em=cols[3])
+
+    def taxa_info(self):
+        """the last sample's figures: pairs, groups, reads, root_reads, deepest, device_us, peak_bytes"""
+        info = np.zeros(8, np.uint64)
+        lib().bh_taxa_last_info(self.taxa_obj, info.ctypes.data)
+        return dict(zip(("pairs", "groups", "reads", "root_reads", "deepest", "device_us", "peak_bytes"), (int(x) for x in info)))
+
     def abundance_info(self):
         """the last solved sample's figures: iterations, pairs, classes, delta, converged, device_us, peak_bytes, reads"""
         info, reads = np.zeros(8, np.uint64), C.c_uint64()
@@ -1430,6 +1553,11 @@ class Session:
                     err = lib().bh_last_error().decode("utf-8", "replace")
                 lib().bh_em_close(self.em)
                 self.em = C.c_void_p()
+            if self.taxa_obj:
+                if not lib().bh_session_ended(self.h) and not self.cov_aborted and lib().bh_taxa_write(self.taxa_obj, None, None):
+                    err = lib().bh_last_error().decode("utf-8", "replace")
+                lib().bh_taxa_close(self.taxa_obj)
+                self.taxa_obj = C.c_void_p()
             if self.pile:
                 if not lib().bh_session_ended(self.h) and not self.cov_aborted and lib().bh_pile_write(self.pile):
                     err = lib().bh_last_error().decode("utf-8", "replace")

@@ -211,6 +211,7 @@ def main(argv=None):
     ap.add_argument("--coverage-pad", type=int, default=0, help="bases a placement's range is widened by at both ends")
     ap.add_argument("--mates", help="not available here: paired-end reads are joined by burst_hip --mates (one process, the host gather)")
     ap.add_argument("--cigar", action="store_true", help="not available here: the alignment paths are traced by burst_hip --cigar (one process, the host gather)")
+    ap.add_argument("--taxa", metavar="PREFIX", help="not available here: the taxon tables are written by burst_hip --taxa (one process, the host gather)")
     ap.add_argument("--abundance", metavar="PREFIX", help="not available here: the abundance table is written by burst_hip --abundance (one process, the host gather)")
     ap.add_argument("--variants", metavar="PREFIX", help="not available here: the variants table is written by burst_hip --variants (one process, the host gather)")
     ap.add_argument("--cluster", metavar="PREFIX", help="not available here: reads are clustered by burst_hip --cluster (one process, the host gather)")
@@ -251,6 +252,9 @@ def main(argv=None):
         return 1
     if args.variants:       # (exit code 1, as burst_hip refuses what it cannot do)
         print("ERROR: --variants is not available in python -m burst_amd.run: use burst_hip --variants (one process, --gpus N with the host gather)", flush=True)
+        return 1
+    if args.taxa:           # (exit code 1, as burst_hip refuses it)
+        print("ERROR: --taxa is not available in python -m burst_amd.run: use burst_hip --taxa (one process, --gpus N with the host gather)", flush=True)
         return 1
     if args.abundance:      # (exit code 1, as burst_hip refuses it)
         print("ERROR: --abundance is not available in python -m burst_amd.run: use burst_hip --abundance (one process, --gpus N with the host gather)", flush=True)

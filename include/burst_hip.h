@@ -406,6 +406,34 @@ typedef struct BhipEmLine { uint32_t group, ref; } BhipEmLine;
 BHIP_API int bhip_em_run(void *handle, uint32_t n_headers, uint32_t n_groups, const uint32_t *group_w, const BhipEmLine *lines, uint64_t n_lines,
                          uint32_t max_iters, uint64_t tol, uint64_t *counts /* [n_headers], units of 2^-30 read */, uint64_t info[8]);
 
+/* Taxon tables: every group of reads goes to the lowest common ancestor of the taxonomies of the references it was placed on (burst_hip
+ * --taxa; the reference's embalmulate.c counts column 13 of BEST output, and its README leaves the tied references of ALLPATHS output to
+ * the user).  Everything is in integers and bit-exact on any machine.
+ *   tree        n_nodes nodes numbered in PREORDER: parent[0] = 0 is the root (depth 0); for v > 0, parent[v] < v and parent[v] is v - 1 or
+ *               one of its ancestors, so that a subtree is a contiguous range of numbers.  The order of siblings is free and no result
+ *               depends on it.  At most 64 levels below the root.  header_node[h] < n_nodes is the node of header h (0: no taxonomy).
+ *   groups      as bhip_em_run: group g stands for group_w[g] reads, its candidates are the DISTINCT ref among its lines (both strands and
+ *               all placements of one header are one candidate), n of them.  A group of weight 0 has a taxon and adds nothing.
+ *   taxon       t = (agree * n + 999) / 1000, agree in 501 .. 1000 permille (1000: the strict lowest common ancestor).  The group's taxon is
+ *               the deepest node whose subtree holds the nodes of at least t candidates.  It is unique: two nodes of one depth have
+ *               disjoint subtrees and t > n / 2.  A candidate at the root sends the group to the root when agree = 1000.
+ *   counts      own[v] = the sum of group_w over the groups whose taxon is v; clade[v] = the sum of own over the subtree of v (sums modulo
+ *               2^64); a group without lines counts nowhere; clade[0] = the reads of the groups with lines.
+ *   group_node  NULL, or [n_groups]: every group's taxon, 0xFFFFFFFF for a group without lines
+ *   info        [0] distinct (group, ref) pairs, [1] groups with lines, [2] their reads, [3] reads at the root = own[0], [4] the deepest level
+ *               of a group's taxon, [5] device microseconds (HIP events around everything launched), [6] peak device bytes, [7] 0
+ * bhip_taxa_rollup sums counts given per header (the abundance's, units of 2^-30 read) the same way: own[v] = the sum of header_count over
+ * the headers with header_node = v, clade = its subtree sums.
+ * No line: zeros, nothing is launched.  BHIP_E_ARG with a text, never a device fault, the handle staying usable: parent[0] != 0, a parent
+ * that breaks the preorder property, a node more than 64 levels deep, a header_node >= n_nodes, a line's ref >= n_headers or group >=
+ * n_groups, agree outside 501 .. 1000, n_lines >= 2^31.  The calls leave nothing resident but scratch buffers of the handle, which
+ * bhip_destroy frees.  Device side: csrc/bhip_taxa.hip. */
+BHIP_API int bhip_taxa_run(void *handle, uint32_t n_nodes, const uint32_t *parent, uint32_t n_headers, const uint32_t *header_node, uint32_t n_groups,
+                           const uint32_t *group_w, const BhipEmLine *lines, uint64_t n_lines, uint32_t agree,
+                           uint32_t *group_node /* may be NULL; 0xFFFFFFFF = no lines */, uint64_t *own, uint64_t *clade, uint64_t info[8]);
+BHIP_API int bhip_taxa_rollup(void *handle, uint32_t n_nodes, const uint32_t *parent, uint32_t n_headers, const uint32_t *header_node,
+                              const uint64_t *header_count, uint64_t *own, uint64_t *clade);
+
 /* Variant sites: which bases one sample's reads show at a reference position, and where they differ from the reference (burst_hip
  * --variants; no reference counterpart).  The result is a function of the sample's printed lines.  A LINE is a path as bhip_trace_paths
  * returns it -- query entry q of q_codes / q_off, lane refIx, first lane column ref_first, ops[op_off .. op_off + n_ops) -- placed on the
