@@ -49,7 +49,7 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
            "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_taxa_run", "bhip_taxa_rollup", "bhip_pile_run", "bhip_consensus_run", "bhip_consensus_info",
-           "bhip_alleles_run", "bhip_alleles_info",
+           "bhip_alleles_run", "bhip_alleles_info", "bhip_site_counts", "bhip_site_counts_info",
            "bhip_cluster_run", "bhip_cluster_info", "bhip_chimera_run", "bhip_chimera_info", "bhip_md_tags"]
 
 # BhipMateLine, 20 bytes: pair and header numbers, .b6 columns 9 and 10 (signed), column 11
@@ -98,12 +98,26 @@ CONS_INFO = ("events", "candidates", "segments", "covered", "device_us", "peak_b
 ALLELE_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("allele", "<u8"), ("ref", "<u4"), ("depth", "<u4"), ("count", "<u4"), ("pad", "<u4"), ("code_off", "<u8")])
 assert ALLELE_DTYPE.itemsize == 40
 ALLELES_INFO = ("events", "distinct", "alleles", "skipped_end", "skipped_adjacent", "skipped_long", "device_us", "peak_bytes")
+# bhip_site_counts: BhipCountRange, 16 bytes: a line covers [pos, pos + span - 1] of a header for w reads; BhipCountRecord, 24 bytes: allele 0 = a
+# site record (ref 1..4), else the allele word; BhipCountCell, 24 bytes: depth, n[A C G T], count
+COUNT_RANGE_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("span", "<u4"), ("w", "<u4")])
+COUNT_RECORD_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("allele", "<u8"), ("ref", "<u4"), ("pad", "<u4")])
+COUNT_CELL_DTYPE = np.dtype([("depth", "<u4"), ("n", "<u4", (4,)), ("count", "<u4")])
+assert COUNT_RANGE_DTYPE.itemsize == 16 and COUNT_RECORD_DTYPE.itemsize == 24 and COUNT_CELL_DTYPE.itemsize == 24
+SITE_COUNTS_INFO = ("ranges", "records", "device_us", "peak_bytes")
 MD_INFO = ("device_us", "requests", "md_bytes", "peak_bytes")
 
 # BhipClusterEdge, 12 bytes: read q has a printed line against read r with this many edits (bhip_cluster_run)
 CLUSTER_EDGE_DTYPE = np.dtype([("q", "<u4"), ("r", "<u4"), ("edits", "<u4")])
 assert CLUSTER_EDGE_DTYPE.itemsize == 12
 CLUSTER_INFO = ("rounds", "edges_kept", "centroids", "device_us", "device_bytes", "edges", "nodes")
+
+
+def count_arrays(ranges, sites, alleles, records):
+    """the four inputs of site_counts as contiguous arrays of their dtypes (None or an empty list: none)"""
+    def arr(x, dt):
+        return np.zeros(0, dt) if x is None or len(x) == 0 else np.ascontiguousarray(x, dtype=dt)
+    return arr(ranges, COUNT_RANGE_DTYPE), arr(sites, PILE_SITE_DTYPE), arr(alleles, ALLELE_DTYPE), arr(records, COUNT_RECORD_DTYPE)
 
 
 def cluster_edges(rows):
@@ -284,6 +298,10 @@ def _load():
     lib.bhip_alleles_run.restype = i32
     lib.bhip_alleles_info.argtypes = [vp, vp]
     lib.bhip_alleles_info.restype = i32
+    lib.bhip_site_counts.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp]
+    lib.bhip_site_counts.restype = i32
+    lib.bhip_site_counts_info.argtypes = [vp, vp]
+    lib.bhip_site_counts_info.restype = i32
     lib.bhip_cluster_run.argtypes = [vp, u32, vp, vp, u64, vp, vp]
     lib.bhip_cluster_run.restype = i32
     lib.bhip_cluster_info.argtypes = [vp, vp]
@@ -644,6 +662,22 @@ class Device:
         info = np.zeros(8, np.uint64)
         _chk(lib().bhip_alleles_info(self._h, _ptr(info)))
         return dict(zip(ALLELES_INFO, (int(x) for x in info)))
+
+    def site_counts(self, ranges, sites, alleles, records):
+        """one sample's counts at the records the caller names (bhip_site_counts).  ranges: COUNT_RANGE_DTYPE, the sample's lines; sites: its
+        pile_run(1, 1) result (PILE_SITE_DTYPE, ascending header, pos); alleles: its alleles_run(1, 1) result (ALLELE_DTYPE, in its order);
+        records: COUNT_RECORD_DTYPE, in any order.  Returns the cells (COUNT_CELL_DTYPE, one per record); site_counts_info() has the call's
+        figures"""
+        ranges, sites, alleles, records = count_arrays(ranges, sites, alleles, records)
+        cells, info = np.zeros(max(len(records), 1), COUNT_CELL_DTYPE), np.zeros(8, np.uint64)
+        _chk(lib().bhip_site_counts(self._h, _ptr(ranges), len(ranges), _ptr(sites), len(sites), _ptr(alleles), len(alleles), _ptr(records), len(records), _ptr(cells), _ptr(info)))
+        return cells[:len(records)]
+
+    def site_counts_info(self):
+        """the last site_counts' figures (bhip_site_counts_info): ranges, records, device_us, peak_bytes"""
+        info = np.zeros(8, np.uint64)
+        _chk(lib().bhip_site_counts_info(self._h, _ptr(info)))
+        return dict(zip(SITE_COUNTS_INFO, (int(x) for x in info)))
 
     def cluster_run(self, weights, edges):
         """greedy centroid clusters (bhip_cluster_run).  weights: uint32 per node (read), edges: CLUSTER_EDGE_DTYPE array (or rows q, r, edits), raw

@@ -456,6 +456,7 @@ struct Handle {
 	void *pile = nullptr;         // scratch buffers and events of bhip_pile_run (bhip_pile.hip), made by the first call that launches
 	void *cons = nullptr;         // scratch buffers and figures of bhip_consensus_run (bhip_consensus.hip), beside those of Handle::pile, which it shares
 	void *alleles = nullptr;      // scratch buffers and figures of bhip_alleles_run (bhip_alleles.hip), beside those of Handle::pile, which it shares
+	void *sitecounts = nullptr;   // scratch buffers, events and figures of bhip_site_counts (bhip_sitecounts.hip), made by the first call that launches
 	void *taxa = nullptr;         // scratch buffers and events of bhip_taxa_run and bhip_taxa_rollup (bhip_taxa.hip), made by the first call that launches
 	void *cluster = nullptr;      // scratch buffers and events of bhip_cluster_run (bhip_cluster.hip), made by the first call that launches
 	uint64_t cluster_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // bhip_cluster_info: the figures of the last bhip_cluster_run
@@ -485,6 +486,7 @@ void bhip_em_release(Handle *h);                                             // 
 void bhip_pile_release(Handle *h);                                           // bhip_pile.hip
 void bhip_consensus_release(Handle *h);                                      // bhip_consensus.hip
 void bhip_alleles_release(Handle *h);                                        // bhip_alleles.hip
+void bhip_sitecounts_release(Handle *h);                                     // bhip_sitecounts.hip
 void bhip_cluster_release(Handle *h);                                        // bhip_cluster.hip
 void bhip_taxa_release(Handle *h);                                           // bhip_taxa.hip
 void bhip_chimera_release(Handle *h);                                        // bhip_chimera.hip

@@ -76,6 +76,7 @@ extern "C" void bhip_destroy(void *handle) {
 	bhip_em_release(h);
 	bhip_consensus_release(h);
 	bhip_alleles_release(h);
+	bhip_sitecounts_release(h);
 	bhip_pile_release(h);
 	bhip_cluster_release(h);
 	bhip_taxa_release(h);

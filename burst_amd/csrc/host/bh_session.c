@@ -36,7 +36,7 @@ struct BhSession {
 	FILE *out; char *out_path;
 	char *cov_name;                 /* with a coverage or an abundance: the output the loaded sample was given (names its column, also when the sample fails) */
 	int taxa_col;                   /* ... and its column in the taxon tables */
-	int cov_col, em_col, pile_col, cons_col;  /* the loaded sample has its column in the coverage / the abundance, its block in the variants / the consensus already */
+	int cov_col, em_col, pile_col, cons_col, vcf_col;  /* the loaded sample has its column in the coverage / the abundance, its block in the variants / the consensus already */
 	BhPlaceSink sink;               /* the report's placements of the current sample (buffer kept across samples) */
 	BhMates *mates;                 /* bh_session_run_mates: the joiner, made on first use */
 	BhCluster *cluster;             /* bh_session_set_cluster: NULL, or the clustering every reported sample is given */
@@ -207,7 +207,10 @@ static int sample_fail_ex(BhSession *s, BhSampleResult *res, int rc, const char 
 		else if (s->cov_name && !s->cons_col) (void)bh_consensus_sample_failed(s->cons, s->cov_name);
 	}
 	if (s->sam && s->i0 >= 0) { if (s->dead) bh_sam_abort(s->sam); else bh_sam_discard(s->sam); }      /* (no OUT.sam of a sample that failed) */
-	if (s->vcf && s->i0 >= 0) { if (s->dead) bh_vcf_abort(s->vcf); else bh_vcf_sample_failed(s->vcf); }      /* (no OUT.vcf either) */
+	if (s->vcf && s->i0 >= 0) {      /* (no OUT.vcf either; a study gives the sample its '.' column unless bh_vcf_sample has dealt with it) */
+		if (s->dead) bh_vcf_abort(s->vcf);
+		else { bh_vcf_sample_failed(s->vcf); if (s->cov_name && !s->vcf_col) (void)bh_vcf_study_sample_failed(s->vcf, s->cov_name); }
+	}
 	free(s->cov_name); s->cov_name = NULL;
 	return bh_set_error(rc, "%s", res->err);
 }
@@ -221,7 +224,7 @@ int bh_session_load(BhSession *s, const char *queries, const char *out_path, BhS
 	if (s->dead) { res->rc = s->dead; snprintf(res->err, sizeof res->err, "the session was ended by an earlier error (code %d)", s->dead); return bh_set_error(s->dead, "%s", res->err); }
 	if (s->cur) return bh_set_error(BH_E_USAGE, "bh_session_load: the previous sample has not been finished or dropped");
 	s->tLoad = wall();
-	free(s->cov_name); s->cov_name = NULL; s->cov_col = s->em_col = s->taxa_col = s->pile_col = s->cons_col = 0;
+	free(s->cov_name); s->cov_name = NULL; s->cov_col = s->em_col = s->taxa_col = s->pile_col = s->cons_col = s->vcf_col = 0;
 	if ((s->o.cov || s->o.em || s->o.pile || s->cons || s->vcf || s->taxa) && out_path && s->i0 >= 0 && !(s->cov_name = strdup(out_path))) return bh_set_error(BH_E_OOM, "OOM:session");
 	SessIngest *g = NULL;
 	/* the outstanding ingest is this sample's: take it.  If it is another one's (prefetched before this sample was named) it stays
@@ -275,7 +278,7 @@ int bh_session_drop(BhSession *s) {
 	if (s->taxa && s->cur && s->cov_name && !s->dead) (void)bh_taxa_sample_failed(s->taxa, s->cov_name);
 	if (s->o.pile && s->cur && s->cov_name && !s->dead) (void)bh_pile_sample_failed(s->o.pile, s->cov_name);
 	if (s->cons && s->cur && s->cov_name && !s->dead) (void)bh_consensus_sample_failed(s->cons, s->cov_name);
-	if (s->vcf && s->cur) bh_vcf_sample_failed(s->vcf);
+	if (s->vcf && s->cur) { bh_vcf_sample_failed(s->vcf); if (s->cov_name && !s->dead) (void)bh_vcf_study_sample_failed(s->vcf, s->cov_name); }
 	drop_sample(s);
 	return BH_OK;
 }
@@ -435,6 +438,7 @@ int bh_session_finish(BhSession *s, BhSampleResult *res) {
 		}
 		if (s->vcf) {      /* the sample's OUT.vcf: its sites and its alleles, one call each over the lines the tracer handed over */
 			rc = bh_vcf_sample(s->vcf, R[s->i0].hh, s->cov_name, Q->codes, Q->qoff, Q->numEntries);
+			s->vcf_col = 1;      /* (a study has the sample, or its '.' column) */
 			if (rc) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); return sample_fail(s, res, rc, msg); }
 			if (o->verbose) bh_vcf_print_info(s->vcf);
 			PHASE("VCF of the sample");

@@ -25,6 +25,7 @@ struct BhVcf {
 	bh_pile_solver_fn pile_fn; void *pile_ctx;
 	bh_alleles_solver_fn al_fn; void *al_ctx;
 	uint64_t info[12]; int have_info;  /* of the last sample that was written */
+	BhVcfStudy *study;                 /* bh_vcf_set_study: NULL, or the study VCF every sample's (1, 1) lists are handed to (bh_vcfstudy.c) */
 };
 
 /* ---- the definition in plain C ---- */
@@ -196,9 +197,32 @@ int bh_vcf_open(const BhDb *db, const char *lengths_file, uint32_t min_depth, ui
 void bh_vcf_set_solver(BhVcf *v, bh_pile_solver_fn pile_fn, void *pile_ctx, bh_alleles_solver_fn al_fn, void *al_ctx) {
 	if (v) { v->pile_fn = pile_fn; v->pile_ctx = pile_ctx; v->al_fn = al_fn; v->al_ctx = al_ctx; }
 }
-void bh_vcf_abort(BhVcf *v) { if (v && !v->dead) v->dead = BH_E_DEVICE; }
+void bh_vcf_set_study(BhVcf *v, BhVcfStudy *study) { if (v) v->study = study; }
+void bh_vcf_abort(BhVcf *v) { if (v && !v->dead) v->dead = BH_E_DEVICE; if (v) bh_vcfstudy_abort(v->study); }
 void bh_vcf_sample_failed(BhVcf *v) { if (v) bh_pile_drop_lines(v->lines); }      /* (no OUT.vcf of a sample that failed) */
-static int die(BhVcf *v, int rc) { v->dead = rc; return rc; }
+int bh_vcf_study_sample_failed(BhVcf *v, const char *out_path) { return v && v->study ? bh_vcfstudy_sample_failed(v->study, out_path) : BH_OK; }
+static int die(BhVcf *v, int rc) { v->dead = rc; bh_vcfstudy_abort(v->study); return rc; }
+
+/* what the study file shares with OUT.vcf: the contig names, the lengths (no table: the database's own extents, as --sam takes them), the
+ * header block in front of the column line (study: the NS line as well) */
+uint32_t bh_vcf_n_headers(const BhVcf *v) { return v ? v->nH : 0; }
+const char *bh_vcf_contig(const BhVcf *v, uint32_t h) { return v && h < v->nH ? v->sn[h] : ""; }
+int bh_vcf_ensure_lengths(BhVcf *v, void *hh) {
+	if (!v) return bh_set_error(BH_E_USAGE, "bh_vcf_ensure_lengths: no vcf object");
+	if (v->have_len) return BH_OK;
+	if (!v->db) return bh_set_error(BH_E_USAGE, "bh_vcf_sample: no reference lengths");
+	const int rc = bh_cov_default_lengths(v->db, v->al_fn ? NULL : hh, v->len);
+	if (!rc) v->have_len = 1;
+	return rc;
+}
+void bh_vcf_write_header(const BhVcf *v, FILE *f, int study) {
+	fputs("##fileformat=VCFv4.2\n##source=burst_hip\n", f);
+	for (uint32_t h = 0; h < v->nH; ++h) fprintf(f, "##contig=<ID=%s,length=%u>\n", v->sn[h], v->len[h]);
+	fputs("##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Reads observing the position\">\n", f);
+	if (study) fputs("##INFO=<ID=NS,Number=1,Type=Integer,Description=\"Samples with a read observing the position\">\n", f);
+	fputs("##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Reads observing the position\">\n"
+	      "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Reads per allele, reference first\">\n", f);
+}
 
 int bh_vcf_collect(BhVcf *v, const uint64_t *idx, const BhipPathReq *req, const uint32_t *first, const uint64_t *off, const uint32_t *ops, uint64_t nr,
                    const BhPathBuf *bufs, uint64_t n_chunks) {
@@ -256,11 +280,10 @@ int bh_vcf_sample(BhVcf *v, void *hh, const char *out_path, const uint8_t *q_cod
 	if (v->dead) return bh_set_error(v->dead, "the VCF output was ended by an earlier error");
 	if (n_queries > 0xFFFFFFFFull) return die(v, bh_set_error(BH_E_INTERNAL, "vcf: %lu query entries", (unsigned long)n_queries));
 	int rc;
-	if (!v->have_len) {      /* no table: the database's own extents, as --sam takes them */
-		if (!v->db) return die(v, bh_set_error(BH_E_USAGE, "bh_vcf_sample: no reference lengths"));
-		if ((rc = bh_cov_default_lengths(v->db, v->al_fn ? NULL : hh, v->len))) return die(v, rc);
-		v->have_len = 1;
-	}
+	if ((rc = bh_vcf_ensure_lengths(v, hh))) return die(v, rc);
+	/* with a study attached the solvers are asked at (1, 1): everything the sample observes that is not plain, which the study keeps; the
+	 * thresholds are then applied here (write_records does it for the sites, the alleles are filtered below), so OUT.vcf has the same bytes */
+	const uint32_t askDepth = v->study ? 1u : v->minDepth, askAlt = v->study ? 1u : v->minAlt;
 	const BhipPileLine *lines = NULL; const uint32_t *ops = NULL; uint64_t n_ops = 0, n_printed = 0;
 	const uint64_t n_lines = bh_pile_lines(v->lines, &lines, &ops, &n_ops, &n_printed);
 	uint64_t site_cap = n_lines < 1024 ? 1024 : n_lines, ns = 0, pinfo[8] = {0};
@@ -271,7 +294,7 @@ int bh_vcf_sample(BhVcf *v, void *hh, const char *out_path, const uint8_t *q_cod
 		BhipPileSite *s2 = realloc(sites, site_cap * sizeof(*s2));
 		if (!s2) VCF_FAIL(bh_set_error(BH_E_OOM, "OOM:vcf"));
 		sites = s2;
-		rc = (v->pile_fn ? v->pile_fn : pile_device)(v->pile_fn ? v->pile_ctx : hh, q_codes, q_off, (uint32_t)n_queries, lines, n_lines, ops, n_ops, v->minDepth, v->minAlt, sites, site_cap, &ns, pinfo);
+		rc = (v->pile_fn ? v->pile_fn : pile_device)(v->pile_fn ? v->pile_ctx : hh, q_codes, q_off, (uint32_t)n_queries, lines, n_lines, ops, n_ops, askDepth, askAlt, sites, site_cap, &ns, pinfo);
 		if (rc != BH_E_CAPACITY) break;
 		if (attempt || ns <= site_cap) { rc = bh_set_error(BH_E_INTERNAL, "vcf: %lu sites do not fit the room the first call asked for", (unsigned long)ns); break; }
 		site_cap = ns;
@@ -281,7 +304,7 @@ int bh_vcf_sample(BhVcf *v, void *hh, const char *out_path, const uint8_t *q_cod
 		BhipAllele *a2 = realloc(al, al_cap * sizeof(*a2)); if (a2) al = a2;
 		uint8_t *c2 = realloc(codes, code_cap); if (c2) codes = c2;
 		if (!a2 || !c2) VCF_FAIL(bh_set_error(BH_E_OOM, "OOM:vcf"));
-		rc = (v->al_fn ? v->al_fn : alleles_device)(v->al_fn ? v->al_ctx : hh, q_codes, q_off, (uint32_t)n_queries, lines, n_lines, ops, n_ops, v->minDepth, v->minAlt, al, al_cap, &na,
+		rc = (v->al_fn ? v->al_fn : alleles_device)(v->al_fn ? v->al_ctx : hh, q_codes, q_off, (uint32_t)n_queries, lines, n_lines, ops, n_ops, askDepth, askAlt, al, al_cap, &na,
 		                                            codes, code_cap, &nc, ainfo);
 		if (rc != BH_E_CAPACITY) break;
 		if (attempt || (na <= al_cap && nc <= code_cap)) { rc = bh_set_error(BH_E_INTERNAL, "vcf: %lu alleles and %lu codes do not fit the room the first call asked for", (unsigned long)na, (unsigned long)nc); break; }
@@ -289,35 +312,45 @@ int bh_vcf_sample(BhVcf *v, void *hh, const char *out_path, const uint8_t *q_cod
 		if (nc > code_cap) code_cap = nc;
 	}
 	if (rc) VCF_FAIL(rc);
+	BhipAllele *al_all = NULL; uint64_t na_all = na;      /* (study: the (1, 1) list is kept whole, OUT.vcf takes the alleles that pass) */
+	if (v->study) {
+		if (!(al_all = malloc((na ? na : 1) * sizeof(*al_all)))) VCF_FAIL(bh_set_error(BH_E_OOM, "OOM:vcf"));
+		memcpy(al_all, al, na * sizeof(*al));
+		uint64_t k = 0;
+		for (uint64_t i = 0; i < na; ++i) if (al[i].depth >= v->minDepth && al[i].count >= v->minAlt) al[k++] = al[i];      /* (code_off still points into the whole code list) */
+		na = k; ainfo[2] = k;
+	}
 	/* OUT.vcf under a temporary name */
 	char *finn = NULL, *tmpn = NULL, *name = bh_pile_sample_name(out_path);
-	if (!name || asprintf(&finn, "%s.vcf", out_path) < 0) { finn = NULL; free(name); VCF_FAIL(bh_set_error(BH_E_OOM, "OOM:vcf")); }
-	if (asprintf(&tmpn, "%s.vcf.tmp%ld", out_path, (long)getpid()) < 0) { free(name); free(finn); VCF_FAIL(bh_set_error(BH_E_OOM, "OOM:vcf")); }
+	if (!name || asprintf(&finn, "%s.vcf", out_path) < 0) { finn = NULL; free(name); free(al_all); VCF_FAIL(bh_set_error(BH_E_OOM, "OOM:vcf")); }
+	if (asprintf(&tmpn, "%s.vcf.tmp%ld", out_path, (long)getpid()) < 0) { free(name); free(finn); free(al_all); VCF_FAIL(bh_set_error(BH_E_OOM, "OOM:vcf")); }
 	FILE *f = fopen(tmpn, "wb");
 	if (!f) {      /* (the sample's own error: the object stays usable) */
 		rc = bh_set_error(BH_E_IO, "ERROR: Cannot open output: %s", tmpn);
-		free(name); free(finn); free(tmpn); free(sites); free(al); free(codes);
+		free(name); free(finn); free(tmpn); free(sites); free(al); free(codes); free(al_all);
 		bh_pile_drop_lines(v->lines);
-		return rc;
+		(void)bh_vcfstudy_sample_failed(v->study, out_path);
+		return bh_set_error(BH_E_IO, "ERROR: Cannot open output: %s.vcf.tmp%ld", out_path, (long)getpid());
 	}
 	setvbuf(f, NULL, _IOFBF, 1 << 20);
-	fputs("##fileformat=VCFv4.2\n##source=burst_hip\n", f);
-	for (uint32_t h = 0; h < v->nH; ++h) fprintf(f, "##contig=<ID=%s,length=%u>\n", v->sn[h], v->len[h]);
-	fputs("##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Reads observing the position\">\n"
-	      "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Reads observing the position\">\n"
-	      "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Reads per allele, reference first\">\n", f);
+	bh_vcf_write_header(v, f, 0);
 	fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", name);
 	uint64_t counts[3] = {0, 0, 0};
 	const int bad = write_records(v, f, sites, ns, al, na, codes, nc, counts);
-	free(name); free(sites); free(al); free(codes);
+	free(name);
 	rc = BH_OK;
 	if (bad) rc = bh_set_error(BH_E_INTERNAL, "vcf: a site or an allele is out of order or out of range");
 	if ((ferror(f) | fclose(f)) && !rc) rc = bh_set_error(BH_E_IO, "ERROR: write failed: %s", tmpn);
 	if (!rc && rename(tmpn, finn)) rc = bh_set_error(BH_E_IO, "ERROR: Cannot rename %s to %s", tmpn, finn);
 	if (rc) (void)unlink(tmpn);
 	free(finn); free(tmpn);
+	if (v->study) {      /* the sample has its OUT.vcf: the study keeps its ranges and its (1, 1) lists; without one its column is '.' */
+		if (rc == BH_E_IO) { char msg[512]; snprintf(msg, sizeof msg, "%s", bh_last_error()); (void)bh_vcfstudy_sample_failed(v->study, out_path); bh_set_error(rc, "%s", msg); }
+		else if (!rc) rc = bh_vcfstudy_add(v->study, out_path, lines, n_lines, ops, sites, ns, al_all, na_all, codes, nc, v->minDepth, v->minAlt);
+	}
+	free(sites); free(al); free(codes); free(al_all);
 	bh_pile_drop_lines(v->lines);
-	if (rc) { if (rc != BH_E_IO) v->dead = rc; return rc; }
+	if (rc) { if (rc != BH_E_IO && rc != BH_E_USAGE) die(v, rc); return rc; }
 	v->info[0] = n_printed; v->info[1] = ainfo[0]; v->info[2] = ainfo[1]; v->info[3] = ainfo[2]; v->info[4] = counts[0]; v->info[5] = counts[1]; v->info[6] = counts[2];
 	v->info[7] = ainfo[3]; v->info[8] = ainfo[4]; v->info[9] = ainfo[5]; v->info[10] = ainfo[6] + pinfo[3]; v->info[11] = ainfo[7] > pinfo[4] ? ainfo[7] : pinfo[4];
 	v->have_info = 1;

@@ -613,6 +613,48 @@ int  bh_alleles_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off, 
                      const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, uint32_t min_alt, BhipAllele *alleles, uint64_t cap, uint64_t *n_alleles,
                      uint8_t *codes, uint64_t code_cap, uint64_t *n_codes, uint64_t info[8]);
 
+/* ---- the study VCF: every sample's counts at every record any sample reports (bh_vcfstudy.c; burst_hip --vcf --vcf-study PREFIX) ----
+ * The definition is include/burst_hip.h "Site counts" (DESIGN.md section 7k).  With a study attached (bh_vcf_set_study) bh_vcf_sample asks
+ * its two solvers at thresholds (1, 1), applies --vcf-min-depth and --vcf-min-alt on the host -- OUT.vcf keeps its bytes -- and hands the
+ * sample over (bh_vcfstudy_add): per sample the study keeps in host memory a range of 16 bytes per line, the (1, 1) sites and alleles and
+ * the records the sample reports with the codes of its Dels; a failed sample keeps nothing.  bh_vcfstudy_write merges the reported records
+ * in the order of OUT.vcf, makes ONE solver call per sample on the reporting rank's handle and writes PREFIXstudy.vcf under a temporary
+ * name, renamed when it is whole: the header block of OUT.vcf by the same code (bh_vcf_write_header) with an NS line, a column per sample
+ * in study order under the coverage tables' names (bh_pile_sample_name), INFO DP=<sum of the depths>;NS=<samples with depth >= 1>, FORMAT
+ * DP:AD for every sample with no threshold applied, explicit zeros for a sample without a read there, `.` for a sample that failed alone.
+ * Two samples of one name are BH_E_USAGE that names both (bh_vcfstudy_check_names: the command line asks before a device is touched).  A
+ * list that comes back inconsistent (n[ref - 1] > depth, count > depth) is BH_E_INTERNAL.  Any error but a usage error is final: no file
+ * is written and bh_vcfstudy_close removes the temporary file.
+ *   bh_vcfstudy_set_solver   another solver (tests): bhip_site_counts' arguments behind ctx, return codes in this file's terms; NULL: the device
+ *   bh_vcfstudy_print_info   the `VcfStudy:` line; bh_vcfstudy_last_info: [0] samples done [1] failed [2] SNV [3] Del [4] Ins records [5] cells
+ *                            [6] host bytes kept [7] device microseconds
+ *   bh_site_counts_host      the primitive in plain sequential C, a solver (ctx unused): a loop over all ranges per record */
+typedef struct BhVcfStudy BhVcfStudy;
+typedef int (*bh_sitecounts_solver_fn)(void *ctx, const BhipCountRange *ranges, uint64_t n_ranges, const BhipPileSite *sites, uint64_t n_sites, const BhipAllele *alleles, uint64_t n_alleles,
+                                       const BhipCountRecord *records, uint64_t n_records, BhipCountCell *cells, uint64_t info[8]);
+int  bh_vcfstudy_open(const char *prefix, BhVcfStudy **study);
+void bh_vcfstudy_set_solver(BhVcfStudy *study, bh_sitecounts_solver_fn fn, void *ctx);
+int  bh_vcfstudy_check_names(const char *const *out_paths, uint64_t n);
+int  bh_vcfstudy_add(BhVcfStudy *study, const char *out_path, const BhipPileLine *lines, uint64_t n_lines, const uint32_t *ops, const BhipPileSite *sites, uint64_t n_sites,
+                     const BhipAllele *alleles, uint64_t n_alleles, const uint8_t *codes, uint64_t n_codes, uint32_t min_depth, uint32_t min_alt);
+int  bh_vcfstudy_sample_failed(BhVcfStudy *study, const char *out_path);
+void bh_vcfstudy_abort(BhVcfStudy *study);
+int  bh_vcfstudy_write(BhVcfStudy *study, BhVcf *vcf, void *hip_handle);
+const char *bh_vcfstudy_path(const BhVcfStudy *study);
+void bh_vcfstudy_print_info(BhVcfStudy *study);
+void bh_vcfstudy_last_info(const BhVcfStudy *study, uint64_t info[8]);
+void bh_vcfstudy_close(BhVcfStudy *study);
+int  bh_site_counts_host(void *unused, const BhipCountRange *ranges, uint64_t n_ranges, const BhipPileSite *sites, uint64_t n_sites, const BhipAllele *alleles, uint64_t n_alleles,
+                         const BhipCountRecord *records, uint64_t n_records, BhipCountCell *cells, uint64_t info[8]);
+/* bh_vcf.c's side: the study every sample is handed to (NULL: none; the caller opens and closes it); a sample that failed before its
+ * bh_vcf_sample gets its `.` column; what the study file shares with OUT.vcf */
+void bh_vcf_set_study(BhVcf *vcf, BhVcfStudy *study);
+int  bh_vcf_study_sample_failed(BhVcf *vcf, const char *out_path);
+uint32_t bh_vcf_n_headers(const BhVcf *vcf);
+const char *bh_vcf_contig(const BhVcf *vcf, uint32_t header);
+int  bh_vcf_ensure_lengths(BhVcf *vcf, void *hip_handle);
+void bh_vcf_write_header(const BhVcf *vcf, FILE *f, int study);
+
 /* ---- greedy centroid clusters of the reads of a query file aligned against itself (bh_cluster.c; burst_hip --cluster) ----
  * The definition is bhip_cluster_run's (include/burst_hip.h): nodes = the reads in file order, named by column 1; weight 1, or with
  * use_sizes the N of a trailing `;size=N[;]`; an edge per printed line whose column 2 is the name of another read, its edits the smallest

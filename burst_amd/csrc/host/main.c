@@ -14,6 +14,7 @@
  *             [--chimera-min-seg G] [--chimera-min-gain D]      de-novo two-parent chimera check of the reads from their self-hits and the hits' paths (bh_chimera.c)
  *   ... -q / -o or --samples ... --variants PREFIX [--variants-min-depth N] [--variants-min-alt N] [--variants-reads all|unique]   variant sites per sample (bh_pile.c)
  *   ... -q / -o or --samples ... --consensus PREFIX [--consensus-min-depth N] [--consensus-min-breadth PERMILLE] [--consensus-reads all|unique] [--consensus-lengths FILE]   consensus per reference and sample (bh_consensus.c)
+ *   ... --vcf --vcf-study PREFIX        PREFIXstudy.vcf: every sample's DP:AD at every record any sample's OUT.vcf has (bh_vcfstudy.c)
  *   ... -q / -o or --samples ... --vcf [--vcf-min-depth N] [--vcf-min-alt N] [--vcf-reads all|unique] [--vcf-lengths FILE]   OUT.vcf beside every .b6 output OUT: SNVs and indel alleles (bh_vcf.c)
  *   ... -q / -o or --samples ... --sam [--sam-unmapped] [--sam-lengths FILE]      OUT.sam beside every .b6 output OUT, with NM and MD tags (bh_sam.c)
  *
@@ -141,6 +142,7 @@ typedef struct {
 	const char *cons_prefix; uint32_t cons_min_depth, cons_min_breadth; int cons_unique; const char *cons_lengths;
 	int vcf; uint32_t vcf_min_depth, vcf_min_alt; int vcf_unique; const char *vcf_lengths;
 	const char *taxa_prefix; uint32_t taxa_agree;
+	const char *vcf_study;
 } SamplesArgs;
 typedef struct { char *q, *o, *m; int line; } Sample;      /* m: the mates file of a three-field line, or NULL */
 
@@ -202,6 +204,24 @@ static int open_vcf(const BhDb *db, const char *lengths, uint32_t min_depth, uin
 	atexit(vcf_atexit);
 	return 0;
 }
+/* the study VCF of a run: closed on every way out, so that a run that ends on an error leaves neither file nor temporary file */
+static BhVcfStudy *g_vcfstudy;
+static void vcfstudy_atexit(void) { bh_vcfstudy_close(g_vcfstudy); g_vcfstudy = NULL; }
+static int open_vcfstudy(const char *prefix) {
+	const int rc = bh_vcfstudy_open(prefix, &g_vcfstudy);
+	if (rc) { fprintf(stderr, "%s\n", bh_last_error()); return code_to_exit(rc); }
+	bh_vcf_set_study(g_vcf, g_vcfstudy);
+	atexit(vcfstudy_atexit);
+	return 0;
+}
+/* the end of a run with --vcf-study: the file, its line on standard output.  Returns 0 or the exit code */
+static int write_vcfstudy(void *hh, const char *prefix) {
+	const int rc = bh_vcfstudy_write(g_vcfstudy, g_vcf, hh);
+	if (rc) { if (rc == BH_E_USAGE) puts(bh_last_error()); else fprintf(stderr, "%s\n", bh_last_error()); return code_to_exit(rc); }
+	bh_vcfstudy_print_info(g_vcfstudy);
+	printf("Study VCF written: %sstudy.vcf\n", prefix);
+	return 0;
+}
 static int samples_main(SamplesArgs *a) {
 	Sample *S = NULL; int nS = 0, rc;
 	if (a->list_FN) { const int e = read_sample_list(a, &S, &nS); if (e) return e; }
@@ -221,6 +241,15 @@ static int samples_main(SamplesArgs *a) {
 	if (any_mates && a->var_prefix) { puts("ERROR: --variants of paired output are out of scope: they do not go with mates"); return 1; }
 	if (any_mates && a->cons_prefix) { puts("ERROR: --consensus of paired output is out of scope: it does not go with mates"); return 1; }
 	if (any_mates && a->vcf) { puts("ERROR: --vcf of paired output is out of scope: it does not go with mates"); return 1; }
+	if (a->vcf_study) {      /* (two samples of one name would share a column: refused before a device is touched) */
+		const char **outs = calloc((size_t)nS, sizeof(*outs));
+		if (!outs) { fputs("OOM:samples\n", stderr); return 3; }
+		for (int i = 0; i < nS; ++i) outs[i] = S[i].o;
+		rc = bh_vcfstudy_check_names(outs, (uint64_t)nS);
+		free(outs);
+		if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; }
+		if (rc) DIE(rc);
+	}
 	if (any_mates && a->sam) { puts("ERROR: --sam of paired output (paired flags, RNEXT, TLEN) is out of scope: it does not go with mates"); return 1; }
 	const int usedb = bh_is_edx(a->ref_FN);
 	if (usedb < 0) DIE(usedb);
@@ -300,6 +329,7 @@ static int samples_main(SamplesArgs *a) {
 		const int e = open_vcf(&db, a->vcf_lengths, a->vcf_min_depth, a->vcf_min_alt, a->vcf_unique);
 		if (e) { bh_session_close(ses); return e; }
 		if ((rc = bh_session_set_vcf(ses, g_vcf))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); bh_session_close(ses); return 1; } DIES(rc); }
+		if (a->vcf_study) { const int e2 = open_vcfstudy(a->vcf_study); if (e2) { bh_session_close(ses); return e2; } }
 	}
 	if (shard_db && (uint32_t)n_shards > db.numRclumps) { bh_session_close(ses); puts("ERROR: more database shards than clumps"); return 1; }
 	{ const int e = open_devices(&db, n_gpus, dev_list, shard_db, n_shards, a->accel_dev, K, a->z, hhs, ranks, slices); if (e) { bh_session_close(ses); return e; } }
@@ -352,6 +382,12 @@ static int samples_main(SamplesArgs *a) {
 		else printf("Consensus written: %sconsensus.fa, %sconsensus.txt\n", a->cons_prefix, a->cons_prefix);
 	} else if (g_cons) puts("No consensus is written: the run ended on an error");
 	bh_consensus_close(g_cons); g_cons = NULL;
+	if (g_vcfstudy && !bh_session_ended(ses)) {      /* one bhip_site_counts call per sample on rank 0's handle, then the file */
+		tp = wall();
+		const int e = write_vcfstudy(hhs[0], a->vcf_study);
+		if (e) { if (!first_fail) first_fail = e; } else PHASE("study VCF");
+	} else if (g_vcfstudy) puts("No study VCF is written: the run ended on an error");
+	bh_vcfstudy_close(g_vcfstudy); g_vcfstudy = NULL;
 	bh_vcf_close(g_vcf); g_vcf = NULL;     /* (every sample's file was renamed or removed when the sample ended) */
 	bh_sam_close(sam); sam = NULL;         /* (every sample's file was renamed or removed when the sample ended) */
 	printf("\nSamples: %d done, %d failed. Alignment time: %f seconds\n", n_done, n_failed, wall() - start);
@@ -427,6 +463,12 @@ static void usage(void) {
 	puts("                  >= --vcf-min-alt reads.  INFO DP=Depth, sample field DP:AD (for an indel AD's first number is the observing reads without this");
 	puts("                  allele).  An indel at an end of a path or directly behind the other kind is no allele; nothing is left-aligned.  --vcf-reads");
 	puts("                  unique counts only reads printed on one line.  Refuses what --variants refuses, and --cluster and --chimeras");
+	puts("--vcf-study <prefix>: with --vcf, leave <prefix>study.vcf as well: one multi-sample VCF with a record wherever at least one sample's OUT.vcf has");
+	puts("                  one (an SNV's ALT is the union of the samples' ALTs) and a column per sample in study order, named as the coverage tables name");
+	puts("                  them.  Every sample's DP:AD is given at every record with no threshold applied: a sample that shows the reference there has its");
+	puts("                  reads on the first AD number, one without a read prints 0:0,0, one that failed alone prints '.'.  INFO DP=<sum of the depths>;");
+	puts("                  NS=<samples with a read there>.  No pooled call and no genotypes; -q / -o is a study of one sample.  Two samples of one name are");
+	puts("                  refused.  OUT.vcf keeps its bytes");
 	puts("--cluster <prefix> [--cluster-sizes]: with -q reads -r the same reads (FASTA or .edx) -m FORAGE, greedy centroid clusters of the reads from the");
 	puts("                  lines they print against each other: the reads in the order of their weight (1, or with --cluster-sizes the N of a trailing");
 	puts("                  ;size=N of the name), ties in file order; a read with a line to an earlier centroid joins the one with the fewest edits, any");
@@ -470,6 +512,7 @@ int main(int argc, char **argv) {
 	const char *mates_FN = 0; BhMatesOpts mopts = {BHIP_MATES_FR, 0, 1000, BHIP_MATES_ALL}; int mates_opts_given = 0;
 	const char *clu_prefix = 0; int clu_sizes = 0;
 	int sam = 0, sam_unmapped = 0; const char *sam_lengths = 0;
+	const char *vcf_study = 0;
 	int vcf = 0, vcf_unique = 0, vcf_opts_given = 0; uint32_t vcf_min_depth = 4, vcf_min_alt = 2; const char *vcf_lengths = 0;
 	const char *cons_prefix = 0, *cons_lengths = 0; uint32_t cons_min_depth = 4, cons_min_breadth = 0; int cons_unique = 0, cons_opts_given = 0;
 	const char *chi_prefix = 0; int chi_sizes = 0, chi_opts_given = 0; uint32_t chi_skew = 2, chi_min_seg = 16, chi_min_gain = 3;
@@ -554,6 +597,7 @@ int main(int argc, char **argv) {
 			NEEDARG("--vcf-reads"); vcf_opts_given = 1;
 			if (!strcmp(argv[i], "all")) vcf_unique = 0; else if (!strcmp(argv[i], "unique")) vcf_unique = 1; else { puts("ERROR: --vcf-reads all|unique"); return 1; }
 		}
+		else if (!strcmp(a, "--vcf-study")) { NEEDARG("--vcf-study"); vcf_study = argv[i]; }
 		else if (!strcmp(a, "--vcf-lengths")) { NEEDARG("--vcf-lengths"); vcf_lengths = argv[i]; vcf_opts_given = 1; }
 		else if (!strcmp(a, "--sam")) sam = 1;
 		else if (!strcmp(a, "--sam-unmapped")) sam_unmapped = 1;
@@ -717,6 +761,7 @@ int main(int argc, char **argv) {
 	if (cons_prefix && !samples_FN && !(ref_FN && query_FN && output_FN)) { puts("ERROR: --consensus goes with an alignment run: -r, -q and -o, or --samples"); return 1; }
 	/* (--vcf counts from the same paths, traced on the same handle: it refuses what --variants refuses, and the self-alignment outputs) */
 	if (vcf_opts_given && !vcf) { puts("ERROR: --vcf-min-depth, --vcf-min-alt, --vcf-reads and --vcf-lengths go with --vcf"); return 1; }
+	if (vcf_study && !vcf) { puts("ERROR: --vcf-study goes with --vcf"); return 1; }
 	if (vcf && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --vcf calls from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
 	if (vcf && (shard_db || n_shards)) { puts("ERROR: --vcf traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
 	if (vcf && !gather_host) { puts("ERROR: --vcf takes the host gather only (drop --gather rccl)"); return 1; }
@@ -770,7 +815,7 @@ int main(int argc, char **argv) {
 		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given, em_prefix, em_iters, em_tol,
 		                  var_prefix, var_min_depth, var_min_alt, var_unique, sam, sam_unmapped, sam_lengths,
 		                  cons_prefix, cons_min_depth, cons_min_breadth, cons_unique, cons_lengths,
-		                  vcf, vcf_min_depth, vcf_min_alt, vcf_unique, vcf_lengths, taxa_prefix, (uint32_t)taxa_agree};
+		                  vcf, vcf_min_depth, vcf_min_alt, vcf_unique, vcf_lengths, taxa_prefix, (uint32_t)taxa_agree, vcf_study};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
@@ -908,6 +953,7 @@ int main(int argc, char **argv) {
 	if (taxa_prefix && (rc = bh_taxa_open(&db, taxa_prefix, &taxonomy, txo.ncbi, (uint32_t)taxa_agree, &taxa))) { JOIN_INGEST(); if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
 	if (cons_prefix) { const int e = open_consensus(&db, cons_prefix, cons_lengths, cons_min_depth, cons_min_breadth, cons_unique); if (e) { JOIN_INGEST(); return e; } }
 	if (vcf) { const int e = open_vcf(&db, vcf_lengths, vcf_min_depth, vcf_min_alt, vcf_unique); if (e) { JOIN_INGEST(); return e; } }
+	if (vcf_study) { const int e = open_vcfstudy(vcf_study); if (e) { JOIN_INGEST(); return e; } }
 	if (sam) {      /* (before a device is touched: two headers of one name, a lengths table without a header) */
 		if ((rc = bh_sam_open(&db, sam_lengths, sam_unmapped, &g_sam))) { JOIN_INGEST(); if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
 		atexit(sam_atexit);      /* (whichever way the run ends before bh_sam_end: no file, no temporary file) */
@@ -1084,6 +1130,12 @@ int main(int argc, char **argv) {
 		bh_vcf_print_info(g_vcf);
 		printf("VCF records written: %s.vcf\n", output_FN);
 		PHASE("VCF");
+		if (g_vcfstudy) {      /* a study of one sample */
+			const int e = write_vcfstudy(hhs[0], vcf_study);
+			if (e) { fflush(NULL); return e; }
+			PHASE("study VCF");
+			bh_vcfstudy_close(g_vcfstudy); g_vcfstudy = NULL;
+		}
 		bh_vcf_close(g_vcf); g_vcf = NULL;
 	}
 	if (cov) {      /* a study of one sample: the Dataset column and the sample's (rank 0's handle; the lines exist only here) */

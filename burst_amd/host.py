@@ -400,6 +400,22 @@ def lib():
         L.bh_alleles_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                       C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         L.bh_session_set_vcf.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_vcfstudy_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        L.bh_vcfstudy_set_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_vcfstudy_set_solver.restype = None
+        L.bh_vcfstudy_check_names.argtypes = [C.POINTER(C.c_char_p), C.c_uint64]
+        L.bh_vcfstudy_add.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]
+        L.bh_vcfstudy_sample_failed.argtypes = [C.c_void_p, C.c_char_p]
+        L.bh_vcfstudy_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("bh_vcfstudy_abort", "bh_vcfstudy_print_info", "bh_vcfstudy_close"):
+            getattr(L, name).argtypes = [C.c_void_p]
+            getattr(L, name).restype = None
+        L.bh_vcfstudy_last_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_vcfstudy_last_info.restype = None
+        L.bh_vcf_set_study.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_vcf_set_study.restype = None
+        L.bh_vcf_study_sample_failed.argtypes = [C.c_void_p, C.c_char_p]
+        L.bh_site_counts_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.bh_sam_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
         L.bh_sam_open_heads.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.bh_sam_set_md.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -702,6 +718,19 @@ def consensus_host(refs, q_codes, q_off, lines, ops, min_depth=4, seg_cap=None, 
 
 
 VCF_INFO = ("lines", "events", "distinct", "alleles", "snv", "del", "ins", "skipped_end", "skipped_adjacent", "skipped_long", "device_us", "peak_bytes")
+
+
+VCF_STUDY_INFO = ("samples", "failed", "snv", "del", "ins", "cells", "host_bytes", "device_us")
+
+
+def site_counts_host(ranges, sites, alleles, records):
+    """bh_site_counts_host, bhip_site_counts' definition in plain sequential C (no device; a loop over all ranges per record): the cells
+    (capi.COUNT_CELL_DTYPE, one per record).  Arguments as capi.Device.site_counts takes them"""
+    ranges, sites, alleles, records = capi.count_arrays(ranges, sites, alleles, records)
+    cells, info = np.zeros(max(len(records), 1), capi.COUNT_CELL_DTYPE), np.zeros(8, np.uint64)
+    _chk(lib().bh_site_counts_host(None, ranges.ctypes.data, len(ranges), sites.ctypes.data, len(sites), alleles.ctypes.data, len(alleles), records.ctypes.data, len(records),
+                                   cells.ctypes.data, info.ctypes.data))
+    return cells[:len(records)]
 
 
 def alleles_host(refs, q_codes, q_off, lines, ops, min_depth=4, min_alt=2, cap=None, code_cap=None):
@@ -1092,7 +1121,7 @@ class Session:
                  chimeras=None, chimera_sizes=False, chimera_skew=2, chimera_min_seg=16, chimera_min_gain=3, chimera_host=False,
                  sam=False, sam_unmapped=False, sam_lengths=None, sam_md=None,
                  consensus=None, consensus_min_depth=4, consensus_min_breadth=0, consensus_reads="all", consensus_lengths=None, consensus_host=False,
-                 vcf=False, vcf_min_depth=4, vcf_min_alt=2, vcf_reads="all", vcf_lengths=None, vcf_host=False,
+                 vcf=False, vcf_min_depth=4, vcf_min_alt=2, vcf_reads="all", vcf_lengths=None, vcf_host=False, vcf_study=None, vcf_study_host=False,
                  taxa=None, taxa_agree=1000, taxa_host=False):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
         reference and the path's CIGAR in =XID (bh_paths.c; traced on the handle of the rank that reports; query-sharded sessions of one
@@ -1136,11 +1165,18 @@ class Session:
         `name<TAB>length` table for the contig lines, default the database's own extents), from ONE bhip_pile_run and ONE bhip_alleles_run
         per sample on rank 0's device handle -- or bh_pile_host and bh_alleles_host with vcf_host=True.  Same limits as variants; goes with
         them, the consensus, coverage, abundance, cigar and sam.  vcf_info() has the last sample's figures.
+        vcf_study = prefix (goes with vcf=True): the two calls are made at thresholds (1, 1) and filtered on the host -- OUT.vcf keeps its bytes --
+        and every sample's lines (as ranges) and lists are kept in host memory; vcf_study() then writes prefix + "study.vcf" (bh_vcfstudy.c:
+        a record wherever one sample's OUT.vcf has one, DP:AD of every sample at every record with no threshold applied, `.` for a sample that
+        failed alone) from ONE bhip_site_counts call per sample on rank 0's device handle -- or bh_site_counts_host with vcf_study_host=True --
+        and returns the figures.  close() writes it if vcf_study() was not called, unless the session ended on an error.
         taxa = prefix (needs taxonomy=): every reported sample gets a column of the taxon tables (bh_taxa.c: every read goes to the deepest
         taxonomy node that holds at least taxa_agree permille, 501 .. 1000, of the references it was placed on -- 1000: their lowest common
         ancestor), reduced on rank 0's device handle -- or by bh_taxa_host with taxa_host=True; with abundance= its counts are rolled up the
         tree as well.  close() writes prefix + "taxa.txt", "taxa_L<k>.txt" and "taxa_abundance_L<k>.txt" unless the session ended on an
         error; taxa() returns names, depths and the integer columns.  Not with mates, cluster or chimeras."""
+        if vcf_study is not None and not vcf:
+            raise ValueError("vcf_study goes with vcf=True")
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
         self._mates_join = mates_join
         self.cov, self.em, self.pile, self.cluster, self.chimera = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -1183,6 +1219,7 @@ class Session:
         self.cov_aborted = False
         self.cons = C.c_void_p()
         self.vcf = C.c_void_p()
+        self.vcfstudy = C.c_void_p()
         if coverage is not None and (rank == 0 or len(devs) > 1):      # (in a job of processes the lines exist only where rank 0 reports)
             _chk(lib().bh_cov_open(C.byref(db.c), coverage.encode(), coverage_lengths.encode() if coverage_lengths else None, int(coverage_pad), C.byref(self.cov)))
             if coverage_tap is not None:
@@ -1274,6 +1311,11 @@ class Session:
                 self._vcf_refs = BhPileRefs(C.cast(db.c.packed, C.c_void_p), C.cast(db.c.clumpLen, C.c_void_p), db.c.numRclumps, db.c.totR)
                 ctx = C.cast(C.pointer(self._vcf_refs), C.c_void_p)
                 lib().bh_vcf_set_solver(self.vcf, C.cast(lib().bh_pile_host, C.c_void_p), ctx, C.cast(lib().bh_alleles_host, C.c_void_p), ctx)
+        if vcf_study is not None:
+            _chk(lib().bh_vcfstudy_open(str(vcf_study).encode(), C.byref(self.vcfstudy)))
+            if vcf_study_host:
+                lib().bh_vcfstudy_set_solver(self.vcfstudy, C.cast(lib().bh_site_counts_host, C.c_void_p), None)
+            lib().bh_vcf_set_study(self.vcf, self.vcfstudy)
         if (sam_unmapped or sam_lengths) and not sam:
             raise ValueError("sam_unmapped and sam_lengths go with sam=True")
         if sam:
@@ -1303,7 +1345,7 @@ class Session:
             if self.h:
                 lib().bh_session_close(self.h)
                 self.h = C.c_void_p()
-            for name, close in (("sam", lib().bh_sam_close), ("taxa_obj", lib().bh_taxa_close), ("vcf", lib().bh_vcf_close), ("cons", lib().bh_consensus_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
+            for name, close in (("sam", lib().bh_sam_close), ("taxa_obj", lib().bh_taxa_close), ("vcfstudy", lib().bh_vcfstudy_close), ("vcf", lib().bh_vcf_close), ("cons", lib().bh_consensus_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
                 if getattr(self, name):
                     close(getattr(self, name))
                     setattr(self, name, C.c_void_p())
@@ -1522,6 +1564,22 @@ class Session:
         lib().bh_vcf_last_info(self.vcf, info.ctypes.data)
         return dict(zip(VCF_INFO, (int(x) for x in info)))
 
+    def vcf_study(self):
+        """writes prefix + "study.vcf" from the samples reported so far (once: the kept lists are released) and returns the figures: samples
+        (done), failed, snv, del, ins (records), cells, host_bytes (kept), device_us"""
+        if not self.vcfstudy:
+            raise HostError("the session has no study VCF")
+        if lib().bh_session_ended(self.h):
+            raise HostError("the session ended on an error: no study VCF is written")
+        _chk(lib().bh_vcfstudy_write(self.vcfstudy, self.vcf, self.ranks[0].hh))
+        self._vcfstudy_written = True
+        return self.vcf_study_info()
+
+    def vcf_study_info(self):
+        info = np.zeros(8, np.uint64)
+        lib().bh_vcfstudy_last_info(self.vcfstudy, info.ctypes.data)
+        return dict(zip(VCF_STUDY_INFO, (int(x) for x in info)))
+
     def sam_info(self):
         """the last written sample's figures: records, unmapped, md_bytes, device_us"""
         info = np.zeros(4, np.uint64)
@@ -1568,6 +1626,11 @@ class Session:
                     err = lib().bh_last_error().decode("utf-8", "replace")
                 lib().bh_consensus_close(self.cons)
                 self.cons = C.c_void_p()
+            if self.vcfstudy:     # (before the handles go: the counts are taken on rank 0's)
+                if not getattr(self, "_vcfstudy_written", False) and not lib().bh_session_ended(self.h) and not self.cov_aborted and lib().bh_vcfstudy_write(self.vcfstudy, self.vcf, self.ranks[0].hh):
+                    err = lib().bh_last_error().decode("utf-8", "replace")
+                lib().bh_vcfstudy_close(self.vcfstudy)
+                self.vcfstudy = C.c_void_p()
             if self.vcf:          # (every sample's file was renamed or removed when the sample ended)
                 lib().bh_vcf_close(self.vcf)
                 self.vcf = C.c_void_p()

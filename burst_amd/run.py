@@ -234,8 +234,9 @@ def main(argv=None):
     ap.add_argument("--vcf-min-alt", metavar="N", help="not available here: goes with burst_hip --vcf")
     ap.add_argument("--vcf-reads", metavar="all|unique", help="not available here: goes with burst_hip --vcf")
     ap.add_argument("--vcf-lengths", metavar="FILE", help="not available here: goes with burst_hip --vcf")
+    ap.add_argument("--vcf-study", metavar="PREFIX", help="not available here: goes with burst_hip --vcf")
     args = ap.parse_args(argv)
-    if args.vcf or args.vcf_min_depth or args.vcf_min_alt or args.vcf_reads or args.vcf_lengths:      # (exit code 1, as burst_hip refuses what it cannot do)
+    if args.vcf or args.vcf_min_depth or args.vcf_min_alt or args.vcf_reads or args.vcf_lengths or args.vcf_study:      # (exit code 1, as burst_hip refuses what it cannot do)
         print("ERROR: --vcf is not available in python -m burst_amd.run: use burst_hip --vcf (one process, --gpus N with the host gather)", flush=True)
         return 1
     if args.consensus or args.consensus_min_depth or args.consensus_min_breadth or args.consensus_reads or args.consensus_lengths:      # (exit code 1, as burst_hip refuses what it cannot do)

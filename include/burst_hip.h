@@ -543,6 +543,48 @@ BHIP_API int bhip_alleles_run(void *handle, const uint8_t *q_codes, const uint64
                               uint8_t *codes, uint64_t code_cap, uint64_t *n_codes, uint64_t info[8]);
 BHIP_API int bhip_alleles_info(void *handle, uint64_t info[8]);
 
+/* Site counts: one sample's counts at records the caller names, the primitive of the study VCF (burst_hip --vcf-study; no reference
+ * counterpart).  All integer arithmetic, a pure function of the samples' printed lines, bit-exact on any machine.
+ * STUDY VCF.  Lines, observations, classes, Depth, the counts A C G T Del Other, Ref, allele runs, allele words and all / unique are exactly
+ * those of "Variant sites" and "Indel alleles" above.  For sample s write Depth_s(h,p), n_s[b](h,p) and count_s(h,p,word): all 0 where the
+ * sample observes nothing.  D = --vcf-min-depth, A = --vcf-min-alt.
+ *   SNV record at (h,p)         exists when Ref(h,p) is A/C/G/T and some sample has Depth_s >= D and, for a base b != Ref, n_s[b] >= A.  ALT is
+ *                               the set of bases b != Ref for which some sample satisfies both, in the order A C G T.
+ *   Allele record (h,p,word)    exists when some sample has Depth_s(h,p) >= D and count_s(h,p,word) >= A.  REF and ALT letters as in OUT.vcf;
+ *                               a Del's deleted letters come from a reporting sample (all agree: the database is the same).
+ *   The study file has a record exactly when at least one sample's OUT.vcf has it; an SNV's ALT is the union of the reporting samples' ALTs.
+ *   SAMPLE FIELDS (FORMAT DP:AD) for every sample at every record, with no threshold applied: SNV Depth_s:n_s[Ref],n_s[alt1],... (a
+ *                               sample's plain observations count as Ref); indel Depth_s(anchor):Depth_s-count_s,count_s; a sample with no
+ *                               read at the record prints explicit zeros (0:0,0); a sample that failed alone prints `.`.
+ *   INFO DP=<sum of Depth_s>;NS=<samples with Depth_s >= 1>.  Records in header-number order, then by POS; at one POS the SNV first, then the
+ *   alleles by word: the order of OUT.vcf.  No pooled call (a record that passes only on counts summed over samples), no genotypes.
+ * THE PRIMITIVE.  bhip_pile_run and bhip_alleles_run at thresholds (1, 1) return everything a sample observes that is not plain; what is
+ * missing is the depth of a sample where it observed nothing unusual.  A RANGE is a line of the sample: it covers [pos, pos + span - 1] of
+ * `header` and stands for w reads; span = the '=' + X + D of its path and may be 0 (it then contributes nothing).  A RECORD with allele 0 is
+ * a site record (ref in 1..4), any other is an allele record with that word.  cells[i], each standing alone (records need not be sorted or
+ * distinct):
+ *   depth   the summed w of the ranges that hold (header, pos)
+ *   site    n[0..3] = those of the entry of `sites` at (header, pos); without one n[ref - 1] = depth, the others 0; count = 0
+ *   allele  count = that of the entry of `alleles` with (header, pos, allele), or 0; n = 0
+ * `sites`: the sample's bhip_pile_run(1, 1) result, ascending (header, pos); `alleles`: its bhip_alleles_run(1, 1) result in its order.
+ * The cost follows ranges + records (csrc/bhip_sitecounts.hip): starts and one-past-ends sorted with running weight
+ * sums, per record two binary searches for the depth (the stabbing count of the variant sites) and one into `sites` or, by the 128-bit key
+ * (header << 32 | pos, allele), into `alleles`.  64-bit integer sums and exact look-ups: no order of threads or ranges changes a byte.
+ * n_records == 0: nothing is launched.  n_ranges == 0: every depth is 0 and nothing is launched.  BHIP_E_ARG with a text, before any device
+ * memory is touched and with the handle staying usable, for a range with pos == 0, w == 0 or pos + span > 2^32 - 1, summed weights beyond
+ * 2^31 - 1, `sites` not strictly ascending, `alleles` not strictly ascending by (header, pos, allele), a record with pos == 0, a site
+ * record with ref outside 1..4, and any count of 2^32 or more.
+ * info (may be NULL; bhip_site_counts_info returns that of the last call on the handle): [0] ranges, [1] records, [2] device microseconds
+ * (HIP events around everything launched), [3] peak device bytes of the scratch buffers (the handle keeps them; bhip_destroy frees them),
+ * [4..7] 0. */
+typedef struct BhipCountRange  { uint32_t header, pos, span, w; } BhipCountRange;
+typedef struct BhipCountRecord { uint32_t header, pos; uint64_t allele; uint32_t ref, pad; } BhipCountRecord;
+typedef struct BhipCountCell   { uint32_t depth, n[4], count; } BhipCountCell;
+BHIP_API int bhip_site_counts(void *handle, const BhipCountRange *ranges, uint64_t n_ranges, const BhipPileSite *sites, uint64_t n_sites,
+                              const BhipAllele *alleles, uint64_t n_alleles, const BhipCountRecord *records, uint64_t n_records,
+                              BhipCountCell *cells, uint64_t info[8]);
+BHIP_API int bhip_site_counts_info(void *handle, uint64_t info[8]);
+
 /* Clustering: greedy centroid clusters of the reads of a query file from the lines it prints against itself (burst_hip --cluster; no
  * reference counterpart: its README lists clustering "as an output mode" as planned and names the recipe -- the queries as their own
  * references in FORAGE, then clusters picked from that hit graph).  All of it is integer arithmetic, bit-exact on any machine.
