@@ -49,6 +49,7 @@ EXPORTS = ["bhip_init", "bhip_stage_queries", "bhip_align_staged", "bhip_align_b
            "bhip_build_accelerator_shared", "bhip_comm_share", "bhip_team_create", "bhip_team_destroy", "bhip_team_share", "bhip_device_copy", "bhip_dna_marks",
            "bhip_cov_begin", "bhip_cov_add", "bhip_cov_sample_stats", "bhip_cov_dataset_stats", "bhip_cov_info", "bhip_cov_end", "bhip_lane_extents",
            "bhip_trace_paths", "bhip_paths_info", "bhip_mates_join", "bhip_mates_info", "bhip_em_run", "bhip_taxa_run", "bhip_taxa_rollup", "bhip_pile_run", "bhip_consensus_run", "bhip_consensus_info",
+           "bhip_consensus_pairs", "bhip_consensus_pairs_info",
            "bhip_alleles_run", "bhip_alleles_info", "bhip_site_counts", "bhip_site_counts_info",
            "bhip_cluster_run", "bhip_cluster_info", "bhip_chimera_run", "bhip_chimera_info", "bhip_md_tags"]
 
@@ -94,6 +95,21 @@ CONS_SEG_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("len", "<u4"), ("
                            ("ins_major", "<u4"), ("pad", "<u4"), ("off", "<u8")])
 assert CONS_SEG_DTYPE.itemsize == 48
 CONS_INFO = ("events", "candidates", "segments", "covered", "device_us", "peak_bytes")
+# bhip_consensus_pairs: BhipPairSeg, 24 bytes: a segment of a sample's consensus row on a header and where its letters start; BhipPair, 24 bytes:
+# samples a < b on a header, the positions comparable in both rows and those of them with equal letters
+PAIR_SEG_DTYPE = np.dtype([("sample", "<u4"), ("header", "<u4"), ("pos", "<u4"), ("len", "<u4"), ("off", "<u8")])
+PAIR_DTYPE = np.dtype([("header", "<u4"), ("a", "<u4"), ("b", "<u4"), ("pad", "<u4"), ("compared", "<u4"), ("same", "<u4")])
+assert PAIR_SEG_DTYPE.itemsize == 24 and PAIR_DTYPE.itemsize == 24
+CONS_PAIRS_INFO = ("segments", "headers", "union_positions", "examined", "pairs", "device_us", "peak_bytes")
+
+
+def pair_arrays(segs, letters):
+    """the two inputs of consensus_pairs as contiguous arrays (segs: PAIR_SEG_DTYPE or rows of it; letters: bytes, str or uint8)"""
+    segs = np.zeros(0, PAIR_SEG_DTYPE) if segs is None or len(segs) == 0 else np.ascontiguousarray(segs, dtype=PAIR_SEG_DTYPE)
+    if isinstance(letters, str):
+        letters = letters.encode()
+    letters = np.frombuffer(letters, np.uint8) if isinstance(letters, (bytes, bytearray)) else np.ascontiguousarray(letters, dtype=np.uint8)
+    return segs, letters
 # BhipAllele, 40 bytes: an indel allele behind the anchor (header, pos) (bhip_alleles_run).  allele: Del(n) = n; Ins = n << 60 | c1 << 56 | ...
 ALLELE_DTYPE = np.dtype([("header", "<u4"), ("pos", "<u4"), ("allele", "<u8"), ("ref", "<u4"), ("depth", "<u4"), ("count", "<u4"), ("pad", "<u4"), ("code_off", "<u8")])
 assert ALLELE_DTYPE.itemsize == 40
@@ -294,6 +310,10 @@ def _load():
     lib.bhip_consensus_run.restype = i32
     lib.bhip_consensus_info.argtypes = [vp, vp]
     lib.bhip_consensus_info.restype = i32
+    lib.bhip_consensus_pairs.argtypes = [vp, u32, vp, u64, vp, u64, u32, vp, u64, C.POINTER(u64), vp]
+    lib.bhip_consensus_pairs.restype = i32
+    lib.bhip_consensus_pairs_info.argtypes = [vp, vp]
+    lib.bhip_consensus_pairs_info.restype = i32
     lib.bhip_alleles_run.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, u32, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), vp]
     lib.bhip_alleles_run.restype = i32
     lib.bhip_alleles_info.argtypes = [vp, vp]
@@ -630,6 +650,31 @@ class Device:
             seg_cap, letter_cap = max(seg_cap, ns.value), max(letter_cap, nl.value)
         _chk(rc)
         return segs[:ns.value], letters[:nl.value].tobytes()
+
+    def consensus_pairs(self, n_samples, segs, letters, min_compared=1, pair_cap=None, retry=True):
+        """every two samples' consensus rows compared per header (bhip_consensus_pairs).  segs: PAIR_SEG_DTYPE, strictly ascending (sample,
+        header, pos); letters: the bytes the segments' offsets point into.  Returns the pairs (PAIR_DTYPE, ascending header, a, b) with
+        compared >= min_compared; consensus_pairs_info() has the call's figures.  pair_cap: room offered at first; a capacity answer is
+        retried once with the number the call asked for -- not with retry=False: the capacity answer is raised, pairs_wanted holds the
+        number and pairs_buffer the untouched room"""
+        segs, letters = pair_arrays(segs, letters)
+        pair_cap = 1024 if pair_cap is None else int(pair_cap)
+        for attempt in range(2):
+            pairs, n, info = np.zeros(max(pair_cap, 1), PAIR_DTYPE), C.c_uint64(0), np.zeros(8, np.uint64)
+            rc = lib().bhip_consensus_pairs(self._h, int(n_samples), _ptr(segs), len(segs), _ptr(letters), len(letters), int(min_compared), _ptr(pairs), pair_cap, C.byref(n), _ptr(info))
+            self.pairs_wanted, self.pairs_buffer = int(n.value), pairs
+            if rc != BHIP_E_CAPACITY or attempt or not retry:
+                break
+            pair_cap = int(n.value)
+        _chk(rc)
+        return pairs[:n.value]
+
+    def consensus_pairs_info(self):
+        """the last consensus_pairs' figures (bhip_consensus_pairs_info): segments, headers (with two samples or more), union_positions,
+        examined, pairs, device_us, peak_bytes"""
+        info = np.zeros(8, np.uint64)
+        _chk(lib().bhip_consensus_pairs_info(self._h, _ptr(info)))
+        return dict(zip(CONS_PAIRS_INFO, (int(x) for x in info)))
 
     def consensus_info(self):
         """the last consensus_run's figures (bhip_consensus_info): events, candidates, segments, covered, device_us, peak_bytes"""

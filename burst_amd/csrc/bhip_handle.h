@@ -457,6 +457,7 @@ struct Handle {
 	void *cons = nullptr;         // scratch buffers and figures of bhip_consensus_run (bhip_consensus.hip), beside those of Handle::pile, which it shares
 	void *alleles = nullptr;      // scratch buffers and figures of bhip_alleles_run (bhip_alleles.hip), beside those of Handle::pile, which it shares
 	void *sitecounts = nullptr;   // scratch buffers, events and figures of bhip_site_counts (bhip_sitecounts.hip), made by the first call that launches
+	void *conspairs = nullptr;    // scratch buffers, events and figures of bhip_consensus_pairs (bhip_conspairs.hip), made by the first call that launches
 	void *taxa = nullptr;         // scratch buffers and events of bhip_taxa_run and bhip_taxa_rollup (bhip_taxa.hip), made by the first call that launches
 	void *cluster = nullptr;      // scratch buffers and events of bhip_cluster_run (bhip_cluster.hip), made by the first call that launches
 	uint64_t cluster_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // bhip_cluster_info: the figures of the last bhip_cluster_run
@@ -465,6 +466,7 @@ struct Handle {
 	void *md = nullptr;           // scratch buffers and events of bhip_md_tags (bhip_md.hip), made by the first call that launches
 	int opt_em_weak_hash = 0;     // 1 = candidate sets hashed to two bits: the element-by-element comparison decides which groups merge (tests)
 	int opt_em_thread_max = 0, opt_em_wave_max = 0;   // largest candidate set a thread / a wave takes in the abundance step (0 = EM_THREAD_MAX, EM_WAVE_MAX of bhip_em.hip)
+	long long opt_conspairs_bytes = 1ll << 30;   // bytes the code planes of bhip_consensus_pairs may take in one launch (a stated policy; bhip_conspairs.hip)
 	long long opt_cov_event_cap = 0;   // bytes the coverage event sets may take before they are compacted (0 = a fifth of the memory free at the first bhip_cov_add)
 };
 
@@ -487,6 +489,7 @@ void bhip_pile_release(Handle *h);                                           // 
 void bhip_consensus_release(Handle *h);                                      // bhip_consensus.hip
 void bhip_alleles_release(Handle *h);                                        // bhip_alleles.hip
 void bhip_sitecounts_release(Handle *h);                                     // bhip_sitecounts.hip
+void bhip_conspairs_release(Handle *h);                                      // bhip_conspairs.hip
 void bhip_cluster_release(Handle *h);                                        // bhip_cluster.hip
 void bhip_taxa_release(Handle *h);                                           // bhip_taxa.hip
 void bhip_chimera_release(Handle *h);                                        // bhip_chimera.hip

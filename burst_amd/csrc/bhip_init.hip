@@ -77,6 +77,7 @@ extern "C" void bhip_destroy(void *handle) {
 	bhip_consensus_release(h);
 	bhip_alleles_release(h);
 	bhip_sitecounts_release(h);
+	bhip_conspairs_release(h);
 	bhip_pile_release(h);
 	bhip_cluster_release(h);
 	bhip_taxa_release(h);
@@ -256,6 +257,7 @@ extern "C" int bhip_set_option(void *handle, const char *name, long long value) 
 	if (!strcmp(name, "prefilter_bytes")) { h->opt_pf_bytes = value != 0; return BHIP_OK; }
 	if (!strcmp(name, "prefilter_rb")) { if (value != 0 && (value < 2 || value > 4)) return fail(BHIP_E_ARG, "prefilter_rb must be 0, 2, 3 or 4"); h->opt_pf_rb = (int)value; return BHIP_OK; }
 	if (!strcmp(name, "cov_event_cap")) { if (value < 0) return fail(BHIP_E_ARG, "cov_event_cap must be >= 0 bytes (0 = a fifth of the free memory)"); h->opt_cov_event_cap = value; return BHIP_OK; }
+	if (!strcmp(name, "conspairs_bytes")) { if (value < 1) return fail(BHIP_E_ARG, "conspairs_bytes must be >= 1 byte"); h->opt_conspairs_bytes = value; return BHIP_OK; }
 	if (!strcmp(name, "em_weak_hash")) { h->opt_em_weak_hash = value != 0; return BHIP_OK; }
 	if (!strcmp(name, "em_thread_max")) { if (value < 0 || value > 64) return fail(BHIP_E_ARG, "em_thread_max must be 0 (built in) .. 64"); h->opt_em_thread_max = (int)value; return BHIP_OK; }
 	if (!strcmp(name, "em_wave_max")) { if (value < 0 || value > (1 << 24)) return fail(BHIP_E_ARG, "em_wave_max must be 0 (built in) .. 2^24"); h->opt_em_wave_max = (int)value; return BHIP_OK; }

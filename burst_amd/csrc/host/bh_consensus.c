@@ -26,6 +26,8 @@ struct BhCons {
 	/* the rows so far */
 	BhConsRow *rows; uint64_t nRows, capRows;
 	char **names; uint32_t nSamples;
+	uint8_t *failed;                /* per sample: it failed alone (bh_consensus_sample_failed) */
+	BhConsPairs *pairs; const BhConsPairsHooks *ph;      /* bh_consensus_set_pairs: NULL, or the collector every written record's segments and letters are handed to, and its entry points (bh_conspairs.c: this file links without it) */
 	uint64_t info[8], infoLines, infoRecords; int have_info;      /* of the last sample that was solved */
 };
 
@@ -237,7 +239,19 @@ int bh_consensus_open(const BhDb *db, const char *prefix, const char *lengths_fi
 }
 
 void bh_consensus_set_solver(BhCons *cn, bh_cons_solver_fn fn, void *ctx) { if (cn) { cn->fn = fn; cn->ctx = ctx; } }
-void bh_consensus_abort(BhCons *cn) { if (cn && !cn->dead) cn->dead = BH_E_DEVICE; }
+void bh_consensus_abort(BhCons *cn) { if (cn && !cn->dead) { cn->dead = BH_E_DEVICE; if (cn->pairs) cn->ph->abort(cn->pairs); } }
+void bh_consensus_set_pairs(BhCons *cn, BhConsPairs *pairs, const BhConsPairsHooks *hooks) { if (cn) { cn->pairs = hooks ? pairs : NULL; cn->ph = hooks; } }
+
+/* the end of the run with a pairs collector attached, before bh_consensus_write: ONE solver call over the rows of every written record on
+ * the reporting rank's handle, and the three files under their temporary names */
+int bh_consensus_pairs(BhCons *cn, void *hh) {
+	if (!cn || !cn->pairs) return bh_set_error(BH_E_USAGE, "bh_consensus_pairs: no consensus with a pairs collector");
+	if (cn->dead) return bh_set_error(cn->dead, "the consensus was ended by an earlier error: no file is written");
+	if (!cn->fa || !cn->tx || cn->ph->written(cn->pairs)) return bh_set_error(BH_E_USAGE, "bh_consensus_pairs: the files have been written");
+	const int rc = cn->ph->write(cn->pairs, hh, cn->nSamples, cn->names, cn->failed, cn->head, cn->byRank, cn->length, cn->nH);
+	if (rc) cn->dead = rc;
+	return rc;
+}
 
 static int die(BhCons *cn, int rc) { cn->dead = rc; return rc; }
 static void drop_lines(BhCons *cn) { cn->nLines = cn->nOps = cn->nPrinted = 0; }
@@ -245,8 +259,11 @@ static void drop_lines(BhCons *cn) { cn->nLines = cn->nOps = cn->nPrinted = 0; }
 static int new_sample(BhCons *cn, const char *out_path) {
 	char **nn = realloc(cn->names, ((size_t)cn->nSamples + 1) * sizeof(*nn));
 	if (nn) cn->names = nn;
+	uint8_t *nf = realloc(cn->failed, (size_t)cn->nSamples + 1);
+	if (nf) cn->failed = nf;
 	char *nm = sample_name(out_path ? out_path : "sample");
-	if (!nn || !nm) { free(nm); return bh_set_error(BH_E_OOM, "OOM:consensus"); }
+	if (!nn || !nf || !nm) { free(nm); return bh_set_error(BH_E_OOM, "OOM:consensus"); }
+	cn->failed[cn->nSamples] = 0;
 	cn->names[cn->nSamples++] = nm;
 	return BH_OK;
 }
@@ -308,7 +325,7 @@ int bh_consensus_sample_failed(BhCons *cn, const char *out_path) {
 	if (!cn) return BH_OK;
 	drop_lines(cn);
 	const int rc = new_sample(cn, out_path);
-	if (!rc) printf(" --> consensus: sample '%s' failed alone: it has no rows\n", cn->names[cn->nSamples - 1]);
+	if (!rc) { cn->failed[cn->nSamples - 1] = 1; printf(" --> consensus: sample '%s' failed alone: it has no rows\n", cn->names[cn->nSamples - 1]); }
 	return rc;
 }
 
@@ -380,6 +397,7 @@ int bh_consensus_sample(BhCons *cn, void *hh, const char *out_path, const uint8_
 			put_n(cn->fa, L - p);
 			fputc('\n', cn->fa);
 			++records;
+			if (cn->pairs && (rc = cn->ph->add(cn->pairs, sample, segs[a].header, segs + a, b - a, letters))) { free(segs); free(letters); return die(cn, rc); }      /* (kept: the row takes part) */
 		}
 		fprintf(cn->tx, "%s\t%s\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", cn->head[h], cn->names[sample], L, row.covered, row.called, row.same, row.subst, row.del, row.ambig,
 		        row.ins_major, row.record);
@@ -411,12 +429,14 @@ int bh_consensus_write(BhCons *cn) {
 	if (!cn) return bh_set_error(BH_E_USAGE, "bh_consensus_write: no consensus object");
 	if (cn->dead) return bh_set_error(cn->dead, "the consensus was ended by an earlier error: no file is written");
 	if (!cn->fa || !cn->tx) return bh_set_error(BH_E_USAGE, "bh_consensus_write: the files have been written");
+	if (cn->pairs && !cn->ph->written(cn->pairs)) return bh_set_error(BH_E_USAGE, "bh_consensus_write: a pairs collector is attached and bh_consensus_pairs has not run");
 	FILE *fa = cn->fa, *tx = cn->tx; cn->fa = cn->tx = NULL;
 	int rc = BH_OK;
 	const int bad_fa = ferror(fa) | fclose(fa), bad_tx = ferror(tx) | fclose(tx);
 	if (bad_fa || bad_tx) rc = bh_set_error(BH_E_IO, "ERROR: write failed: %s", bad_fa ? cn->tmpFa : cn->tmpTx);
 	else if (rename(cn->tmpFa, cn->finFa)) rc = bh_set_error(BH_E_IO, "ERROR: Cannot rename %s to %s", cn->tmpFa, cn->finFa);
 	else if (rename(cn->tmpTx, cn->finTx)) { rc = bh_set_error(BH_E_IO, "ERROR: Cannot rename %s to %s", cn->tmpTx, cn->finTx); (void)unlink(cn->finFa); }
+	if (!rc && cn->pairs && (rc = cn->ph->commit(cn->pairs))) { (void)unlink(cn->finFa); (void)unlink(cn->finTx); }      /* (all five, or none) */
 	if (rc) { (void)unlink(cn->tmpFa); (void)unlink(cn->tmpTx); cn->dead = rc; }
 	return rc;
 }
@@ -441,6 +461,6 @@ void bh_consensus_close(BhCons *cn) {
 	for (uint32_t c = 0; c < cn->nSamples; ++c) free(cn->names[c]);
 	if (cn->head) for (uint32_t h = 0; h < cn->nH; ++h) free(cn->head[h]);
 	free(cn->names); free(cn->head); free(cn->rank); free(cn->byRank); free(cn->length); free(cn->tmpFa); free(cn->finFa); free(cn->tmpTx); free(cn->finTx);
-	free(cn->lines); free(cn->ops); free(cn->rows);
+	free(cn->lines); free(cn->ops); free(cn->rows); free(cn->failed);
 	free(cn);
 }

@@ -149,6 +149,15 @@ int bh_session_set_consensus(BhSession *s, BhCons *cons) {
 	s->cons = cons;
 	return BH_OK;
 }
+
+/* the end of a run whose consensus has a pairs collector, before the caller's bh_consensus_write: the one solver call on the reporting
+ * rank's handle and the three files under their temporary names */
+int bh_session_consensus_pairs(BhSession *s) {
+	if (!s || !s->cons) return bh_set_error(BH_E_USAGE, "bh_session_consensus_pairs: no session with a consensus");
+	if (s->dead) return bh_set_error(s->dead, "the session was ended by an earlier error (code %d): no file is written", s->dead);
+	if (s->i0 < 0) return bh_set_error(BH_E_USAGE, "bh_session_consensus_pairs: this process holds no reporting rank");
+	return bh_consensus_pairs(s->cons, s->ranks[s->i0].hh);
+}
 int bh_session_set_vcf(BhSession *s, BhVcf *vcf) {
 	if (!s) return bh_set_error(BH_E_USAGE, "bh_session_set_vcf: no session");
 	if (vcf && s->o.shard_db > 1) return bh_set_error(BH_E_USAGE, "ERROR: --vcf traces the paths on rank 0's handle, which must hold the whole database: it does not go with database shards");

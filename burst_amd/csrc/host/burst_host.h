@@ -566,6 +566,55 @@ int  bh_consensus_host(void *refs, const uint8_t *q_codes, const uint64_t *q_off
                        const uint32_t *ops, uint64_t n_ops, uint32_t min_depth, BhipConsSeg *segs, uint64_t seg_cap, uint64_t *n_segs,
                        char *letters, uint64_t letter_cap, uint64_t *n_letters, uint64_t info[8]);
 
+/* ---- sample-to-sample identity of the consensus rows per reference (bh_conspairs.c; burst_hip --consensus PREFIX --consensus-pairs) ----
+ * The definition is include/burst_hip.h "Consensus pairs" (DESIGN.md section 7l), a pure function of the written PREFIXconsensus.fa.  With a
+ * collector attached (bh_conspairs_attach) bh_consensus_sample hands over the segments and letters of every (sample, header) whose record
+ * it writes; the collector keeps them in host memory (24 bytes per segment, a byte per covered position; no spilling).  At the end of the
+ * run bh_consensus_pairs makes ONE solver call on the reporting rank's handle and writes PREFIXconsensus_pairs.txt, _identity.txt and
+ * _compared.txt under temporary names; bh_consensus_write, which refuses to run before it, renames all five files together.  A sample that
+ * failed alone reads NA in its whole row and column of both matrices.  Two samples of one name are BH_E_USAGE that names both outputs
+ * (bh_conspairs_check_names: the command line asks before a device is touched; names sorted, neighbours compared).  A record covered
+ * through position 2^32 - 1 is BH_E_USAGE when it is handed over (the primitive's keys end one position earlier).  The matrices are
+ * summed from the pair list (a sorted list of the cells that have a pair row), never as samples^2 sums.  Any error is final: no file is written, and
+ * bh_conspairs_close removes the temporary files.
+ *   bh_conspairs_check_min    BH_E_USAGE with the command line's text for --consensus-pairs-min outside 1 .. 2^31 - 1
+ *   bh_conspairs_set_solver   another solver (tests): bhip_consensus_pairs' arguments behind ctx, return codes in this file's terms; NULL: the device
+ *   bh_conspairs_print_info   the `ConsensusPairs:` line; bh_conspairs_last_info: [0] samples done [1] failed [2] participating records [3] headers
+ *                             with two or more [4] union positions [5] pairs examined [6] pairs written [7] host bytes kept; the device microseconds
+ *   bh_consensus_pairs_host   the primitive in plain sequential C, a solver (ctx unused): a dense row per (sample, header), a double loop over the samples
+ * bh_consensus.c reaches the collector through BhConsPairsHooks alone, so that it links without this file. */
+typedef struct BhConsPairs BhConsPairs;
+typedef int (*bh_conspairs_solver_fn)(void *ctx, uint32_t n_samples, const BhipPairSeg *segs, uint64_t n_segs, const char *letters, uint64_t n_letters, uint32_t min_compared,
+                                      BhipPair *pairs, uint64_t pair_cap, uint64_t *n_pairs, uint64_t info[8]);
+typedef struct BhConsPairsHooks {
+	int  (*add)(BhConsPairs *pairs, uint32_t sample, uint32_t header, const BhipConsSeg *segs, uint64_t n, const char *letters);
+	int  (*write)(BhConsPairs *pairs, void *hip_handle, uint32_t n_samples, char *const *names, const uint8_t *failed, char *const *head, const uint32_t *by_rank,
+	              const uint32_t *length, uint32_t n_headers);
+	int  (*written)(const BhConsPairs *pairs);
+	int  (*commit)(BhConsPairs *pairs);
+	void (*abort)(BhConsPairs *pairs);
+} BhConsPairsHooks;
+int  bh_conspairs_check_min(uint64_t min_compared);
+int  bh_conspairs_check_names(const char *const *out_paths, uint64_t n);
+int  bh_conspairs_open(const char *prefix, uint32_t min_compared, BhConsPairs **pairs);
+void bh_conspairs_set_solver(BhConsPairs *pairs, bh_conspairs_solver_fn fn, void *ctx);
+void bh_conspairs_attach(BhConsPairs *pairs, BhCons *cons);
+int  bh_conspairs_add(BhConsPairs *pairs, uint32_t sample, uint32_t header, const BhipConsSeg *segs, uint64_t n, const char *letters);
+int  bh_conspairs_write(BhConsPairs *pairs, void *hip_handle, uint32_t n_samples, char *const *names, const uint8_t *failed, char *const *head, const uint32_t *by_rank,
+                        const uint32_t *length, uint32_t n_headers);
+int  bh_conspairs_written(const BhConsPairs *pairs);
+int  bh_conspairs_commit(BhConsPairs *pairs);
+void bh_conspairs_abort(BhConsPairs *pairs);
+void bh_conspairs_print_info(BhConsPairs *pairs);
+void bh_conspairs_last_info(const BhConsPairs *pairs, uint64_t info[8], uint64_t *device_us);
+void bh_conspairs_close(BhConsPairs *pairs);
+int  bh_consensus_pairs_host(void *unused, uint32_t n_samples, const BhipPairSeg *segs, uint64_t n_segs, const char *letters, uint64_t n_letters, uint32_t min_compared,
+                             BhipPair *pairs, uint64_t pair_cap, uint64_t *n_pairs, uint64_t info[8]);
+/* bh_consensus.c's side: the collector and its entry points (NULL: none; the caller opens and closes it); the end of the run, before
+ * bh_consensus_write */
+void bh_consensus_set_pairs(BhCons *cons, BhConsPairs *pairs, const BhConsPairsHooks *hooks);
+int  bh_consensus_pairs(BhCons *cons, void *hip_handle);
+
 /* ---- VCF output beside the .b6: SNVs and indel alleles per sample from the alignment paths (bh_vcf.c; burst_hip --vcf) ----
  * The alleles are bhip_alleles_run's (include/burst_hip.h "Indel alleles"), the SNVs a subset of bhip_pile_run's sites.  Per sample the
  * lines the tracer handed over (bh_pile.c's collector: the same lines, the same unique-read rule) go through ONE bhip_pile_run and ONE
@@ -859,6 +908,9 @@ int  bh_session_set_taxa(BhSession *s, BhTaxa *tx);
  * opens the path tracer (without the --cigar columns unless the session has them) and goes with coverage, abundance, variants and the SAM
  * writer.  Not with database shards, clusters, the chimera check or bh_session_run_mates */
 int  bh_session_set_consensus(BhSession *s, BhCons *cons);
+/* a consensus with a pairs collector (bh_conspairs_attach): when every sample has been reported and before the caller's
+ * bh_consensus_write, the one bhip_consensus_pairs call on the reporting rank's handle and the three files under temporary names */
+int  bh_session_consensus_pairs(BhSession *s);
 /* likewise NULL, or the VCF writer every reported sample is given (rank 0's process; the caller opens and closes it): OUT.vcf beside the
  * output OUT.  Goes with coverage, abundance, variants, the consensus, cigar and the SAM writer.  Not with database shards, clusters, the
  * chimera check or bh_session_run_mates */

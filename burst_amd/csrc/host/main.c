@@ -14,7 +14,8 @@
  *             [--chimera-min-seg G] [--chimera-min-gain D]      de-novo two-parent chimera check of the reads from their self-hits and the hits' paths (bh_chimera.c)
  *   ... -q / -o or --samples ... --variants PREFIX [--variants-min-depth N] [--variants-min-alt N] [--variants-reads all|unique]   variant sites per sample (bh_pile.c)
  *   ... -q / -o or --samples ... --consensus PREFIX [--consensus-min-depth N] [--consensus-min-breadth PERMILLE] [--consensus-reads all|unique] [--consensus-lengths FILE]   consensus per reference and sample (bh_consensus.c)
- *   ... --vcf --vcf-study PREFIX        PREFIXstudy.vcf: every sample's DP:AD at every record any sample's OUT.vcf has (bh_vcfstudy.c)
+ *   ... --consensus PREFIX --consensus-pairs [--consensus-pairs-min N]   PREFIXconsensus_pairs.txt, _identity.txt, _compared.txt: every two samples' consensus rows compared per reference (bh_conspairs.c)
+ *   ... --vcf --vcf-study PREFIX       PREFIXstudy.vcf: every sample's DP:AD at every record any sample's OUT.vcf has (bh_vcfstudy.c)
  *   ... -q / -o or --samples ... --vcf [--vcf-min-depth N] [--vcf-min-alt N] [--vcf-reads all|unique] [--vcf-lengths FILE]   OUT.vcf beside every .b6 output OUT: SNVs and indel alleles (bh_vcf.c)
  *   ... -q / -o or --samples ... --sam [--sam-unmapped] [--sam-lengths FILE]      OUT.sam beside every .b6 output OUT, with NM and MD tags (bh_sam.c)
  *
@@ -143,6 +144,7 @@ typedef struct {
 	int vcf; uint32_t vcf_min_depth, vcf_min_alt; int vcf_unique; const char *vcf_lengths;
 	const char *taxa_prefix; uint32_t taxa_agree;
 	const char *vcf_study;
+	int cons_pairs; uint32_t cons_pairs_min;
 } SamplesArgs;
 typedef struct { char *q, *o, *m; int line; } Sample;      /* m: the mates file of a three-field line, or NULL */
 
@@ -182,14 +184,28 @@ static int read_sample_list(const SamplesArgs *a, Sample **out, int *n_out) {
 
 /* the consensus of a run: closed on every way out, so that a run that ends on an error leaves neither file nor temporary file */
 static BhCons *g_cons;
-static void cons_atexit(void) { bh_consensus_close(g_cons); g_cons = NULL; }
-/* opened before a device is touched: the lengths table is checked against the database's headers */
-static int open_consensus(const BhDb *db, const char *prefix, const char *lengths, uint32_t min_depth, uint32_t min_breadth, int unique) {
+static BhConsPairs *g_conspairs;      /* --consensus-pairs: the collector of the consensus's written rows */
+static void close_consensus(void) { bh_consensus_close(g_cons); g_cons = NULL; bh_conspairs_close(g_conspairs); g_conspairs = NULL; }
+static void cons_atexit(void) { close_consensus(); }
+/* opened before a device is touched: the lengths table is checked against the database's headers.  pairs_min: 0, or --consensus-pairs-min */
+static int open_consensus(const BhDb *db, const char *prefix, const char *lengths, uint32_t min_depth, uint32_t min_breadth, int unique, uint32_t pairs_min) {
 	if (!db->refMap || !db->numRefHeads) { puts("ERROR: --consensus needs the reference headers of the database"); return 1; }
-	const int rc = bh_consensus_open(db, prefix, lengths, min_depth, min_breadth, unique, &g_cons);
+	int rc = bh_consensus_open(db, prefix, lengths, min_depth, min_breadth, unique, &g_cons);
+	if (!rc && pairs_min && !(rc = bh_conspairs_open(prefix, pairs_min, &g_conspairs))) bh_conspairs_attach(g_conspairs, g_cons);
+	atexit(cons_atexit);
 	if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; }
 	if (rc) { fprintf(stderr, "%s\n", bh_last_error()); return code_to_exit(rc); }
-	atexit(cons_atexit);
+	return 0;
+}
+/* the end of a run with --consensus: with --consensus-pairs the one call on rank 0's handle and the three files, then all files get their
+ * names together.  Returns 0 or the exit code */
+static int write_consensus(void *hh, const char *prefix) {
+	int rc = g_conspairs ? bh_consensus_pairs(g_cons, hh) : BH_OK;
+	if (!rc) rc = bh_consensus_write(g_cons);
+	if (rc) { if (rc == BH_E_USAGE) puts(bh_last_error()); else fprintf(stderr, "%s\n", bh_last_error()); fflush(NULL); return code_to_exit(rc); }
+	if (g_conspairs) bh_conspairs_print_info(g_conspairs);
+	printf("Consensus written: %sconsensus.fa, %sconsensus.txt\n", prefix, prefix);
+	if (g_conspairs) printf("Consensus pairs written: %sconsensus_pairs.txt, %sconsensus_identity.txt, %sconsensus_compared.txt\n", prefix, prefix, prefix);
 	return 0;
 }
 /* the VCF writer of a run: closed on every way out */
@@ -246,6 +262,15 @@ static int samples_main(SamplesArgs *a) {
 		if (!outs) { fputs("OOM:samples\n", stderr); return 3; }
 		for (int i = 0; i < nS; ++i) outs[i] = S[i].o;
 		rc = bh_vcfstudy_check_names(outs, (uint64_t)nS);
+		free(outs);
+		if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; }
+		if (rc) DIE(rc);
+	}
+	if (a->cons_pairs) {      /* (two samples of one name would share a row and a column of the matrices: refused before a device is touched) */
+		const char **outs = calloc((size_t)nS, sizeof(*outs));
+		if (!outs) { fputs("OOM:samples\n", stderr); return 3; }
+		for (int i = 0; i < nS; ++i) outs[i] = S[i].o;
+		rc = bh_conspairs_check_names(outs, (uint64_t)nS);
 		free(outs);
 		if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; }
 		if (rc) DIE(rc);
@@ -321,7 +346,7 @@ static int samples_main(SamplesArgs *a) {
 		if ((rc = bh_sam_open(&db, a->sam_lengths, a->sam_unmapped, &sam)) || (rc = bh_session_set_sam(ses, sam))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); bh_session_close(ses); return 1; } DIES(rc); }
 	}
 	if (a->cons_prefix) {
-		const int e = open_consensus(&db, a->cons_prefix, a->cons_lengths, a->cons_min_depth, a->cons_min_breadth, a->cons_unique);
+		const int e = open_consensus(&db, a->cons_prefix, a->cons_lengths, a->cons_min_depth, a->cons_min_breadth, a->cons_unique, a->cons_pairs ? a->cons_pairs_min : 0);
 		if (e) { bh_session_close(ses); return e; }
 		if ((rc = bh_session_set_consensus(ses, g_cons))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); bh_session_close(ses); return 1; } DIES(rc); }
 	}
@@ -378,10 +403,11 @@ static int samples_main(SamplesArgs *a) {
 	} else if (pile) puts("No variants table is written: the run ended on an error");
 	bh_pile_close(pile); pile = NULL;      /* (a table that was not written leaves no temporary file) */
 	if (g_cons && !bh_session_ended(ses)) {
-		if ((rc = bh_consensus_write(g_cons))) { if (rc == BH_E_USAGE) puts(bh_last_error()); else fprintf(stderr, "%s\n", bh_last_error()); if (!first_fail) first_fail = code_to_exit(rc); }
-		else printf("Consensus written: %sconsensus.fa, %sconsensus.txt\n", a->cons_prefix, a->cons_prefix);
+		tp = wall();      /* (with --consensus-pairs: one bhip_consensus_pairs call on rank 0's handle before the files get their names) */
+		const int e = write_consensus(hhs[0], a->cons_prefix);
+		if (e) { if (!first_fail) first_fail = e; } else if (g_conspairs) PHASE("consensus pairs");
 	} else if (g_cons) puts("No consensus is written: the run ended on an error");
-	bh_consensus_close(g_cons); g_cons = NULL;
+	close_consensus();
 	if (g_vcfstudy && !bh_session_ended(ses)) {      /* one bhip_site_counts call per sample on rank 0's handle, then the file */
 		tp = wall();
 		const int e = write_vcfstudy(hhs[0], a->vcf_study);
@@ -455,6 +481,12 @@ static void usage(void) {
 	puts("                  letter where it is an ambiguity code), N elsewhere.  Insertions are counted (InsMajor), not written.  A record is written when");
 	puts("                  a position was called and 1000 * Called >= --consensus-min-breadth (0) * length; the table has a row per covered (sample,");
 	puts("                  header).  --consensus-reads unique counts only reads printed on one line.  Refuses what --variants refuses");
+	puts("--consensus-pairs [--consensus-pairs-min <int>]: with --consensus, compare the written records of every reference between every two samples and");
+	puts("                  leave <prefix>consensus_pairs.txt (per reference and pair a < b in study order: Length, Compared = positions where both rows");
+	puts("                  show one of A C G T -, Same, Differ, Identity = Same / Compared; rows with Compared >= --consensus-pairs-min (1)),");
+	puts("                  <prefix>consensus_identity.txt (samples x samples, sum Same / sum Compared over the pair's rows, NA without one) and");
+	puts("                  <prefix>consensus_compared.txt (the sums Compared; the diagonal is the sample's own comparable positions).  N and ambiguity");
+	puts("                  letters are never compared.  A sample that failed alone reads NA throughout.  Two samples of one name are refused");
 	puts("--vcf [--vcf-min-depth <int>] [--vcf-min-alt <int>] [--vcf-reads all|unique] [--vcf-lengths <file>]: with -q / -o or --samples, leave OUT.vcf");
 	puts("                  beside every output OUT (VCFv4.2, one sample, no genotypes): a contig line per reference (ID and length as --sam's @SQ), and from");
 	puts("                  the alignment paths of the printed lines three kinds of records at positions with Depth >= --vcf-min-depth (4): an SNV where the");
@@ -515,6 +547,7 @@ int main(int argc, char **argv) {
 	const char *vcf_study = 0;
 	int vcf = 0, vcf_unique = 0, vcf_opts_given = 0; uint32_t vcf_min_depth = 4, vcf_min_alt = 2; const char *vcf_lengths = 0;
 	const char *cons_prefix = 0, *cons_lengths = 0; uint32_t cons_min_depth = 4, cons_min_breadth = 0; int cons_unique = 0, cons_opts_given = 0;
+	int cons_pairs = 0, cons_pairs_min_given = 0; uint32_t cons_pairs_min = 1;
 	const char *chi_prefix = 0; int chi_sizes = 0, chi_opts_given = 0; uint32_t chi_skew = 2, chi_min_seg = 16, chi_min_gain = 3;
 	BhTax taxonomy; memset(&taxonomy, 0, sizeof taxonomy);
 	BhTaxOpts txo; memset(&txo, 0, sizeof txo); txo.taxacut = 10;   /* burst.c:92 */
@@ -640,6 +673,13 @@ int main(int argc, char **argv) {
 			if (!strcmp(argv[i], "all")) cons_unique = 0; else if (!strcmp(argv[i], "unique")) cons_unique = 1; else { puts("ERROR: --consensus-reads all|unique"); return 1; }
 		}
 		else if (!strcmp(a, "--consensus-lengths")) { NEEDARG("--consensus-lengths"); cons_lengths = argv[i]; cons_opts_given = 1; }
+		else if (!strcmp(a, "--consensus-pairs")) cons_pairs = 1;
+		else if (!strcmp(a, "--consensus-pairs-min")) {
+			NEEDARG("--consensus-pairs-min");
+			char *end = NULL; const unsigned long long v = strtoull(argv[i], &end, 10);
+			if (!*argv[i] || *end || bh_conspairs_check_min(v)) { puts("ERROR: --consensus-pairs-min takes 1 .. 2147483647"); return 1; }
+			cons_pairs_min = (uint32_t)v; cons_pairs_min_given = 1;
+		}
 		else if (!strcmp(a, "--mates")) { NEEDARG("--mates"); mates_FN = argv[i]; }
 		else if (!strcmp(a, "--insert-min") || !strcmp(a, "--insert-max")) {
 			const int is_max = !strcmp(a, "--insert-max");
@@ -753,6 +793,8 @@ int main(int argc, char **argv) {
 	if (var_prefix && mates_FN) { puts("ERROR: --variants of paired output are out of scope: they do not go with --mates"); return 1; }
 	/* (--consensus calls from the same paths, traced on the same handle: it refuses what --variants refuses, and the self-alignment outputs) */
 	if (cons_opts_given && !cons_prefix) { puts("ERROR: --consensus-min-depth, --consensus-min-breadth, --consensus-reads and --consensus-lengths go with --consensus <prefix>"); return 1; }
+	if ((cons_pairs || cons_pairs_min_given) && !cons_prefix) { puts("ERROR: --consensus-pairs and --consensus-pairs-min go with --consensus <prefix>"); return 1; }
+	if (cons_pairs_min_given && !cons_pairs) { puts("ERROR: --consensus-pairs-min goes with --consensus-pairs"); return 1; }
 	if (cons_prefix && (makedb || mkacx_FN || xalpha)) { puts("ERROR: --consensus calls from the lines of an alignment run: it does not go with -d, --make-acx or -x"); return 1; }
 	if (cons_prefix && (shard_db || n_shards)) { puts("ERROR: --consensus traces the paths on rank 0's handle, which must hold the whole database: it does not go with --shard db or --shards"); return 1; }
 	if (cons_prefix && !gather_host) { puts("ERROR: --consensus takes the host gather only (drop --gather rccl)"); return 1; }
@@ -815,7 +857,7 @@ int main(int argc, char **argv) {
 		                  query_FN, mates_FN, output_FN, mopts, mates_opts_given, em_prefix, em_iters, em_tol,
 		                  var_prefix, var_min_depth, var_min_alt, var_unique, sam, sam_unmapped, sam_lengths,
 		                  cons_prefix, cons_min_depth, cons_min_breadth, cons_unique, cons_lengths,
-		                  vcf, vcf_min_depth, vcf_min_alt, vcf_unique, vcf_lengths, taxa_prefix, (uint32_t)taxa_agree, vcf_study};
+		                  vcf, vcf_min_depth, vcf_min_alt, vcf_unique, vcf_lengths, taxa_prefix, (uint32_t)taxa_agree, vcf_study, cons_pairs, cons_pairs_min};
 		return samples_main(&sa);
 	}
 	if (mkacx_FN) {   /* (re)build an accelerator for an existing .edx:  burst_hip -r DB.edx --make-acx DB.acx [-k 12|15] [-y] */
@@ -951,7 +993,7 @@ int main(int argc, char **argv) {
 	if (em_prefix && (rc = bh_em_open(&db, em_prefix, em_iters, em_tol, &em))) DIEJ(rc);
 	BhTaxa *taxa = NULL;      /* (the tree of the map's strings: a string of too many levels is refused before a device is touched) */
 	if (taxa_prefix && (rc = bh_taxa_open(&db, taxa_prefix, &taxonomy, txo.ncbi, (uint32_t)taxa_agree, &taxa))) { JOIN_INGEST(); if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
-	if (cons_prefix) { const int e = open_consensus(&db, cons_prefix, cons_lengths, cons_min_depth, cons_min_breadth, cons_unique); if (e) { JOIN_INGEST(); return e; } }
+	if (cons_prefix) { const int e = open_consensus(&db, cons_prefix, cons_lengths, cons_min_depth, cons_min_breadth, cons_unique, cons_pairs ? cons_pairs_min : 0); if (e) { JOIN_INGEST(); return e; } }
 	if (vcf) { const int e = open_vcf(&db, vcf_lengths, vcf_min_depth, vcf_min_alt, vcf_unique); if (e) { JOIN_INGEST(); return e; } }
 	if (vcf_study) { const int e = open_vcfstudy(vcf_study); if (e) { JOIN_INGEST(); return e; } }
 	if (sam) {      /* (before a device is touched: two headers of one name, a lengths table without a header) */
@@ -1119,11 +1161,14 @@ int main(int argc, char **argv) {
 		bh_pile_close(pile); pile = NULL;
 	}
 	if (g_cons) {   /* a study of one sample: its block, then both files get their names (a failure: the exit handler removes the temporary files) */
-		if ((rc = bh_consensus_sample(g_cons, hhs[0], output_FN, Q.codes, Q.qoff, Q.numEntries)) || (rc = bh_consensus_write(g_cons))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
+		if ((rc = bh_consensus_sample(g_cons, hhs[0], output_FN, Q.codes, Q.qoff, Q.numEntries)) || (g_conspairs && (rc = bh_consensus_pairs(g_cons, hhs[0]))) || (rc = bh_consensus_write(g_cons)))
+			{ if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }
 		bh_consensus_print_info(g_cons);
+		if (g_conspairs) bh_conspairs_print_info(g_conspairs);      /* (a study of one sample: no pair, 1 x 1 matrices) */
 		printf("Consensus written: %sconsensus.fa, %sconsensus.txt\n", cons_prefix, cons_prefix);
+		if (g_conspairs) printf("Consensus pairs written: %sconsensus_pairs.txt, %sconsensus_identity.txt, %sconsensus_compared.txt\n", cons_prefix, cons_prefix, cons_prefix);
 		PHASE("consensus");
-		bh_consensus_close(g_cons); g_cons = NULL;
+		close_consensus();
 	}
 	if (g_vcf) {    /* OUT.vcf: written under a temporary name, renamed when it is whole (a failure leaves none) */
 		if ((rc = bh_vcf_sample(g_vcf, hhs[0], output_FN, Q.codes, Q.qoff, Q.numEntries))) { if (rc == BH_E_USAGE) { puts(bh_last_error()); fflush(NULL); return 1; } DIE(rc); }

@@ -386,6 +386,22 @@ def lib():
         L.bh_consensus_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         L.bh_session_set_consensus.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_conspairs_check_min.argtypes = [C.c_uint64]
+        L.bh_conspairs_check_names.argtypes = [C.POINTER(C.c_char_p), C.c_uint64]
+        L.bh_conspairs_open.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.bh_conspairs_set_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bh_conspairs_set_solver.restype = None
+        L.bh_conspairs_attach.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_conspairs_attach.restype = None
+        for name in ("bh_conspairs_abort", "bh_conspairs_print_info", "bh_conspairs_close"):
+            getattr(L, name).argtypes = [C.c_void_p]
+            getattr(L, name).restype = None
+        L.bh_conspairs_last_info.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.bh_conspairs_last_info.restype = None
+        L.bh_conspairs_written.argtypes = [C.c_void_p]
+        L.bh_consensus_pairs.argtypes = [C.c_void_p, C.c_void_p]
+        L.bh_session_consensus_pairs.argtypes = [C.c_void_p]
+        L.bh_consensus_pairs_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         L.bh_vcf_open.argtypes = [C.POINTER(BhDb), C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.bh_vcf_open_heads.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.bh_vcf_set_solver.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -718,6 +734,25 @@ def consensus_host(refs, q_codes, q_off, lines, ops, min_depth=4, seg_cap=None, 
 
 
 VCF_INFO = ("lines", "events", "distinct", "alleles", "snv", "del", "ins", "skipped_end", "skipped_adjacent", "skipped_long", "device_us", "peak_bytes")
+
+
+CONS_PAIRS_INFO = ("samples", "failed", "records", "headers", "union_positions", "examined", "pairs", "host_bytes")
+
+
+def consensus_pairs_host(n_samples, segs, letters, min_compared=1, pair_cap=None):
+    """bh_consensus_pairs_host, bhip_consensus_pairs' definition in plain sequential C (no device; a dense row per (sample, header) and a
+    double loop over the samples): (pairs capi.PAIR_DTYPE, info uint64 [8]).  Arguments as capi.Device.consensus_pairs takes them"""
+    segs, letters = capi.pair_arrays(segs, letters)
+    pair_cap = 1024 if pair_cap is None else int(pair_cap)
+    for attempt in range(2):
+        pairs, n, info = np.zeros(max(pair_cap, 1), capi.PAIR_DTYPE), C.c_uint64(0), np.zeros(8, np.uint64)
+        rc = lib().bh_consensus_pairs_host(None, int(n_samples), segs.ctypes.data, len(segs), letters.ctypes.data, len(letters), int(min_compared), pairs.ctypes.data, pair_cap,
+                                           C.byref(n), info.ctypes.data)
+        if rc != E_CAPACITY or attempt:
+            break
+        pair_cap = int(n.value)
+    _chk(rc)
+    return pairs[:n.value], info
 
 
 VCF_STUDY_INFO = ("samples", "failed", "snv", "del", "ins", "cells", "host_bytes", "device_us")
@@ -1121,6 +1156,7 @@ class Session:
                  chimeras=None, chimera_sizes=False, chimera_skew=2, chimera_min_seg=16, chimera_min_gain=3, chimera_host=False,
                  sam=False, sam_unmapped=False, sam_lengths=None, sam_md=None,
                  consensus=None, consensus_min_depth=4, consensus_min_breadth=0, consensus_reads="all", consensus_lengths=None, consensus_host=False,
+                 consensus_pairs=False, consensus_pairs_min=1, consensus_pairs_host=False,
                  vcf=False, vcf_min_depth=4, vcf_min_alt=2, vcf_reads="all", vcf_lengths=None, vcf_host=False, vcf_study=None, vcf_study_host=False,
                  taxa=None, taxa_agree=1000, taxa_host=False):
         """cigar: every line of every output carries two further columns, the leftmost 1-based position of its alignment path on the original
@@ -1159,6 +1195,11 @@ class Session:
         consensus_lengths: a `name<TAB>length` table, default the database's own extents), from ONE bhip_consensus_run per sample on rank
         0's device handle -- or bh_consensus_host with consensus_host=True; consensus() returns the table's rows so far, close() writes both
         files unless the session ended on an error.  Same limits as variants; goes with them, coverage, abundance, cigar and sam.
+        consensus_pairs=True (goes with consensus=prefix): the segments and letters of every written record are kept in host memory, and
+        consensus_pairs() -- or close() -- compares every two samples' rows per reference (bh_conspairs.c: Compared = positions where both
+        show one of A C G T -, Same = equal ones; pair rows with Compared >= consensus_pairs_min) with ONE bhip_consensus_pairs call on rank
+        0's device handle -- or bh_consensus_pairs_host with consensus_pairs_host=True -- and leaves prefix + "consensus_pairs.txt",
+        "consensus_identity.txt" and "consensus_compared.txt", named together with the two consensus files by close().
         vcf: every reported sample's output OUT gets OUT.vcf beside it (bh_vcf.c: VCFv4.2, one sample, no genotypes; an SNV record where a
         base other than an A/C/G/T reference base has vcf_min_alt reads, a record per deletion and per insertion of at most 15 symbols with
         vcf_min_alt reads, at positions of vcf_min_depth reads; vcf_reads "unique": only reads printed on one line; vcf_lengths: a
@@ -1177,6 +1218,12 @@ class Session:
         error; taxa() returns names, depths and the integer columns.  Not with mates, cluster or chimeras."""
         if vcf_study is not None and not vcf:
             raise ValueError("vcf_study goes with vcf=True")
+        if (consensus_pairs or int(consensus_pairs_min) != 1) and consensus is None:
+            raise ValueError("consensus_pairs and consensus_pairs_min go with consensus=prefix")
+        if int(consensus_pairs_min) != 1 and not consensus_pairs:      # (as the command line refuses --consensus-pairs-min without --consensus-pairs)
+            raise ValueError("consensus_pairs_min goes with consensus_pairs=True")
+        if consensus_pairs and not 1 <= int(consensus_pairs_min) < 1 << 31:
+            raise ValueError("consensus_pairs_min: 1 .. 2^31 - 1")
         self.db, self.h, self._cb, self.node = db, C.c_void_p(), [], node
         self._mates_join = mates_join
         self.cov, self.em, self.pile, self.cluster, self.chimera = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -1218,6 +1265,7 @@ class Session:
         self.ended = False
         self.cov_aborted = False
         self.cons = C.c_void_p()
+        self.conspairs = C.c_void_p()
         self.vcf = C.c_void_p()
         self.vcfstudy = C.c_void_p()
         if coverage is not None and (rank == 0 or len(devs) > 1):      # (in a job of processes the lines exist only where rank 0 reports)
@@ -1295,6 +1343,11 @@ class Session:
             if consensus_host:
                 self._cons_refs = BhPileRefs(C.cast(db.c.packed, C.c_void_p), C.cast(db.c.clumpLen, C.c_void_p), db.c.numRclumps, db.c.totR)
                 lib().bh_consensus_set_solver(self.cons, C.cast(lib().bh_consensus_host, C.c_void_p), C.cast(C.pointer(self._cons_refs), C.c_void_p))
+            if consensus_pairs:
+                _chk(lib().bh_conspairs_open(consensus.encode(), int(consensus_pairs_min), C.byref(self.conspairs)))
+                if consensus_pairs_host:
+                    lib().bh_conspairs_set_solver(self.conspairs, C.cast(lib().bh_consensus_pairs_host, C.c_void_p), None)
+                lib().bh_conspairs_attach(self.conspairs, self.cons)
         if vcf_lengths and not vcf:
             raise ValueError("vcf_lengths goes with vcf=True")
         if vcf:
@@ -1345,7 +1398,7 @@ class Session:
             if self.h:
                 lib().bh_session_close(self.h)
                 self.h = C.c_void_p()
-            for name, close in (("sam", lib().bh_sam_close), ("taxa_obj", lib().bh_taxa_close), ("vcfstudy", lib().bh_vcfstudy_close), ("vcf", lib().bh_vcf_close), ("cons", lib().bh_consensus_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
+            for name, close in (("sam", lib().bh_sam_close), ("taxa_obj", lib().bh_taxa_close), ("vcfstudy", lib().bh_vcfstudy_close), ("vcf", lib().bh_vcf_close), ("cons", lib().bh_consensus_close), ("conspairs", lib().bh_conspairs_close), ("cluster", lib().bh_cluster_close), ("chimera", lib().bh_chimera_close)):
                 if getattr(self, name):
                     close(getattr(self, name))
                     setattr(self, name, C.c_void_p())
@@ -1527,6 +1580,26 @@ class Session:
         lib().bh_consensus_rows(self.cons, rows.ctypes.data, n)
         return rows[:n]
 
+    def consensus_pairs(self):
+        """when every sample has been reported: ONE bhip_consensus_pairs call over the kept rows on rank 0's device handle (or
+        bh_consensus_pairs_host with consensus_pairs_host=True) and prefix + "consensus_pairs.txt", "consensus_identity.txt" and
+        "consensus_compared.txt" under temporary names (once: the kept rows are released, and no further sample can be reported); close()
+        gives them and the two consensus files their names together.  Returns the figures: samples (done), failed, records (that take
+        part), headers (with two or more), union_positions, examined, pairs (written), host_bytes (kept), device_us"""
+        if not self.conspairs:
+            raise HostError("the session has no consensus pairs")
+        if lib().bh_session_ended(self.h):
+            raise HostError("the session ended on an error: no consensus pairs are written")
+        _chk(lib().bh_session_consensus_pairs(self.h))
+        return self.consensus_pairs_info()
+
+    def consensus_pairs_info(self):
+        info, us = np.zeros(8, np.uint64), C.c_uint64()
+        lib().bh_conspairs_last_info(self.conspairs, info.ctypes.data, C.byref(us))
+        d = dict(zip(CONS_PAIRS_INFO, (int(x) for x in info)))
+        d["device_us"] = us.value
+        return d
+
     def consensus_info(self):
         """the last called sample's figures: events, candidates, segments, covered, device_us, peak_bytes, lines, records"""
         info, lines, records = np.zeros(8, np.uint64), C.c_uint64(), C.c_uint64()
@@ -1622,10 +1695,14 @@ class Session:
                 lib().bh_pile_close(self.pile)
                 self.pile = C.c_void_p()
             if self.cons:
-                if not lib().bh_session_ended(self.h) and not self.cov_aborted and lib().bh_consensus_write(self.cons):
-                    err = lib().bh_last_error().decode("utf-8", "replace")
+                if not lib().bh_session_ended(self.h) and not self.cov_aborted:     # (the pairs before the handles go, then all files get their names)
+                    if (self.conspairs and not lib().bh_conspairs_written(self.conspairs) and lib().bh_session_consensus_pairs(self.h)) or lib().bh_consensus_write(self.cons):
+                        err = lib().bh_last_error().decode("utf-8", "replace")
                 lib().bh_consensus_close(self.cons)
                 self.cons = C.c_void_p()
+                if self.conspairs:
+                    lib().bh_conspairs_close(self.conspairs)
+                    self.conspairs = C.c_void_p()
             if self.vcfstudy:     # (before the handles go: the counts are taken on rank 0's)
                 if not getattr(self, "_vcfstudy_written", False) and not lib().bh_session_ended(self.h) and not self.cov_aborted and lib().bh_vcfstudy_write(self.vcfstudy, self.vcf, self.ranks[0].hh):
                     err = lib().bh_last_error().decode("utf-8", "replace")

@@ -229,6 +229,8 @@ def main(argv=None):
     ap.add_argument("--consensus-min-breadth", metavar="PERMILLE", help="not available here: goes with burst_hip --consensus")
     ap.add_argument("--consensus-reads", metavar="all|unique", help="not available here: goes with burst_hip --consensus")
     ap.add_argument("--consensus-lengths", metavar="FILE", help="not available here: goes with burst_hip --consensus")
+    ap.add_argument("--consensus-pairs", action="store_true", help="not available here: goes with burst_hip --consensus")
+    ap.add_argument("--consensus-pairs-min", metavar="N", help="not available here: goes with burst_hip --consensus --consensus-pairs")
     ap.add_argument("--vcf", action="store_true", help="not available here: VCF records are written by burst_hip --vcf (one process, the host gather)")
     ap.add_argument("--vcf-min-depth", metavar="N", help="not available here: goes with burst_hip --vcf")
     ap.add_argument("--vcf-min-alt", metavar="N", help="not available here: goes with burst_hip --vcf")
@@ -238,6 +240,9 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.vcf or args.vcf_min_depth or args.vcf_min_alt or args.vcf_reads or args.vcf_lengths or args.vcf_study:      # (exit code 1, as burst_hip refuses what it cannot do)
         print("ERROR: --vcf is not available in python -m burst_amd.run: use burst_hip --vcf (one process, --gpus N with the host gather)", flush=True)
+        return 1
+    if args.consensus_pairs or args.consensus_pairs_min:      # (exit code 1, as burst_hip refuses what it cannot do)
+        print("ERROR: --consensus-pairs is not available in python -m burst_amd.run: use burst_hip --consensus PREFIX --consensus-pairs (one process, --gpus N with the host gather)", flush=True)
         return 1
     if args.consensus or args.consensus_min_depth or args.consensus_min_breadth or args.consensus_reads or args.consensus_lengths:      # (exit code 1, as burst_hip refuses what it cannot do)
         print("ERROR: --consensus is not available in python -m burst_amd.run: use burst_hip --consensus (one process, --gpus N with the host gather)", flush=True)

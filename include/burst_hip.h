@@ -504,6 +504,49 @@ BHIP_API int bhip_consensus_run(void *handle, const uint8_t *q_codes, const uint
                                 uint64_t info[8]);
 BHIP_API int bhip_consensus_info(void *handle, uint64_t info[8]);
 
+/* Consensus pairs: for every reference and every two samples, on how many positions both consensus rows show a call and on how many of
+ * those they agree (burst_hip --consensus --consensus-pairs; no reference counterpart).  A pure function of the written
+ * PREFIXconsensus.fa, all integer arithmetic, bit-exact on any machine.
+ *   PARTICIPANT   a (sample, header) whose record --consensus writes (Called >= 1 and the --consensus-min-breadth test passes).  Its ROW
+ *                 is the record's L letters: the letters bhip_consensus_run returned inside the segments, N everywhere else.
+ *   COMPARABLE    a position of a row whose byte is one of A C G T - (rule 3 of the call).  N is not comparable, and neither are the
+ *                 ambiguity letters of rule 2: both samples would show the reference's own letter there, which says nothing.
+ *   FIGURES       for samples a < b (study order) that both take part on header h: Compared = the positions comparable in both rows, Same =
+ *                 those of them with equal bytes ('-' against '-' is equal, '-' against a base is not), Differ = Compared - Same.
+ *   PAIR ROW      exists when Compared >= M = --consensus-pairs-min (1 .. 2^31 - 1, default 1; policy, not a measurement).
+ *   FILES         PREFIXconsensus_pairs.txt: `#Reference SampleA SampleB Length Compared Same Differ Identity` (tabs), rows in strcmp order
+ *                 of the whole header, then a, then b; Identity = %.6f of (double)Same / (double)Compared.  PREFIXconsensus_identity.txt:
+ *                 `#Identity` and the samples' names (those of the coverage tables), a row per sample; cell (a, b), a != b, = %.6f of
+ *                 sum Same / sum Compared (64-bit sums) over the pair's rows in the pairs file, NA when it has none; the diagonal is
+ *                 1.000000.  PREFIXconsensus_compared.txt: the same shape with the integer sum Compared (0 where the other has NA); its
+ *                 diagonal is the number of comparable positions of the sample's records.  Both are symmetric.  A sample that failed alone
+ *                 takes part nowhere: its whole row and column, the diagonal included, read NA in both matrices.
+ * THE PRIMITIVE.  segs: strictly ascending by (sample, header, pos), within a (sample, header) pos >= the previous pos + len, pos >= 1,
+ * len >= 1; segment s owns letters[off .. off + len); `header` is any number that orders the headers (the consensus's header numbers are
+ * their places in strcmp order).  pairs: ascending (header, a, b), only those with compared >= min_compared.
+ * The cost follows segments + covered positions + participating pairs x the words of their header's union, never a reference's length
+ * (csrc/bhip_conspairs.hip): per header the union of all samples' segments gives a compressed axis; every (sample,
+ * header) gets three code planes of 64-bit words over it; a workgroup owns a tile of sample pairs of one header, stages the tile's rows
+ * through LDS and counts with popcounts; the selection is by key.  Integer sums only: no order of threads, and no budget, changes a byte.
+ * Option "conspairs_bytes" (bhip_set_option; default 1 GiB, a stated policy) bounds the plane buffer: headers are processed in groups
+ * that fit; a header too large alone goes in consecutive slabs of words while its pair cells stay resident (a value below one word of
+ * every row of a header, 24 bytes x its samples, acts as that).  Copies of the input and the pair cells of a group are beside it.
+ * BHIP_E_ARG with a text, before any device memory is touched and with the handle staying usable: segments out of order or overlapping,
+ * pos == 0, len == 0, pos + len > 2^32 - 1, off + len beyond n_letters, sample >= n_samples, n_samples > 65535 (policy), min_compared == 0
+ * or > 2^31 - 1, 2^32 or more segments.  (pos + len <= 2^32 - 1 is one position short of what --consensus itself takes: a record
+ * called through position 2^32 - 1 is refused by the run with a usage message when it is handed over.)  n_samples < 2 or n_segs == 0: nothing is launched, no pairs.  BHIP_E_CAPACITY when pair_cap is
+ * too small: *n_pairs is the number wanted, nothing is written, the handle stays usable (the sum of m (m - 1) / 2 over the headers with m
+ * participants always suffices).
+ * info (may be NULL; bhip_consensus_pairs_info returns that of the last call on the handle): [0] segments, [1] headers with at least two
+ * samples, [2] union positions of those headers, [3] pairs examined, [4] pairs returned, [5] device microseconds (HIP events around
+ * everything launched), [6] peak device bytes of the scratch buffers (the handle keeps them; bhip_destroy frees them), [7] 0. */
+typedef struct BhipPairSeg { uint32_t sample, header, pos, len; uint64_t off; } BhipPairSeg;
+typedef struct BhipPair    { uint32_t header, a, b, pad; uint32_t compared, same; } BhipPair;
+BHIP_API int bhip_consensus_pairs(void *handle, uint32_t n_samples, const BhipPairSeg *segs, uint64_t n_segs, const char *letters,
+                                  uint64_t n_letters, uint32_t min_compared, BhipPair *pairs, uint64_t pair_cap, uint64_t *n_pairs,
+                                  uint64_t info[8]);
+BHIP_API int bhip_consensus_pairs_info(void *handle, uint64_t info[8]);
+
 /* Indel alleles: which bases one sample's reads insert behind a reference position, and which reference columns they delete there
  * (burst_hip --vcf; no reference counterpart: the definition is this project's own).  A function of the sample's printed lines, all
  * integer arithmetic, bit-exact on any machine.  Lines, the walk (reference position p, query index j), observations, Depth, Ref and the
